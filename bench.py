@@ -4,21 +4,23 @@
 Headline (``--mode infer``, the default): one step = one batch of B synthetic rendered-glyph
 strips (B x 1 x 24 x 102*T_src, T_src=12) through the acoustic model (teacher-forced durations
 summing to T_mel=512 frames, predicted energy) and the HiFi-GAN V1
-generator on its postnet mel (config C3 shape per utterance) -> B x 131,072 samples.  The same
-run also measures BASELINE.json's per-config lines C2 (acoustic only, B=32, mel-frames/s),
-C3 (generator only, B=64 x 80 x 512, samples/s) and -- on one GPU -- C4 (the acoustic training
-step, B=32 x 512 frames) and C5 (the HiFi-GAN V1 training step, B=16 x 8192 samples) as graphed
+generator on its postnet mel (config C3 shape per utterance) -> B x 131,072 samples.  A plain run
+sets up, warms up, times the steps, writes the last timed step's outputs (``--dump-outputs DIR``)
+and prints the line.  With ``--full`` the same run adds a roofline pass (per-kernel HIP events,
+outside the timed region), the CPU baseline and BASELINE.json's per-config lines C2 (acoustic
+only, B=32, mel-frames/s), C3 (generator only, B=64 x 80 x 512, samples/s) and -- on one GPU --
+C4 (the acoustic training step, B=32 x 512 frames) and C5 (the HiFi-GAN V1 training step, B=16 x 8192 samples) as graphed
 single-GPU steps, each with its own roofline, under ``configs`` of the one JSON line.  Inputs are resident in HBM before every timed region.
 Multi-GPU: one process per GPU (torchrun), every rank synthesises its own batch (utterances
 are independent: replicas, no data-path collective), only the timing uses a
 barrier and a MAX all-reduce.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--precision mixed]
-                    [--mode infer|c2|c3|train|gan] [--comm-dtype fp32|bf16]
+                    [--mode infer|c2|c3|train|gan] [--comm-dtype fp32|bf16] [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (rank 0) with the metric of BASELINE.json, the dominant kernel's
-roofline (HIP events on the launching stream over the timed region) and the CPU baseline
-(the oracle restatement timed on this host: BASELINE.md's C1 / C2 / C3 plan).
+Prints ONE JSON line (rank 0) with the metric of BASELINE.json and ``ms_per_step`` and, with
+``--full``, the dominant kernel's roofline (HIP events on the launching stream in a pass of its
+own) and the CPU baseline (the oracle restatement timed on the host: BASELINE.md's C1 / C2 / C3 plan).
 """
 
 import argparse
@@ -72,6 +74,12 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: every rank joins a gloo group, the ranks are "
                          "all-gathered and rank 0 prints them (no model, no CUDA call)")
+    ap.add_argument("--full", action="store_true",
+                    help="infer / c2 / c3: also run what the headline figure does not need -- the roofline pass "
+                         "with per-kernel events, the C2 / C3 / C4 / C5 sub-measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample where the outputs exceed 64 MB in all)")
     ap.add_argument("--mode", default="infer", choices=["infer", "c2", "c3", "train", "gan"],
                     help="infer: end-to-end synthesis (headline, with C2 / C3 sub-lines); c2: acoustic model "
                          "only; c3: HiFi-GAN generator only (B=64); train: C4 training step (DDP); "
@@ -100,6 +108,43 @@ def timed(fn, steps, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed, out
+
+
+DUMP_MAX_BYTES = 63 * 1000 * 1000  # with the .npy headers: under 64 MB in all
+
+
+def _named_outputs(out, prefix="out"):
+    """Flatten what a timed step returned (tensor, number, tuple / list, dict) into {name: tensor}."""
+    if torch.is_tensor(out):
+        return {prefix: out}
+    if isinstance(out, (int, float)):
+        return {prefix: torch.tensor(float(out))}
+    named = {}
+    if isinstance(out, dict):
+        for k, v in out.items():
+            named.update(_named_outputs(v, f"{prefix}_{k}"))
+    elif isinstance(out, (tuple, list)):
+        for i, v in enumerate(out):
+            named.update(_named_outputs(v, f"{prefix}{i}"))
+    return named  # None and other non-array entries are not outputs
+
+
+def dump_outputs(dirname, out, prefix="out"):
+    """--dump-outputs: the arrays of the last timed step as DIR/<name>.npy in float32.  Past 64 MB in
+    all every array is cut to its share of the budget: elements at fixed, seeded flat indices (the
+    same for every run with the same arguments), written as a 1-D array."""
+    if dirname is None or int(os.environ.get("RANK", "0")) != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    named = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in _named_outputs(out, prefix).items()}
+    total = sum(v.size for v in named.values())
+    budget = DUMP_MAX_BYTES // 4
+    rng = np.random.default_rng(1234)
+    for name, v in named.items():
+        if total > budget:
+            keep = max(1, budget * v.size // total)
+            v = v.reshape(-1)[np.sort(rng.choice(v.size, size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
 
 
 def _pmc_traffic():
@@ -281,22 +326,28 @@ def measure_c2(a, dev, dist, model=None):
             out = gout
         else:
             elapsed, out = timed(lambda: model(*args), a.steps, dist)
-        # roofline pass: HIP events around each decoder FFN w_1 launch, outside the timed region
-        timer = KernelTimer(["dec_ffn_w1"] if not a.no_kernel_timer else [])
-        with timer:
-            timed(lambda: model(*args), a.steps, dist)
+        if a.mode == "c2":
+            dump_outputs(a.dump_outputs, out)
+        roof = None
+        if a.full:
+            # roofline pass: HIP events around each decoder FFN w_1 launch, outside the timed region
+            timer = KernelTimer(["dec_ffn_w1"] if not a.no_kernel_timer else [])
+            with timer:
+                timed(lambda: model(*args), a.steps, dist)
+            peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
+            roof = roofline(timer.summary(), peak, lambda t: "decoder FFN w_1 conv, k=9 256->1024")
+            if roof is not None:
+                roof["measured_in"] = "separate eager pass with an event pair per w_1 launch (not the timed region)"
     assert torch.isfinite(out[1]).all()
     world = dist.get_world_size() if dist else 1
     frames = B * a.mel_len * a.steps * world
-    peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
     return {"metric": "C2 acoustic forward mel-frames/sec (vTTS, batch 32, teacher-forced T_mel=512)",
             "value": round(frames / elapsed, 1), "unit": "mel-frames/s", "ms_per_step": round(elapsed / a.steps * 1e3, 3),
             "per_gpu_batch": B, "tflops_step": round(771.4e9 * B / 32 / (elapsed / a.steps) / 1e12, 1),
             "hip_graph": hip_graph,
             # rounds <= 4 timed eager forwards; from round 5 the timed region replays one HIP graph
             "timing_mode": "hip_graph_replay" if hip_graph else "eager",
-            "roofline": dict(roofline(timer.summary(), peak, lambda t: "decoder FFN w_1 conv, k=9 256->1024"),
-                             measured_in="separate eager pass with an event pair per w_1 launch (not the timed region)")}
+            "roofline": roof}
 
 
 def measure_c3(a, dev, dist, gen=None):
@@ -313,25 +364,30 @@ def measure_c3(a, dev, dist, gen=None):
         for _ in range(a.warmup):
             gen(mel)
         elapsed, wav = timed(lambda: gen(mel), a.steps, dist)
-        # roofline pass with per-stage events, MRF chains serialized (see infer)
-        timer = KernelTimer([f"mrf_s{i}" for i in range(4)] if not a.no_kernel_timer else [])
-        streams, hm.MRF_STREAMS = hm.MRF_STREAMS, False
-        try:
-            gen(mel)
-            with timer:
-                timed(lambda: gen(mel), a.steps, dist)
-        finally:
-            hm.MRF_STREAMS = streams
+        if a.mode == "c3":
+            dump_outputs(a.dump_outputs, wav, "wav")
+        roof = None
+        if a.full:
+            # roofline pass with per-stage events, MRF chains serialized (see infer)
+            timer = KernelTimer([f"mrf_s{i}" for i in range(4)] if not a.no_kernel_timer else [])
+            streams, hm.MRF_STREAMS = hm.MRF_STREAMS, False
+            try:
+                gen(mel)
+                with timer:
+                    timed(lambda: gen(mel), a.steps, dist)
+            finally:
+                hm.MRF_STREAMS = streams
+            peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
+            roof = roofline(timer.summary(), peak, _mrf_label, batch=B)
     assert wav.shape == (B, 1, a.mel_len * HOP) and torch.isfinite(wav).all()
     world = dist.get_world_size() if dist else 1
     samples = B * a.mel_len * HOP * a.steps * world
-    peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
     return {"metric": "C3 HiFi-GAN generator audio samples/sec (batch 64 x 80-mel x 512-frame)",
             "value": round(samples / elapsed, 1), "unit": "audio samples/s",
             "ms_per_step": round(elapsed / a.steps * 1e3, 3), "per_gpu_batch": B,
             "x_realtime": round(samples / elapsed / SR, 1),
             "tflops_step": round(2398848.0 * B * a.mel_len * HOP / (elapsed / a.steps) / 1e12, 1),
-            "roofline": roofline(timer.summary(), peak, _mrf_label, batch=B)}
+            "roofline": roof}
 
 
 # ----------------------------------------------------------------------------------- training configs
@@ -432,6 +488,8 @@ def run_train(a, dev, rank, world, dist, B=None):
     for _ in range(a.warmup):
         run(batch)
     elapsed, losses = timed(lambda: run(batch), a.steps, dist)
+    if a.mode == "train":
+        dump_outputs(a.dump_outputs, losses, "loss")
     frames = B * a.mel_len * a.steps * world
     n_grad = sum(p.numel() for p in (bk.params if bk else []))
     ms = elapsed / a.steps * 1e3
@@ -481,6 +539,8 @@ def run_gan(a, dev, rank, world, dist, B=None):
     for _ in range(a.warmup):
         run(x, y)
     elapsed, losses = timed(lambda: run(x, y), a.steps, dist)
+    if a.mode == "gan":
+        dump_outputs(a.dump_outputs, losses, "loss")
     samples = B * seg * a.steps * world
     ms = elapsed / a.steps * 1e3
     peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
@@ -663,28 +723,32 @@ def infer(a, dev, rank, world, dist):
             step()
         elapsed, wav = timed(step, a.steps, dist)  # the headline: no kernel timer in the timed region
         assert wav.shape == (a.batch, a.mel_len * HOP) and torch.isfinite(wav).all()
-        # roofline pass: the same step run sequentially (acoustic model then vocoder on one stream, the
-        # C = 256 MRF chains one after another), per-stage HIP events on the launching stream -- so
-        # each kernel's duration is its own, as in the serialized rocprofv3 trace under profiles/
-        timer = KernelTimer([f"mrf_s{i}" for i in range(4)] if not a.no_kernel_timer else [])
-        streams, hm.MRF_STREAMS = hm.MRF_STREAMS, False
-        try:
-            seq_step()
-            with timer:
-                roof_elapsed, _ = timed(seq_step, a.steps, dist)
-        finally:
-            hm.MRF_STREAMS = streams
+        dump_outputs(a.dump_outputs, wav, "wav")
+        roof = None
+        if a.full:
+            # roofline pass: the same step run sequentially (acoustic model then vocoder on one stream, the
+            # C = 256 MRF chains one after another), per-stage HIP events on the launching stream -- so
+            # each kernel's duration is its own, as in the serialized rocprofv3 trace under profiles/
+            timer = KernelTimer([f"mrf_s{i}" for i in range(4)] if not a.no_kernel_timer else [])
+            streams, hm.MRF_STREAMS = hm.MRF_STREAMS, False
+            try:
+                seq_step()
+                with timer:
+                    roof_elapsed, _ = timed(seq_step, a.steps, dist)
+            finally:
+                hm.MRF_STREAMS = streams
+            peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
+            roof = roofline(timer.summary(), peak, _mrf_label, batch=a.batch)
+            if roof is not None:
+                roof["measured_in"] = (f"sequential roofline pass ({a.steps} steps, "
+                                       f"{roof_elapsed / a.steps * 1e3:.3f} ms per step with events): no "
+                                       "acoustic/vocoder overlap, MRF chains serialized")
     samples = a.batch * a.mel_len * HOP * a.steps * world
     frames = a.batch * a.mel_len * a.steps * world
     value = samples / elapsed
-    peak = F32_PEAK_TFLOPS if a.precision == "fp32" else BF16_PEAK_TFLOPS
-    roof = roofline(timer.summary(), peak, _mrf_label, batch=a.batch)
-    if roof is not None:
-        roof["measured_in"] = (f"sequential roofline pass ({a.steps} steps, {roof_elapsed / a.steps * 1e3:.3f} ms per "
-                               "step with events): no acoustic/vocoder overlap, MRF chains serialized")
 
     configs = None
-    if not a.no_configs:  # BASELINE.json's per-config lines, same run, same models
+    if a.full and not a.no_configs:  # BASELINE.json's per-config lines, same run, same models
         configs = {"C2": measure_c2(a, dev, dist, model), "C3": measure_c3(a, dev, dist, gen)}
         if world == 1 and not a.no_train_configs:
             # C4 / C5 as single-GPU graphed steps (BASELINE.json configs 4 and 5 at their per-GPU
@@ -694,7 +758,7 @@ def infer(a, dev, rank, world, dist):
             configs["C5"] = run_gan(a, dev, rank, world, dist, B=16)
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0:
         cpu = cpu_baseline(a.cpu_seconds, a.src_len, a.mel_len, a.batch)
 
     if rank == 0:

@@ -10,5 +10,7 @@ tail -2 gpurun_out/x3/parity.log
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_train_sizes.py tests/test_gpu_train.py > gpurun_out/x3/train.log 2>&1 || { tail -40 gpurun_out/x3/train.log; exit 1; }
 tail -3 gpurun_out/x3/train.log
 bash tools/c4_prof.sh || exit 1
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --mode c2 --cpu-seconds 0 > gpurun_out/x3/c2.out 2>&1 || { tail -20 gpurun_out/x3/c2.out; exit 1; }
-tail -1 gpurun_out/x3/c2.out | cut -c1-400
+C2_OUT=${OUT:-bench_out}/x3
+mkdir -p "$C2_OUT"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --mode c2 --cpu-seconds 0 > "$C2_OUT/c2.out" 2>&1 || { tail -20 "$C2_OUT/c2.out"; exit 1; }
+tail -1 "$C2_OUT/c2.out" | cut -c1-400

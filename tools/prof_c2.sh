@@ -4,7 +4,7 @@ set -o pipefail
 OUT=gpurun_out/c2prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python bench.py --mode c2 --steps 10 --cpu-seconds 0 > $OUT/bench.out 2>&1 || { tail -20 $OUT/bench.out; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python bench.py --full --mode c2 --steps 10 --cpu-seconds 0 > $OUT/bench.out 2>&1 || { tail -20 $OUT/bench.out; exit 1; }
 python - <<'PY'
 import csv
 rows = list(csv.DictReader(open("gpurun_out/c2prof/run_kernel_stats.csv")))

@@ -10,11 +10,11 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT/pmc"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 export VO_MRF_STREAMS=0
-BENCH="python bench.py --steps 10 --warmup 3 --cpu-seconds 0 --no-configs --no-pipeline"
+BENCH="python bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --no-configs --no-pipeline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $BENCH > "$OUT/trace_bench.out" 2>&1 || { tail -20 "$OUT/trace_bench.out"; exit 1; }
 python tools/trace_tail_stats.py "$OUT/trace/run_kernel_trace.csv" conv_post_rows_kernel 4 3 || exit 1
 rm -f "$OUT/trace/run_kernel_trace.csv"
-PMCB="python bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-configs --no-pipeline"
+PMCB="python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-configs --no-pipeline"
 for c in FETCH_SIZE WRITE_SIZE; do
   lc=$(echo $c | tr 'A-Z' 'a-z')
   for what in bench c2; do
