@@ -112,6 +112,18 @@ typedef struct vo_conv1d_desc {
 int vo_conv1d(const vo_conv1d_desc* d, void* stream);
 /* scratch bytes the split-reduction path of vo_conv1d wants for d (0 = it does not split d) */
 int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d);
+/* The tile the last vo_conv1d call of the calling thread launched (host bookkeeping only: the tests
+ * assert which dispatcher branch a shape took).  Copies min(n, VO_CONV1D_LAUNCH_FIELDS) fields into
+ * rec, in this order: output channels per tile (BCO), output rows per tile (BT), conv stride of the
+ * instantiation (S), utterance-segment tile (SEG, 0 / 1), nice (1 = the instantiation without
+ * channel bounds checks: Ci % 32 == 0 and Co % BCO == 0), reduction splits, sizeof the input, LDS
+ * compute and output element, ROLE (0 = generic, 1..4 = MRF stage), compute dtype (enum vo_dtype),
+ * then the wave tiling that tells apart instantiations of equal BCO x BT: 16-channel MFMA tiles per
+ * wave (NI) and waves across the output channels (WCO); BCO = 16 NI WCO.
+ * All zeros: the call was rejected, or handled outside conv1d_kernel (the streaming upsampler).
+ * Returns the number of fields copied. */
+#define VO_CONV1D_LAUNCH_FIELDS 13
+int vo_conv1d_last_launch(int32_t* rec, int n);
 
 /* Weight preparation (load time).  Replaces the weight-norm fold (remove_weight_norm,
  * scripts/hifigan/models.py:105-109,167-174: w = g * v / ||v||, norm over all dims but 0)

@@ -1,0 +1,250 @@
+"""Every conv1d forward tile the dispatcher ships (launch_types / launch_disc in csrc/conv1d.hip), one NICE
+and one ragged case per instantiation, at its edges against float64 (tests/conv_check.py: bf16-exact
+operands, a derived element-wise bar, rel-L2 < 1e-5 on fp32 output, guard bands around output and input).
+T sits one past a tile multiple, so the last time tile holds a single row.  Every case asserts the launch
+record (ops.conv1d_last_launch) right after the call: a tile-rule change that moves a case onto another
+tile fails here instead of silently dropping coverage.  CASES / REQUIRED are plain data (no GPU at import):
+tests/test_conv_check.py checks REQUIRED against them without one."""
+
+import pytest
+import torch
+
+import conv_check as CC
+from conv_check import ACT_LRELU, ACT_RELU, ACT_TANH, case
+
+pytestmark = pytest.mark.gpu
+
+
+def t_in(To, K, S=1, dil=1, pad=None):
+    """The input length whose natural output length is To."""
+    pad = dil * (K - 1) // 2 if pad is None else pad
+    return (To - 1) * S + dil * (K - 1) + 1 - 2 * pad
+
+
+CASES = []
+
+
+# (NI, WCO) of each tile -- 16-channel MFMA tiles per wave, waves across the output channels; BCO = 16 NI WCO --
+# written by hand from the launch_cfg<..., NI, NJ, WCO, WT, ...> lines of the dispatcher.  Two pairs of tiles
+# share BCO x BT and differ only here: Co = 80 (64 x 128 as 4 x 1) against the bf16 default (2 x 2), and
+# launch_disc's 64 x 64 (4 x 1) against launch_types' (2 x 2).
+WAVE_TYPES = {(128, 16): (2, 4), (32, 16): (1, 2), (128, 32): (2, 4), (32, 256): (2, 1), (64, 256): (4, 1),
+              (64, 64): (2, 2), (64, 128): (2, 2), (128, 256): (4, 2), (256, 256): (4, 4), (128, 128): (4, 2)}
+WAVE_CO80 = (4, 1)
+WAVE_SEG = {(32, 64): (1, 2), (64, 64): (2, 2)}
+WAVE_DISC = {(32, 64): (2, 1), (64, 64): (4, 1), (128, 64): (4, 2), (128, 32): (4, 2)}
+
+
+def add(B, T, Ci, Co, K, io=(("bf16", "bf16", "f32"),), **kw):
+    """One case per (xdt, cdt, ydt) of io."""
+    bco, bt, _, seg = kw["tile"][:4]
+    if kw.get("stride", 1) > 1 or kw.get("groups", 1) > 1:
+        wave = WAVE_DISC[bco, bt]
+    elif seg:
+        wave = WAVE_SEG[bco, bt]
+    else:
+        wave = WAVE_CO80 if (Co == 80 and (bco, bt) == (64, 128)) else WAVE_TYPES[bco, bt]
+    for xdt, cdt, ydt in io:
+        CASES.append(case(B, T, Ci, Co, K, xdt=xdt, cdt=cdt, ydt=ydt, wave=wave, **kw))
+
+
+BB_BF = (("bf16", "bf16", "bf16"), ("bf16", "bf16", "f32"))          # a bf16-output case and its fp32-output twin
+IO4 = BB_BF + (("f32", "bf16", "bf16"), ("f32", "bf16", "f32"))      # the four I/O pairs of bf16 compute
+F32 = (("f32", "f32", "f32"),)
+DISC = (("f32", "f32", "f32"), ("bf16", "bf16", "bf16"), ("bf16", "bf16", "f32"))
+
+# ---------------------------------------------------------------- generic branches, bf16 compute
+# tile = (BCO, BT, S, SEG, nice, splits)
+add(3, 16, 64, 128, 3, io=BB_BF, tile=(128, 16, 1, 0, 1, 1))     # T_out <= 16, Co >= 64
+add(3, 7, 40, 192, 3, io=BB_BF, tile=(128, 16, 1, 0, 0, 1))
+add(2, 32, 64, 128, 3, io=BB_BF, tile=(128, 32, 1, 0, 1, 1))     # T_out <= 32
+add(3, 17, 40, 144, 3, io=BB_BF, tile=(128, 32, 1, 0, 0, 1))
+add(2, 257, 32, 32, 3, io=BB_BF, tile=(32, 256, 1, 0, 1, 1))     # Co <= 32
+add(2, 257, 32, 20, 3, io=BB_BF, tile=(32, 256, 1, 0, 0, 1))     # the lane's 8-channel run crosses the row end
+add(2, 257, 40, 28, 3, io=BB_BF, tile=(32, 256, 1, 0, 0, 1))
+add(2, 257, 32, 64, 3, io=BB_BF, tile=(64, 256, 1, 0, 1, 1))     # Co <= 64
+add(2, 257, 40, 48, 3, io=BB_BF, tile=(64, 256, 1, 0, 0, 1))
+add(2, 129, 64, 80, 5, io=BB_BF, tile=(64, 128, 1, 0, 0, 1))     # Co == 80
+add(2, 65, 64, 128, 3, io=IO4, tile=(64, 64, 1, 0, 1, 1))        # rows <= 2048
+add(2, 65, 40, 144, 3, io=IO4, tile=(64, 64, 1, 0, 0, 1))
+add(9, 257, 64, 256, 1, io=IO4, tile=(64, 128, 1, 0, 1, 1))      # rows > 2048: K = 1, Co <= 256
+add(9, 257, 64, 192, 3, io=BB_BF, tile=(64, 128, 1, 0, 1, 1))    # Co <= 256, Co % 64 == 0, < 512 128-tiles
+add(9, 257, 64, 320, 3, io=BB_BF, tile=(64, 128, 1, 0, 1, 1))    # Co % 64 == 0, < 256 128-tiles
+add(9, 257, 40, 144, 3, io=IO4, tile=(64, 128, 1, 0, 0, 1))      # the bf16 default
+add(22, 257, 32, 512, 3, io=BB_BF, tile=(128, 256, 1, 0, 1, 1))  # 512 <= Co < 768, >= 256 128-tiles
+add(22, 257, 80, 512, 7, io=BB_BF, tile=(128, 256, 1, 0, 0, 1))  # conv_pre
+add(15, 513, 64, 768, 3, io=IO4, tile=(256, 256, 1, 0, 1, 1))    # T_out >= 256, Co >= 768, t256 >= 128
+add(15, 513, 40, 768, 3, io=IO4, tile=(256, 256, 1, 0, 0, 1))
+
+# ---------------------------------------------------------------- generic branches, fp32 compute
+add(3, 16, 64, 128, 3, io=F32, tile=(32, 64, 1, 1, 1, 1))        # SEG, Co < 512: 4 utterances x 32 channels
+add(3, 7, 40, 48, 3, io=F32, tile=(32, 64, 1, 1, 0, 1))
+add(5, 16, 32, 512, 3, io=F32, tile=(64, 64, 1, 1, 1, 1))        # SEG, Co >= 512; B = 5: the last tile holds one utterance
+add(5, 9, 40, 528, 3, io=F32, tile=(64, 64, 1, 1, 0, 1))
+add(3, 16, 64, 128, 5, dil=3, io=F32, tile=(32, 16, 1, 0, 1, 1))  # (K - 1) dil > 8: the one-utterance 32 x 16 tile
+add(3, 7, 40, 80, 5, dil=3, io=F32, tile=(32, 16, 1, 0, 0, 1))
+add(2, 32, 64, 128, 3, io=F32, tile=(128, 32, 1, 0, 1, 1))
+add(3, 17, 40, 144, 3, io=F32, tile=(128, 32, 1, 0, 0, 1))
+add(2, 257, 32, 32, 3, io=F32, tile=(32, 256, 1, 0, 1, 1))
+add(2, 257, 32, 20, 3, io=F32, tile=(32, 256, 1, 0, 0, 1))
+add(2, 257, 32, 64, 3, io=F32, tile=(64, 256, 1, 0, 1, 1))
+add(2, 257, 40, 48, 3, io=F32, tile=(64, 256, 1, 0, 0, 1))
+add(2, 129, 64, 80, 5, io=F32, tile=(64, 128, 1, 0, 0, 1))
+add(2, 65, 64, 128, 3, io=F32, tile=(64, 64, 1, 0, 1, 1))
+add(2, 65, 40, 144, 3, io=F32, tile=(64, 64, 1, 0, 0, 1))
+add(9, 257, 32, 128, 3, io=F32, tile=(128, 128, 1, 0, 1, 1))     # the fp32 default
+add(9, 257, 40, 144, 3, io=F32, tile=(128, 128, 1, 0, 0, 1))
+
+# ---------------------------------------------------------------- strided / grouped (launch_disc)
+for S in (1, 2, 3, 4):
+    G = 4 if S == 1 else 1   # stride 1 reaches launch_disc through groups
+    K = 5
+    T65, T129 = t_in(65, K, S), t_in(129, K, S)
+    # 32 x 64: cog <= 32 (grouped: 4 groups of 32 / 8 output channels) or Co <= 32
+    add(2, T65, 32 * G, 32 * G if S == 1 else 32, K, stride=S, groups=G, io=DISC, tile=(32, 64, S, 0, 1, 1))
+    add(2, T65, 40 if S > 1 else 64, 48 if S == 1 else 20, K, stride=S, groups=2 if S == 1 else 1, io=DISC,
+        tile=(32, 64, S, 0, 0, 1))
+    # 64 x 64: cog <= 64 or Co <= 64
+    G2 = 2 if S == 1 else 1
+    add(2, T65, 64, 64 * G2, K, stride=S, groups=G2, io=DISC, tile=(64, 64, S, 0, 1, 1))
+    add(2, T65, 40 * G2, 48 * G2, K, stride=S, groups=G2, io=DISC, tile=(64, 64, S, 0, 0, 1))
+    # 64 x 64 through t64 < 256 (cog = 128)
+    add(2, T65, 32 * G2, 128 * G2, K, stride=S, groups=G2, io=DISC, tile=(64, 64, S, 0, 1, 1))
+    # 128 x 64: B ceil(T_out / 64) ceil(Co / 128) = 43 * 3 * 2 = 258 >= 256
+    add(43, T129, 32 * G2, 256, K, stride=S, groups=G2, io=DISC, tile=(128, 64, S, 0, 1, 1))
+    add(43, T129, 40 * G2, 272, K, stride=S, groups=G2, io=DISC, tile=(128, 64, S, 0, 0, 1))
+# stride 8 (the ConvTranspose1d(k 16, s 8) input gradient): 128 x 32 at every width
+add(2, t_in(33, 3, 8), 32, 128, 3, stride=8, io=DISC, tile=(128, 32, 8, 0, 1, 1))
+add(2, t_in(33, 3, 8), 40, 48, 3, stride=8, io=DISC, tile=(128, 32, 8, 0, 0, 1))
+add(3, t_in(33, 3, 8), 64, 256, 3, stride=8, groups=2, io=DISC[1:], tile=(128, 32, 8, 0, 1, 1))
+add(2, t_in(33, 3, 8), 32, 20, 3, stride=8, io=DISC, tile=(128, 32, 8, 0, 0, 1))   # NI = 4: the run of 16 crosses Co
+
+# ---------------------------------------------------------------- epilogues, layouts and window edges on
+# the 64 x 64, 64 x 128 and 256 x 256 tiles (bf16 compute)
+BIG = [((2, 65, 64, 128), (64, 64, 1, 0, 1, 1)), ((9, 257, 64, 192), (64, 128, 1, 0, 1, 1)),
+       ((15, 513, 64, 768), (256, 256, 1, 0, 1, 1))]
+for (B, T, Ci, Co), tile in BIG:
+    ragged = tile[:4] + (0, 1)
+    add(B, T, Ci, Co, 3, io=BB_BF, res1=True, res2=True, scale=0.5, post=ACT_RELU, tile=tile)
+    add(B, T, Ci, Co, 3, io=BB_BF, post=ACT_LRELU, post_slope=0.2, pre=ACT_LRELU, tile=tile)
+    add(B, T, Ci, Co, 3, io=BB_BF, post=ACT_TANH, scale=0.5, res2=True, tile=tile)
+    add(B, T, Ci, Co, 3, io=IO4[2:], bias=False, res1=True, pre=ACT_RELU, tile=tile)
+    add(B, T, Ci, Co, 3, dil=32, io=BB_BF, tile=tile)                      # the halo limit (K - 1) dil = 64
+    add(B, T, Ci, Co, 5, pad=4, io=BB_BF, tile=tile)                       # full padding (an input gradient's)
+    add(B, T - 3, Ci, Co, 3, pad=0, T_out=T, io=BB_BF, tile=tile)          # T_out past the natural length
+    add(B, T, Ci, Co, 3, io=BB_BF, ldy_extra=4, y_rows=2, tile=tile)       # ldy % 8 != 0: the scalar epilogue
+    add(B, T, Ci, Co, 3, io=BB_BF, ldy_extra=8, x_rows=3, ldx_extra=8, tile=tile)  # vector epilogue, ldy > Co
+    add(B, T, 40, Co, 3, io=BB_BF, x_rows=2, ldx_extra=24, ldy_extra=16, tile=ragged)
+# bf16 residuals on the scalar epilogue: Co = 20 (the run of 8 channels crosses the row end)
+add(2, 257, 32, 20, 3, io=BB_BF, res1=True, res2=True, scale=0.5, tile=(32, 256, 1, 0, 0, 1))
+
+# a unique, readable id per case
+_seen = {}
+for _c in CASES:
+    extras = [k for k in ("res1", "res2") if _c[k]] + [f"{k}{_c[k]}" for k in ("post", "pre") if _c[k]] + \
+             [f"{k}{_c[k]}" for k in ("ldx_extra", "x_rows", "ldy_extra") if _c[k]] + \
+             ([f"scale{_c['scale']}"] if _c["scale"] != 1.0 else []) + ([] if _c["bias"] else ["nobias"]) + \
+             ([f"pad{_c['pad']}"] if _c["pad"] != _c["dil"] * (_c["K"] - 1) // 2 else []) + \
+             ([f"To{_c['T_out']}"] if _c["T_out_arg"] is not None else [])
+    _c["name"] = "-".join([_c["name"]] + extras)
+    assert _c["name"] not in _seen, _c["name"]
+    _seen[_c["name"]] = _c
+
+# ---------------------------------------------------------------- instantiations that must stay covered
+# (NI, WCO, BT, S, SEG, nice, sizeof TIN, sizeof TC, sizeof TOUT), written by hand from launch_types / launch_disc /
+# vo_conv1d: every tile reachable with default knobs, NICE and ragged, per dtype triple it ships in.  NI and
+# WCO make each entry one instantiation: without them the Co = 80 tile and launch_disc's stride-1 64 x 64
+# tile would coincide with other entries, and deleting their cases would go unnoticed.
+
+
+def _both(ni, wco, bt, s=1, seg=0, sizes=((2, 2, 2), (2, 2, 4)), nices=(1, 0)):
+    return [(ni, wco, bt, s, seg, n) + sz for n in nices for sz in sizes]
+
+
+_ALL4 = ((2, 2, 2), (2, 2, 4), (4, 2, 2), (4, 2, 4))
+_F = ((4, 4, 4),)
+_D = ((4, 4, 4), (2, 2, 2), (2, 2, 4))
+REQUIRED = (
+    # launch_types, bf16 compute: 128 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128, 64 x 64, 64 x 128,
+    # 128 x 256, 256 x 256
+    _both(2, 4, 16) + _both(2, 4, 32) + _both(2, 1, 256) + _both(4, 1, 256) + _both(4, 1, 128, nices=(0,)) +
+    _both(2, 2, 64, sizes=_ALL4) + _both(2, 2, 128, sizes=_ALL4) + _both(4, 2, 256) + _both(4, 4, 256, sizes=_ALL4) +
+    # launch_types, fp32 compute: the two SEG tiles, 32 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128,
+    # 64 x 64, 128 x 128
+    _both(1, 2, 64, seg=1, sizes=_F) + _both(2, 2, 64, seg=1, sizes=_F) + _both(1, 2, 16, sizes=_F) +
+    _both(2, 4, 32, sizes=_F) + _both(2, 1, 256, sizes=_F) + _both(4, 1, 256, sizes=_F) +
+    _both(4, 1, 128, sizes=_F, nices=(0,)) + _both(2, 2, 64, sizes=_F) + _both(4, 2, 128, sizes=_F) +
+    # launch_disc: 32 x 64, 64 x 64, 128 x 64 per stride; 128 x 32 at stride 8
+    [t for s in (1, 2, 3, 4) for t in _both(2, 1, 64, s, sizes=_D) + _both(4, 1, 64, s, sizes=_D) +
+     _both(4, 2, 64, s, sizes=_D)] +
+    _both(4, 2, 32, 8, sizes=_D))
+assert len(set(REQUIRED)) == len(REQUIRED)
+
+
+def _run(c):
+    from visual_onoma_to_wave_amd import ops
+    m = CC.make(c)
+    ref, bar = CC.reference(c, m)
+    dev = torch.device("cuda:0")
+    x_buf, y_buf = m["x_buf"].to(dev), m["y_buf"].to(dev)
+    d = {k: (m[k].to(dev) if m[k] is not None else None) for k in ("w_packed", "bias", "res1", "res2")}
+    ops.conv1d(CC.x_view(c, x_buf), d["w_packed"], d["bias"], out=CC.y_view(c, y_buf), res1=d["res1"], res2=d["res2"],
+               **CC.conv_kwargs(c))
+    rec = ops.conv1d_last_launch()
+    assert rec == CC.record(c), (c["name"], rec, CC.record(c))
+    torch.cuda.synchronize()
+    int_t = CC._INT[m["x_buf"].dtype]
+    assert torch.equal(x_buf.cpu().view(int_t), m["x_buf"].view(int_t)), "the input buffer changed"
+    m["y_buf"].copy_(y_buf.cpu())
+    return CC.verify(c, m, ref, bar)
+
+
+@pytest.mark.parametrize("c", CASES, ids=[c["name"] for c in CASES])
+def test_conv1d_tile(c):
+    _run(c)
+
+
+def test_f32x3_transposed_rejected():
+    """VO_F32X3 has no polyphase ConvTranspose1d form: the C entry point returns VO_ERR_INVALID before the
+    upsampler dispatch, the Python front end raises, the output stays untouched and no tile is recorded."""
+    import ctypes
+    from visual_onoma_to_wave_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    B, T, Ci, s, cout = 2, 16, 128, 2, 64
+    x = torch.randn(B, T, Ci, device=dev)
+    w = torch.randn(2, s * cout, Ci, device=dev)
+    out = torch.empty(B, T * s, cout, device=dev)
+    out.view(torch.int32).fill_(CC.Y_GUARD[torch.float32])
+    tr = dict(stride=s, pad=1, cout=cout)
+    with pytest.raises(ValueError, match="F32X3"):
+        ops.conv1d(x, w, None, Co=s * cout, K=2, pad=1, out=out, transposed=tr, compute_dtype=ops.F32X3)
+    d = _lib.Conv1dDesc()
+    d.x, d.x_dtype, d.x_bstride, d.ldx = x.data_ptr(), _lib.VO_F32, x.stride(0), Ci
+    d.w = w.data_ptr()
+    d.y, d.y_dtype, d.y_bstride, d.ldy = out.data_ptr(), _lib.VO_F32, out.stride(0), cout
+    d.B, d.T_in, d.T_out, d.Ci, d.Co, d.K, d.dil, d.pad = B, T, T + 1, Ci, s * cout, 2, 1, 1
+    d.out_scale, d.compute_dtype = 1.0, _lib.VO_F32X3
+    d.transposed, d.up_stride, d.up_pad, d.up_cout, d.up_tout = 1, s, 1, cout, T * s
+    rc = _lib.lib().vo_conv1d(ctypes.byref(d), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == -1 and b"F32X3" in _lib.lib().vo_last_error()
+    assert set(ops.conv1d_last_launch().values()) == {0}
+    torch.cuda.synchronize()
+    assert bool((out.view(torch.int32) == CC.Y_GUARD[torch.float32]).all())
+
+
+def test_launch_record_reads_zero_for_the_streaming_upsampler():
+    """The record is per call: a generic conv fills it, the next call -- a bf16 Ci = 128 polyphase
+    ConvTranspose1d, which upsample.hip's streaming kernel takes -- leaves it zeroed."""
+    from visual_onoma_to_wave_amd import ops
+    dev = torch.device("cuda:0")
+    c = CASES[0]
+    m = CC.make(c)
+    ops.conv1d(m["x"].to(dev), m["w_packed"].to(dev), m["bias"].to(dev), out_dtype=CC.DT[c["ydt"]],
+               **CC.conv_kwargs(c))
+    assert ops.conv1d_last_launch() == CC.record(c)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 40, 128, generator=g).bfloat16().to(dev)
+    w = (torch.randn(2, 128, 128, generator=g) / 16).bfloat16().to(dev)
+    y = ops.conv1d(x, w, None, Co=128, K=2, pad=1, transposed=dict(stride=2, pad=1, cout=64))
+    assert y.shape == (2, 80, 64) and bool(torch.isfinite(y.float()).all())
+    assert set(ops.conv1d_last_launch().values()) == {0}

@@ -123,6 +123,10 @@ __device__ __forceinline__ void lds_put(bx3_t* p, const Raw8<bx3_t>& v) {
 
 constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
 
+// vo_conv1d_last_launch: the tile of this thread's last vo_conv1d call (zeroed at its entry, filled
+// by launch_cfg_s; host stores only)
+static thread_local int32_t g_last_launch[VO_CONV1D_LAUNCH_FIELDS] = {};
+
 // epilogue: lane (g = lane>>4, lr = lane&15) holds channels [n0, n0 + 4*NI) of position
 // pos for each of its NJ position tiles
 // bf16 output, plain conv, whole 8-channel runs (vec_ok: ldy / y_bstride multiples of 8):
@@ -233,9 +237,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[NI
     col = n0 - phase * a.up_cout;
     trow_shift = phase - a.up_pad;
   }
+  // Co % (4 * NI) != 0: the run of the lane that crosses the end is clamped into the bias (those channels are
+  // not stored); unclamped, it read up to 4 * NI - 4 floats past a bias of Co floats
+  const int bmax = (a.transposed ? a.up_cout : a.Co) - 1;
   float bias[4 * NI];
 #pragma unroll
-  for (int e = 0; e < 4 * NI; ++e) bias[e] = a.bias ? a.bias[(a.transposed ? col : n0) + e] : 0.f;
+  for (int e = 0; e < 4 * NI; ++e) bias[e] = a.bias ? a.bias[min((a.transposed ? col : n0) + e, bmax)] : 0.f;
 
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -1023,6 +1030,9 @@ static int launch_cfg_s(const vo_conv1d_desc* d, hipStream_t st) {
       splits = 1;
     }
   }
+  const int32_t rec[VO_CONV1D_LAUNCH_FIELDS] = {BCO, BT, S, SEG, nice, splits, (int32_t)sizeof(TIN), (int32_t)sizeof(TC),
+                                                (int32_t)sizeof(TOUT), ROLE, d->compute_dtype, NI, WCO};
+  memcpy(g_last_launch, rec, sizeof(rec));
   const unsigned gx = SEG ? (unsigned)((d->B + BT / 16 - 1) / (BT / 16)) : (unsigned)(a.tiles_per_b * d->B);
   dim3 grid(gx, (unsigned)a.co_tiles, (unsigned)splits);
   hipLaunchKernelGGL(kern, grid, dim3(WCO * WT * 64), lds, st, a);
@@ -1232,7 +1242,14 @@ extern "C" int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d) {
   return (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float);
 }
 
+extern "C" int vo_conv1d_last_launch(int32_t* rec, int n) {
+  const int m = rec ? std::max(0, std::min(n, (int)VO_CONV1D_LAUNCH_FIELDS)) : 0;
+  if (m > 0) memcpy(rec, g_last_launch, m * sizeof(int32_t));
+  return m;
+}
+
 extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
+  memset(g_last_launch, 0, sizeof(g_last_launch));
   VO_CHECK_ARG(d != nullptr, "conv1d: null descriptor");
   VO_CHECK_ARG(d->x && d->w && d->y, "conv1d: null tensor pointer");
   VO_CHECK_ARG((d->pre_act != VO_ACT_LRELU || (d->pre_slope >= 0.f && d->pre_slope <= 1.f)) &&
@@ -1262,6 +1279,8 @@ extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
                              d->post_act == VO_ACT_NONE && d->out_scale == 1.f && d->variant == 0 &&
                              d->ymask_slope >= 0.f && d->ymask_slope <= 1.f),
                "conv1d: ymask needs a bf16 output without bias, residuals, activation or scale, slope in [0, 1]");
+  // split-bf16 compute has no polyphase form: refused before the streaming upsampler can take the call
+  VO_CHECK_ARG(!(d->compute_dtype == VO_F32X3 && d->transposed), "conv1d: VO_F32X3 compute excludes transposed");
   if (d->transposed) {  // narrow upsamplers: the persistent streaming kernel (upsample.hip)
     int handled = 0;
     const int rc = vo_ups_try(d, st, &handled);

@@ -86,8 +86,8 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
         raise ValueError(f"conv1d: packed weight {tuple(w_packed.shape)} != [{K}][{Co}][Ci]")
     if w_packed.dtype != storage_dtype(compute_dtype):
         raise ValueError("conv1d: packed weight dtype must equal the compute dtype")
-    if compute_dtype is F32X3 and (x.dtype != torch.float32 or stride > 1 or groups > 1):
-        raise ValueError("conv1d: F32X3 compute needs fp32 input, stride 1, no groups")
+    if compute_dtype is F32X3 and (x.dtype != torch.float32 or stride > 1 or groups > 1 or transposed is not None):
+        raise ValueError("conv1d: F32X3 compute needs fp32 input, stride 1, no groups, not transposed")
     out_dtype = out_dtype or x.dtype
     if transposed is not None:
         s, p, cout = transposed["stride"], transposed["pad"], transposed["cout"]
@@ -160,6 +160,21 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
                   w_packed.numel() * w_packed.element_size())
         timer.stop(tag, ev, flops, nbytes, kernel=f"conv1d_kernel<..., ROLE={d.variant}>")
     return out
+
+
+LAUNCH_FIELDS = ("BCO", "BT", "S", "SEG", "nice", "splits", "sizeof_in", "sizeof_compute", "sizeof_out", "ROLE",
+                 "compute_dtype", "NI", "WCO")
+
+
+def conv1d_last_launch():
+    """The tile the calling thread's last ``conv1d`` launched, as a dict over LAUNCH_FIELDS
+    (vo_conv1d_last_launch in include/vonoma.h); all zeros when the call was rejected or went to the
+    streaming upsampler."""
+    rec = (ctypes.c_int32 * len(LAUNCH_FIELDS))()
+    n = _lib.lib().vo_conv1d_last_launch(rec, len(LAUNCH_FIELDS))
+    if n != len(LAUNCH_FIELDS):
+        raise RuntimeError(f"vo_conv1d_last_launch returned {n} fields, expected {len(LAUNCH_FIELDS)}")
+    return dict(zip(LAUNCH_FIELDS, (int(v) for v in rec)))
 
 
 def pack_dgrad_weight(w, dtype):
