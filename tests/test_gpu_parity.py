@@ -408,24 +408,13 @@ def test_attention_vs_oracle(B, L, lens, dt, tol, cfg):
     assert rel_l2(out.float().cpu(), ref) < tol
 
 
-@pytest.mark.parametrize("C,T", [(32, 1000), (64, 777), (128, 300), (32, 5), (64, 1), (128, 13), (128, 232),
-                                 (128, 233), (32, 488 * 3 + 7), (64, 131072), (32, 65536), (128, 32768),
-                                 # register-resident frames: 104 (C = 32) / 72 (C = 64) output rows per tile
-                                 (32, 104), (32, 105), (32, 24), (64, 72), (64, 73), (64, 16), (64, 72 * 5 - 1),
-                                 # wave-owned planes (resblock_pb3.hip): 200 (C = 128) / 488 (C = 64) output rows per tile
-                                 (128, 200), (128, 201), (128, 200 * 4 + 3), (64, 488), (64, 489), (64, 488 * 3 + 5)])
-@pytest.mark.parametrize("with_acc", [True, False])
-# cfg 0: the shipped dispatch (C = 32: register-resident frames); 80: any rb3_cfg != 0 keeps the LDS-frame
-# kernel (the A/B variants 80-87 of resblock_rr.hip are in the VO_ABLATIONS library)
-@pytest.mark.parametrize("cfg", [0, 80])
-def test_fused_resblock3_vs_torch_fp32(C, T, with_acc, cfg):
-    """vo_resblock3 (a whole k = 3 ResBlock, dilations 1/3/5, in one launch) against the torch fp32
-    ResBlock at tile edges (frame 232 / 488 valid rows), T = 1, and multi-tile persistent runs;
-    and against three vo_resblock_pair launches (same bf16 intermediates up to summation order)."""
+def _resblock3_case(C, T, with_acc, cfg, dils):
+    """vo_resblock3 under rb3_cfg `cfg` against the torch fp32 ResBlock, and against three vo_resblock_pair
+    launches (same bf16 intermediates up to summation order)."""
     import torch.nn.functional as F
     from visual_onoma_to_wave_amd import ops
     g = torch.Generator().manual_seed(C * 7 + T)
-    B, k, dils = 2, 3, (1, 3, 5)
+    B, k = 2, 3
     x = torch.randn(B, T, C, generator=g).to(torch.bfloat16)
     w1 = [torch.randn(C, C, k, generator=g) / (C * k) ** 0.5 for _ in dils]
     w2 = [torch.randn(C, C, k, generator=g) / (C * k) ** 0.5 for _ in dils]
@@ -462,30 +451,43 @@ def test_fused_resblock3_vs_torch_fp32(C, T, with_acc, cfg):
     assert rel_l2(out.float().cpu(), chain.float().cpu()) < 3e-3
 
 
-# cfg 0: the shipped dispatch (wave-owned planes for C = 64 / 128 k = 7 / 11); 93: the LDS-tile kernels;
-# 111: the round-4 C = 64 dispatch (register-resident frames for k = 7);
-# VO_PARITY_PAIR_CFGS=94,95 adds A/B candidates of the ablation build
+@pytest.mark.parametrize("C,T", [(32, 1000), (64, 777), (128, 300), (32, 5), (64, 1), (128, 13), (128, 232),
+                                 (128, 233), (32, 488 * 3 + 7), (64, 131072), (32, 65536), (128, 32768),
+                                 # register-resident frames: 104 (C = 32) / 72 (C = 64) output rows per tile
+                                 (32, 104), (32, 105), (32, 24), (64, 72), (64, 73), (64, 16), (64, 72 * 5 - 1),
+                                 # wave-owned planes (resblock_pb3.hip): 200 (C = 128) / 488 (C = 64) output rows per tile
+                                 (128, 200), (128, 201), (128, 200 * 4 + 3), (64, 488), (64, 489), (64, 488 * 3 + 5),
+                                 # the C = 32 LDS-frame kernel's own edge (256-row frames: 232 output rows per tile)
+                                 (32, 232), (32, 233)])
+@pytest.mark.parametrize("with_acc", [True, False])
+# cfg 0: the shipped dispatch (C = 32: register-resident frames; C = 64 / 128: wave-owned planes).  80 (any
+# rb3_cfg != 0): the LDS-frame kernels -- at C = 32 in either library; at C = 64 / 128 only in the A/B library
+# (make abl, VO_LIB_PATH), the shipped library has the plane kernel alone there and runs it whatever the knob says
+@pytest.mark.parametrize("cfg", [0, 80])
+def test_fused_resblock3_vs_torch_fp32(C, T, with_acc, cfg):
+    """vo_resblock3 (a whole k = 3 ResBlock, dilations 1/3/5, in one launch) against the torch fp32
+    ResBlock at tile edges (frame 232 / 488 valid rows), T = 1, and multi-tile persistent runs;
+    and against three vo_resblock_pair launches (same bf16 intermediates up to summation order)."""
+    _resblock3_case(C, T, with_acc, cfg, (1, 3, 5))
+
+
+@pytest.mark.parametrize("with_acc", [True, False])
+@pytest.mark.parametrize("T", [1, 232, 233, 232 * 3 + 7])
+def test_fused_resblock3_c32_lds_frames_by_default(T, with_acc):
+    """C = 32 off the (1, 3, 5) fast path: dilations (1, 2, 4) (halo 10 <= 12) run the LDS-frame kernel with no knob
+    set -- the only shipped code for them -- at its tile edges (232 output rows per 256-row frame)."""
+    _resblock3_case(32, T, with_acc, 0, (1, 2, 4))
+
+
+# cfg 0: the shipped dispatch (wave-owned planes for C = 64 / 128 k = 7 / 11); 93 and, at C = 64, 111: the LDS-tile
+# kernels there too -- in the shipped library the generic ones that also serve k = 5 / 9 / 13 / 15, in the A/B
+# library (make abl, VO_LIB_PATH) the version-2 kernel at C = 64;
+# VO_PARITY_PAIR_CFGS=94,100 adds A/B candidates of the ablation build
 _PAIR_CFGS = [0, 93, 111] + [int(c) for c in os.environ.get("VO_PARITY_PAIR_CFGS", "").split(",") if c]
 
 
-@pytest.mark.parametrize("cfg", _PAIR_CFGS)
-@pytest.mark.parametrize("with_acc", [True, False])
-@pytest.mark.parametrize("C,T,k,d", [(32, 1000, 11, 5), (64, 777, 7, 3), (32, 5, 3, 1), (64, 1, 11, 1),
-                                     (32, 246 * 3, 11, 5), (64, 4096, 3, 5), (64, 502, 11, 3),
-                                     # several tiles per persistent workgroup (pipelined window/weights)
-                                     (32, 131072, 11, 5), (32, 65536, 3, 1), (64, 65536, 7, 3),
-                                     (64, 65536, 3, 1), (64, 40000, 11, 5),
-                                     # C = 64 k = 7 / 11 plane kernel: one tile (502 / 506 valid rows), +1, two
-                                     (64, 503, 11, 5), (64, 13, 7, 1), (64, 1013, 7, 5), (64, 506, 7, 3),
-                                     (128, 300, 3, 1), (128, 20000, 3, 5),
-                                     # C = 128 k = 7 / 11: T = 1, one tile, tile edges (246 / 250 valid
-                                     # rows), utterances crossing inside a workgroup's run, every dilation
-                                     (128, 1, 7, 3), (128, 1, 11, 5), (128, 13, 11, 1), (128, 246, 11, 5),
-                                     (128, 247, 11, 3), (128, 250, 7, 1), (128, 501, 7, 5), (128, 5000, 11, 3),
-                                     (128, 32768, 11, 5), (128, 32768, 7, 3), (128, 20011, 11, 1)])
-def test_fused_resblock_pair_vs_torch_fp32(C, T, k, d, with_acc, cfg):
-    """vo_resblock_pair (c1 -> lrelu -> c2 + residual, MRF accumulate) at tile edges vs torch fp32,
-    for the shipped dispatch and the round-3 C = 128 kernel."""
+def _pair_case(C, T, k, d, with_acc, cfg):
+    """vo_resblock_pair under pair_cfg `cfg` against torch fp32."""
     import torch.nn.functional as F
     from visual_onoma_to_wave_amd import _lib, ops
     g = torch.Generator().manual_seed(C * T + k)
@@ -513,6 +515,44 @@ def test_fused_resblock_pair_vs_torch_fp32(C, T, k, d, with_acc, cfg):
         _lib.lib().vo_tune(b"pair_cfg", 0)
     assert torch.isfinite(out.float()).all()
     assert rel_l2(out.float().cpu(), ref) < 1e-2
+
+
+@pytest.mark.parametrize("cfg", _PAIR_CFGS)
+@pytest.mark.parametrize("with_acc", [True, False])
+@pytest.mark.parametrize("C,T,k,d", [(32, 1000, 11, 5), (64, 777, 7, 3), (32, 5, 3, 1), (64, 1, 11, 1),
+                                     (32, 246 * 3, 11, 5), (64, 4096, 3, 5), (64, 502, 11, 3),
+                                     # several tiles per persistent workgroup (pipelined window/weights)
+                                     (32, 131072, 11, 5), (32, 65536, 3, 1), (64, 65536, 7, 3),
+                                     (64, 65536, 3, 1), (64, 40000, 11, 5),
+                                     # C = 64 k = 7 / 11 plane kernel: one tile (502 / 506 valid rows), +1, two
+                                     (64, 503, 11, 5), (64, 13, 7, 1), (64, 1013, 7, 5), (64, 506, 7, 3),
+                                     (128, 300, 3, 1), (128, 20000, 3, 5),
+                                     # C = 128 k = 7 / 11: T = 1, one tile, tile edges (246 / 250 valid
+                                     # rows), utterances crossing inside a workgroup's run, every dilation
+                                     (128, 1, 7, 3), (128, 1, 11, 5), (128, 13, 11, 1), (128, 246, 11, 5),
+                                     (128, 247, 11, 3), (128, 250, 7, 1), (128, 501, 7, 5), (128, 5000, 11, 3),
+                                     (128, 32768, 11, 5), (128, 32768, 7, 3), (128, 20011, 11, 1)])
+def test_fused_resblock_pair_vs_torch_fp32(C, T, k, d, with_acc, cfg):
+    """vo_resblock_pair (c1 -> lrelu -> c2 + residual, MRF accumulate) at tile edges vs torch fp32,
+    for the shipped dispatch and the LDS-tile kernels behind pair_cfg 93 / 111."""
+    _pair_case(C, T, k, d, with_acc, cfg)
+
+
+# the generic LDS-tile pair: R1 rows per tile, BT = R1 - (k - 1) of them valid
+_GENERIC_R1 = {128: 256, 64: 512}
+
+
+@pytest.mark.parametrize("with_acc", [True, False])
+@pytest.mark.parametrize("d", [1, 5])
+@pytest.mark.parametrize("edge", ["one", "bt", "bt+1", "2bt+3"])
+@pytest.mark.parametrize("k", [5, 9])
+@pytest.mark.parametrize("C", [64, 128])
+def test_fused_resblock_pair_generic_k(C, k, edge, d, with_acc):
+    """k = 5 / 9 at C = 64 / 128: shapes only the generic LDS-tile kernels serve (no knob set), at T = 1, one full
+    tile, one row more, and two tiles and three rows."""
+    bt = _GENERIC_R1[C] - (k - 1)
+    T = {"one": 1, "bt": bt, "bt+1": bt + 1, "2bt+3": 2 * bt + 3}[edge]
+    _pair_case(C, T, k, d, with_acc, 0)
 
 
 @pytest.mark.parametrize("with_acc,scale", [(True, 1.0 / 3), (False, 1.0), (True, 0.3)])

@@ -151,3 +151,6 @@ def test_vo_tune_rejects_timing_ablations():
         assert L.vo_tune(b"pair_cfg", v) != 0
         assert b"ablation" in L.vo_last_error()
     assert L.vo_tune(b"pair_cfg", 0) == 0
+    assert L.vo_tune(b"wgrad_cfg", 11) != 0  # the weight gradient without its loads
+    assert b"ablation" in L.vo_last_error()
+    assert L.vo_tune(b"wgrad_cfg", 14) == 0 and L.vo_tune(b"wgrad_cfg", 0) == 0  # A/B values stay selectable

@@ -17,10 +17,11 @@
 //    window loads may stay in flight for up to two groups.
 // Dilation <= DMAX (5: the HiFi-GAN V1 MRF); the region rows are sized for it at compile time.
 
+#ifdef VO_ABLATIONS
 #include <algorithm>
 #include <type_traits>
 
-#include "mrf_common.h"
+#include "mrf_common.h"  // visual_onoma_to_wave_amd/csrc (make abl adds it to the include path)
 
 namespace vo {
 
@@ -480,18 +481,7 @@ static int pair2_launch(Pair2Args a, int B, hipStream_t st) {
     vo_set_error("resblock_pair (v2): LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  auto kern = mrf_pair2_kernel<C, WC, WT, NJ, K, GL, TG, VD, PIPE>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NW * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_pair2_kernel<C, WC, WT, NJ, K, GL, TG, VD, PIPE>, a, a.ntiles, NW * 64, lds, true, st);
 }
 
 }  // namespace vo
@@ -500,23 +490,15 @@ using namespace vo;
 
 // Entry from vo_resblock_pair (resblock.hip): returns 1 in *handled when this kernel covers the
 // shape (C = 64 / 128, K = 7 / 11, dilation <= 5), else leaves the launch to the v1 kernels.
-int vo_pair2_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                 const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                 hipStream_t st, int* handled) {
+// C = 128 is reached only under pair_cfg 30 / 31.
+int vo_pair2_try(const MrfPairCall& c, int cfg, int* handled) {
+  const int B = c.B, C = c.C, K = c.K;
+  hipStream_t st = c.st;
   *handled = 0;
-#ifdef VO_ABLATIONS
-  const bool c128 = C == 128;  // the C = 128 form is an A/B variant (pair_cfg 30 / 31)
-#else
-  const bool c128 = false;
-#endif
-  if (!((C == 64 || c128) && (K == 7 || K == 11) && dil >= 1 && dil <= PAIR2_DMAX)) return VO_OK;
+  if (!((C == 64 || C == 128) && (K == 7 || K == 11) && c.dil >= 1 && c.dil <= PAIR2_DMAX)) return VO_OK;
   Pair2Args a;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.dil = dil; a.slope = slope; a.out_scale = out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  mrf_pair_args(a, c);
   *handled = 1;
-#ifdef VO_ABLATIONS
   if (C == 128) {  // 2 x 4 waves of 64 channels, 256-row tiles, whole taps by LDS-DMA
     if (K == 7) return pair2_launch<128, 2, 4, 4, 7, true, 1>(a, B, st);
     return pair2_launch<128, 2, 4, 4, 11, true, 1>(a, B, st);
@@ -526,7 +508,7 @@ int vo_pair2_try(const void* x, const void* w1, const float* b1, const void* w2,
   // faster alone (tools/ab_pair2.py), but s2 -3.6 % / s3 +4 % and the same 13.75 ms in the bench step
   // VALU diet (VD) at C = 64: k = 11 0.408 -> 0.398 ms, k = 7 0.311 -> 0.318 (tools/mrf_bench.py
   // --tune pair_cfg=33,0, round 3): k = 11 ships with it, k = 7 without; cfg 33 swaps both, for A/B
-  if (cfg == 33) {  // (A/B variants of the C = 64 kernel: VO_ABLATIONS builds only)
+  if (cfg == 33) {
     if (K == 7) return pair2_launch<64, 1, 8, 4, 7, false, 2, true>(a, B, st);
     return pair2_launch<64, 1, 8, 4, 11, false, 2, false>(a, B, st);
   }
@@ -547,9 +529,7 @@ int vo_pair2_try(const void* x, const void* w1, const float* b1, const void* w2,
     if (K == 7) return pair2_launch<64, 1, 4, 4, 7, false, 2>(a, B, st);
     return pair2_launch<64, 1, 4, 4, 11, false, 2>(a, B, st);
   }
-#else
-  (void)cfg;
-#endif
   if (K == 7) return pair2_launch<64, 1, 8, 4, 7, false, 2, false>(a, B, st);
   return pair2_launch<64, 1, 8, 4, 11, false, 2, true>(a, B, st);
 }
+#endif  // VO_ABLATIONS

@@ -403,18 +403,7 @@ static int pair3_launch(Pair3Args a, int B, hipStream_t st) {
     vo_set_error("resblock_pair (v3): LDS %zu B exceeds 80 KiB (two workgroups per CU)", lds);
     return VO_ERR_INVALID;
   }
-  auto kern = mrf_pair3_kernel<C, NJ, K, RESW, TG>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_pair3_kernel<C, NJ, K, RESW, TG>, a, a.ntiles, 256, lds, true, st);
 }
 
 }  // namespace vo
@@ -423,16 +412,13 @@ using namespace vo;
 
 // Entry from vo_resblock_pair (resblock.hip): *handled = 1 when this kernel covers the shape
 // (C = 32 / 64, K = 7 / 11, dilation <= 5) for the selected pair_cfg.
-int vo_pair3_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                 const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                 hipStream_t st, int* handled) {
+int vo_pair3_try(const MrfPairCall& c, int cfg, int* handled) {
+  const int B = c.B, C = c.C, K = c.K;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (!((C == 64 || C == 32) && (K == 7 || K == 11) && dil >= 1 && dil <= PAIR3_DMAX)) return VO_OK;
+  if (!((C == 64 || C == 32) && (K == 7 || K == 11) && c.dil >= 1 && c.dil <= PAIR3_DMAX)) return VO_OK;
   Pair3Args a;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.dil = dil; a.slope = slope; a.out_scale = out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  mrf_pair_args(a, c);
   *handled = 1;
   if (C == 64) {  // 256-row tiles, one-tap weight groups streamed by LDS-DMA (cfg 41: two-tap groups)
     if (cfg == 41) {

@@ -275,15 +275,7 @@ static int wave_launch(WaveArgs a, int B, hipStream_t st) {
     vo_set_error("mrf wave kernel: LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>((int64_t)cus, ((int64_t)a.ntiles + NW - 1) / NW);
-  hipLaunchKernelGGL((mrf_wave_kernel<MODE, K, D1, NJ>), dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_wave_kernel<MODE, K, D1, NJ>, a, ((int64_t)a.ntiles + NW - 1) / NW, NW * 64, lds, false, st);
 }
 
 }  // namespace vo
@@ -291,36 +283,36 @@ static int wave_launch(WaveArgs a, int B, hipStream_t st) {
 using namespace vo;
 
 // k = 3 ResBlock at C = 32, dilations (1, 3, 5) (vo_resblock3's shape); *handled = 0 otherwise
-int vo_rb3_wave_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                    const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                    float out_scale, int cfg, hipStream_t st, int* handled) {
+int vo_rb3_wave_try(const MrfBlock3Call& c, int cfg, int* handled) {
+  const int B = c.B;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (C != 32 || dil[0] != 1 || dil[1] != 3 || dil[2] != 5) return VO_OK;
+  if (c.C != 32 || c.dil[0] != 1 || c.dil[1] != 3 || c.dil[2] != 5) return VO_OK;
   WaveArgs a;
-  a.x = (const bf16_t*)x;
+  a.x = (const bf16_t*)c.x;
   for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)w1[s]; a.b[2 * s] = b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)w2[s]; a.b[2 * s + 1] = b2[s];
+    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.b[2 * s] = c.b1[s];
+    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.b[2 * s + 1] = c.b2[s];
   }
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.slope = slope; a.out_scale = out_scale;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
   *handled = 1;
   if (cfg == 31) return wave_launch<0, 3, 1, 10>(a, B, st);   // 160-row frames (136 output rows)
   return wave_launch<0, 3, 1, 8>(a, B, st);                   // 128-row frames (104 output rows)
 }
 
 // k = 7 / 11 pair at C = 32, dilation 1 / 3 / 5
-int vo_pair_wave_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                     const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                     hipStream_t st, int* handled) {
+int vo_pair_wave_try(const MrfPairCall& c, int cfg, int* handled) {
+  const int B = c.B, K = c.K, dil = c.dil;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (C != 32 || !(K == 7 || K == 11) || !(dil == 1 || dil == 3 || dil == 5)) return VO_OK;
+  if (c.C != 32 || !(K == 7 || K == 11) || !(dil == 1 || dil == 3 || dil == 5)) return VO_OK;
   WaveArgs a;
-  a.x = (const bf16_t*)x;
-  a.w[0] = (const bf16_t*)w1; a.b[0] = b1; a.w[1] = (const bf16_t*)w2; a.b[1] = b2;
+  a.x = (const bf16_t*)c.x;
+  a.w[0] = (const bf16_t*)c.w1; a.b[0] = c.b1; a.w[1] = (const bf16_t*)c.w2; a.b[1] = c.b2;
   for (int s = 2; s < 6; ++s) { a.w[s] = nullptr; a.b[s] = nullptr; }
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.slope = slope; a.out_scale = out_scale;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
   *handled = 1;
   (void)cfg;
   // frames: 160 rows (region 160 + 2 x 32 pad at k = 11, d = 5)

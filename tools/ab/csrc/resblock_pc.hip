@@ -476,15 +476,7 @@ static int pc_launch(PcArgs a, int B, hipStream_t st) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>((int64_t)cus, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(kern, a, a.ntiles, 512, lds, false, st);
 }
 
 }  // namespace vo
@@ -493,19 +485,18 @@ using namespace vo;
 
 // C = 128, K in {7, 11}, dil * (K - 1) <= 64, out_scale > 0: the round-4 producer-role pair.
 // *handled = 0 when the shape is not covered (the caller falls back).
-int vo_pair_pc_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale,
-                   hipStream_t st, int* handled) {
+int vo_pair_pc_try(const MrfPairCall& c, int* handled) {
+  const int B = c.B, K = c.K;
+  const void* acc = c.acc;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (C != 128 || (K != 7 && K != 11) || dil < 1 || dil * (K - 1) > 64 || !(out_scale > 0.f) ||
-      (int64_t)T * C * 2 >= (int64_t)1 << 31)
+  if (c.C != 128 || (K != 7 && K != 11) || c.dil < 1 || c.dil * (K - 1) > 64 || !(c.out_scale > 0.f) ||
+      (int64_t)c.T * c.C * 2 >= (int64_t)1 << 31)
     return VO_OK;
   *handled = 1;
   PcArgs a;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.dil = dil; a.slope = slope; a.out_scale = out_scale; a.inv_scale = 1.f / out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  mrf_pair_args(a, c);
+  a.inv_scale = 1.f / c.out_scale;
   const int mode = vo_tune_get("pc_cfg");
 #ifdef VO_ABLATIONS
   if (mode == 8) return K == 7 ? pc_launch<7, true, 0, 1>(a, B, st) : pc_launch<11, true, 0, 1>(a, B, st);

@@ -366,15 +366,7 @@ static int rs_launch(RsArgs a, int B, hipStream_t st) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
     attr = true;
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>((int64_t)cus, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NWV * 64), Gm::LDS, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(kern, a, a.ntiles, NWV * 64, Gm::LDS, false, st);
 }
 
 }  // namespace vo
@@ -382,20 +374,19 @@ static int rs_launch(RsArgs a, int B, hipStream_t st) {
 using namespace vo;
 
 // C = 128, K in {7, 11}, dil * (K - 1) <= 64, out_scale > 0.  *handled = 0 when not covered.
-int vo_pair_rs_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled) {
+int vo_pair_rs_try(const MrfPairCall& c, int cfg, int* handled) {
+  const int B = c.B, K = c.K;
+  const void* acc = c.acc;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (C != 128 || (K != 7 && K != 11) || dil < 1 || dil * (K - 1) > 64 || !(out_scale > 0.f) ||
-      (int64_t)B * T * C * 2 >= ((int64_t)1 << 31))  // 32-bit buffer offsets
+  if (c.C != 128 || (K != 7 && K != 11) || c.dil < 1 || c.dil * (K - 1) > 64 || !(c.out_scale > 0.f) ||
+      (int64_t)B * c.T * c.C * 2 >= ((int64_t)1 << 31))  // 32-bit buffer offsets
     return VO_OK;
   *handled = 1;
   RsArgs a;
+  mrf_pair_args(a, c);
   a.B = B;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.dil = dil; a.slope = slope; a.out_scale = out_scale; a.inv_scale = 1.f / out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  a.inv_scale = 1.f / c.out_scale;
 #ifdef VO_ABLATIONS
   if (cfg == 9) return K == 7 ? rs_launch<7, true, 12, 1, 5, 4, true>(a, B, st) : rs_launch<11, true, 12, 1, 5, 4, true>(a, B, st);
   if (cfg == 10) return K == 7 ? rs_launch<7, true, 6, 1, 5, 8, true>(a, B, st) : rs_launch<11, true, 6, 1, 5, 8, true>(a, B, st);

@@ -1,6 +1,10 @@
-// Helpers shared by the fused MRF kernels (resblock.hip, resblock3.hip): 16-byte staging
-// vectors, the conflict-free LDS row swizzle and packed-bf16 leaky ReLU.
+// Shared by the fused MRF kernels (resblock*.hip): device helpers (16-byte staging vectors, the
+// conflict-free LDS row swizzle, packed-bf16 leaky ReLU) and the one copy of their host side (the
+// persistent launch, the call structs and the prototypes of the vo_*_try dispatch).
 #pragma once
+
+#include <algorithm>
+#include <cmath>
 
 #include "vo_common.h"
 
@@ -57,4 +61,73 @@ __device__ __forceinline__ void unpack8(u32x4 u, float (&f)[8]) {
   }
 }
 
+// ---------------------------------------------------------------- host side: launch and dispatch
+// Every MRF kernel is persistent: a workgroup walks its share of `work` items (tiles, or groups of NWV tiles in
+// the kernels whose waves take a tile each).  The grid is min(CUs * per_cu, work) with per_cu = 1, or, with
+// `by_occupancy`, the resident workgroups per CU the runtime reports for (threads, lds).
+template <class Args>
+static int mrf_launch(void (*kern)(Args), const Args& a, int64_t work, int threads, size_t lds, bool by_occupancy,
+                      hipStream_t st) {
+  int per_cu = 1;
+  if (by_occupancy &&
+      (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess || per_cu < 1))
+    per_cu = 1;
+  const int grid = (int)std::min<int64_t>((int64_t)cu_count() * per_cu, work);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, st, a);
+  VO_RETURN_LAUNCH();
+}
+
+// How the plane kernels add the MRF accumulator: 0 = none; 2 = acc_in / out_scale through an identity MFMA, when
+// 1 / out_scale is a bf16 value (the MRF's 1/3 -> 3); 1 = added in the epilogue
+inline int mrf_acc_mode(const void* acc, float out_scale) {
+  if (!acc) return 0;
+  const float inv = 1.0f / out_scale;
+  const float invb = __bfloat162float(__float2bfloat16(inv));
+  return (invb == inv && std::isfinite(inv) && inv * out_scale == 1.0f) ? 2 : 1;
+}
+
+// One vo_resblock_pair / vo_resblock3 call, as the entry points hand it to the kernels' vo_*_try functions
+struct MrfPairCall {
+  const void* x; const void* w1; const float* b1; const void* w2; const float* b2;
+  void* y; const void* acc;
+  int B, T, C, K, dil;
+  float slope, out_scale;
+  hipStream_t st;
+};
+struct MrfBlock3Call {
+  const void* x; const void* const* w1; const float* const* b1; const void* const* w2; const float* const* b2;
+  const int* dil;
+  void* y; const void* acc;
+  int B, T, C;
+  float slope, out_scale;
+  hipStream_t st;
+};
+
+// the fields every pair kernel's argument struct has, from the call
+template <class A>
+static void mrf_pair_args(A& a, const MrfPairCall& c) {
+  a.x = (const bf16_t*)c.x; a.w1 = (const bf16_t*)c.w1; a.b1 = c.b1; a.w2 = (const bf16_t*)c.w2; a.b2 = c.b2;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.dil = c.dil; a.slope = c.slope; a.out_scale = c.out_scale;
+  a.tiles_per_b = a.ntiles = 0;
+}
+
 }  // namespace vo
+
+// The argument checks of vo_resblock_pair and (frag) vo_resblock_pair_frag (resblock.hip); the error names the entry
+int vo_pair_check(const vo::MrfPairCall& c, bool frag);
+
+// The kernels behind vo_resblock_pair / vo_resblock3: each launches and sets *handled = 1 when it covers the shape
+// (and the knob value `cfg`), else leaves *handled = 0 for the next one.
+int vo_pair_rw_try(const vo::MrfPairCall& c, int cfg, int frag, int* handled);  // resblock_rw.hip
+int vo_rb3_pb_try(const vo::MrfBlock3Call& c, int* handled);                     // resblock_pb3.hip
+int vo_rb3_rr_try(const vo::MrfBlock3Call& c, int cfg, int* handled);            // resblock_rr.hip
+#ifdef VO_ABLATIONS  // the A/B library's kernels (resblock_rr.hip and tools/ab/csrc)
+int vo_pair_rr_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rr.hip
+int vo_pair2_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resblock2.hip
+int vo_pair3_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resblock4.hip
+int vo_pair_pc_try(const vo::MrfPairCall& c, int* handled);             // resblock_pc.hip
+int vo_pair_rs_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rs.hip
+int vo_pair_wave_try(const vo::MrfPairCall& c, int cfg, int* handled);  // resblock5.hip
+int vo_rb3_wave_try(const vo::MrfBlock3Call& c, int cfg, int* handled);  // resblock5.hip
+#endif

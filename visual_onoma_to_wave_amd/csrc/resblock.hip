@@ -587,104 +587,82 @@ static int pair_launch(PairArgs a, int B, hipStream_t st) {
     vo_set_error("resblock_pair: LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  auto kern = mrf_pair_kernel<C, WC, WT, NJ, RES, TG, ABL, PRIO, SB, GL, IP, HP, LATE, VD>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NW * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_pair_kernel<C, WC, WT, NJ, RES, TG, ABL, PRIO, SB, GL, IP, HP, LATE, VD>, a, a.ntiles, NW * 64,
+                    lds, true, st);
 }
 
 }  // namespace vo
 
 using namespace vo;
 
-int vo_pair2_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                 const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                 hipStream_t st, int* handled);  // resblock2.hip
-int vo_pair3_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                 const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                 hipStream_t st, int* handled);  // resblock4.hip
-int vo_pair_pc_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale,
-                   hipStream_t st, int* handled);  // resblock_pc.hip
-int vo_pair_rs_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled);  // resblock_rs.hip
-int vo_pair_rr_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled);  // resblock_rr.hip
-int vo_pair_rw_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled, int frag);  // resblock_rw.hip
-int vo_pair_wave_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                     const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                     hipStream_t st, int* handled);  // resblock5.hip
+int vo_pair_check(const MrfPairCall& c, bool frag) {
+  const char* entry = frag ? "resblock_pair_frag" : "resblock_pair";
+  VO_CHECK_ARG(c.x && c.w1 && c.b1 && c.w2 && c.b2 && c.y, "%s: null pointer", entry);
+  if (frag) {
+    VO_CHECK_ARG((c.C == 64 || c.C == 128) && (c.K == 7 || c.K == 11) && c.dil >= 1 && c.dil * (c.K - 1) <= 64,
+                 "%s: C=%d K=%d dil=%d unsupported (C = 64 / 128, K = 7 / 11, (K-1)*dil <= 64)", entry, c.C, c.K, c.dil);
+  } else {
+    VO_CHECK_ARG(c.C == 32 || c.C == 64 || c.C == 128, "%s: C=%d unsupported (32, 64 or 128)", entry, c.C);
+    VO_CHECK_ARG(c.K % 2 == 1 && c.K >= 1 && c.K <= 15 && c.dil >= 1 && c.dil * (c.K - 1) <= 64,
+                 "%s: K=%d dil=%d unsupported (odd K <= 15, (K-1)*dil <= 64)", entry, c.K, c.dil);
+  }
+  VO_CHECK_ARG(c.slope >= 0.f && c.slope <= 1.f, "%s: slope %g outside [0, 1]", entry, c.slope);
+  VO_CHECK_ARG(c.B > 0 && c.T > 0, "%s: empty", entry);
+  VO_CHECK_ARG(c.y != c.x, "%s: y must not alias x (neighbouring tiles re-read x)", entry);
+  VO_CHECK_ARG(c.acc == nullptr || c.acc == c.y || c.acc != c.x, "%s: acc must not alias x", entry);
+  return VO_OK;
+}
 
 extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                                 void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
                                 float out_scale, void* stream) {
-  VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && y, "resblock_pair: null pointer");
-  VO_CHECK_ARG(C == 32 || C == 64 || C == 128, "resblock_pair: C=%d unsupported (32, 64 or 128)", C);
-  VO_CHECK_ARG(K % 2 == 1 && K >= 1 && K <= 15 && dil >= 1 && dil * (K - 1) <= 64,
-               "resblock_pair: K=%d dil=%d unsupported (odd K <= 15, (K-1)*dil <= 64)", K, dil);
-  VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "resblock_pair: slope %g outside [0, 1]", slope);
-  VO_CHECK_ARG(B > 0 && T > 0, "resblock_pair: empty");
-  VO_CHECK_ARG(y != x, "resblock_pair: y must not alias x (neighbouring tiles re-read x)");
-  VO_CHECK_ARG(acc == nullptr || acc == y || acc != x, "resblock_pair: acc must not alias x");
-  PairArgs a;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.K = K; a.dil = dil; a.slope = slope; a.out_scale = out_scale;
-  a.tiles_per_b = a.ntiles = 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // measured on MI355X, B=32 MRF shapes (tools/ab_pair.py, tools/ab_sb.py): C=32 K<=7 ->
-  // 256-row tiles (3 workgroups/CU), K=11 -> 512-row tiles.  pair_cfg selects the
-  // alternatives for A/B runs.
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, st};
+  if (const int rc = vo_pair_check(c, false)) return rc;
+  PairArgs a;
+  mrf_pair_args(a, c);
+  a.K = K;
+  // Shipped dispatch (measured on MI355X at the B = 32 MRF shapes, tools/ab_pair.py, tools/ab_sb.py, tools/mrf_bench.py):
+  //   C = 64 / 128, K = 7 / 11: wave-owned output planes (resblock_rw.hip);
+  //   everything else: the LDS-tile kernels of this file, tiled per C and K at the end of this function.
+  // pair_cfg 93 (and 99; 111 at C = 64) sends K = 7 / 11 to those LDS-tile kernels as well, in either library.  Every
+  // other pair_cfg value selects a measured-and-dropped variant and means something in the A/B library only
+  // (make abl, VO_ABLATIONS); the shipped library does not contain those kernels and runs its defaults.
   const int cfg = vo_tune_get("pair_cfg");
-  {  // round 5: C = 64 / 128 k = 7 / 11 with wave-owned output planes (resblock_rw.hip); pair_cfg 93 = LDS tiles
-    int handled = 0;
-    const int rc = vo_pair_rw_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled, 0);
+  int handled = 0;
+#ifdef VO_ABLATIONS
+  // round 4: register-resident frames (resblock_rr.hip): C = 32 K = 7 / 11 pair_cfg 90-93, 99; C = 64 94-98 and
+  // 100 = the 144-row k = 7 frames that shipped before the plane kernel
+  if (cfg >= 90 && cfg <= 100) {
+    const int rc = vo_pair_rr_try(c, cfg, &handled);
     if (handled) return rc;
   }
-  {  // round 4: register-resident frames (resblock_rr.hip) for C = 64 k = 7; pair_cfg 90-99 (A/B)
-    int handled = 0;
-    const int rc = vo_pair_rr_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled);
+#endif
+  {
+    const int rc = vo_pair_rw_try(c, cfg, 0, &handled);
     if (handled) return rc;
   }
 #ifdef VO_ABLATIONS  // measured-and-dropped variants (A/B builds only: make abl)
   // round-4 C = 128 candidates (k = 7 / 11): pair_cfg 71 = producer roles (resblock_pc.hip),
   // 72 = register-streamed weights, one wave per SIMD (resblock_rs.hip; rs_cfg 2: two per SIMD)
   if (C == 128 && cfg == 71) {
-    int handled = 0;
-    const int rc = vo_pair_pc_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, st, &handled);
+    const int rc = vo_pair_pc_try(c, &handled);
     if (handled) return rc;
   }
   if (C == 128 && cfg == 72) {
-    int handled = 0;
-    const int rc = vo_pair_rs_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale,
-                                  vo_tune_get("rs_cfg"), st, &handled);
+    const int rc = vo_pair_rs_try(c, vo_tune_get("rs_cfg"), &handled);
     if (handled) return rc;
   }
   if (cfg == 50) {  // round 3: C = 32 with wave-private frames (resblock5.hip)
-    int handled = 0;
-    const int rc = vo_pair_wave_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled);
+    const int rc = vo_pair_wave_try(c, cfg, &handled);
     if (handled) return rc;
   }
   if (cfg == 40 || cfg == 41) {  // round 3: two 4-wave workgroups per CU, LDS-DMA windows (resblock4.hip)
-    int handled = 0;
-    const int rc = vo_pair3_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled);
+    const int rc = vo_pair3_try(c, cfg, &handled);
     if (handled) return rc;
   }
   if (cfg == 30 || cfg == 31) {  // the version-2 kernel at C = 128 (resblock2.hip): -1 % at k = 7, +5 % at k = 11
-    int handled = 0;
-    const int rc = vo_pair2_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled);
+    const int rc = vo_pair2_try(c, cfg, &handled);
     if (handled) return rc;
   }
   // VALU diet (VD): C = 128 -2..4 % (0.682 -> 0.668 ms at k = 11, 0.505 -> 0.485 at k = 7); C = 32
@@ -739,14 +717,14 @@ extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, 
     if (cfg == 9) return pair_launch<64, 1, 8, 3, false, 2>(a, B, st);  // the round-2 default
     if (cfg == 2 && K <= 3) return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);
   }
-#endif
-  // C = 64, k >= 7: the version-2 kernel (resblock2.hip: compile-time K, next window fetched during
-  // P2): 0.453 -> 0.408 ms at k = 11, 0.359 -> 0.326 at k = 7, bit-identical (tools/ab_pair2.py).
+  // C = 64, K = 7 / 11 past the plane kernel (pair_cfg 93 / 99 / 111): the version-2 kernel (tools/ab/csrc/resblock2.hip:
+  // compile-time K, next window fetched during P2): 0.453 -> 0.408 ms at k = 11, 0.359 -> 0.326 at k = 7 against the
+  // generic kernel below, bit-identical (tools/ab_pair2.py).  It shipped until the plane kernel took its shapes.
   if (C == 64) {
-    int handled = 0;
-    const int rc = vo_pair2_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, cfg, st, &handled);
+    const int rc = vo_pair2_try(c, cfg, &handled);
     if (handled) return rc;
   }
+#endif
   if (C == 32) {
     // 512-row in-place tiles, window / residual fetched after P2: k = 11 -13 %, k = 7 -3 %
     // (k = 3 is HBM-bound at ~5 TB/s either way; tools/ab_sb.py pair32 9 5); without the VALU diet
@@ -765,7 +743,7 @@ extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, 
     if (K <= 3) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, true>(a, B, st);
     return pair_launch<128, 2, 4, 4, false, 1, 0, 0, true, true, true, false, true>(a, B, st);
   }
-  // C = 64: k = 3 -> both convs resident in LDS; other k (the version-2 kernel covers 7 / 11) ->
+  // C = 64: k = 3 -> both convs resident in LDS; other k (k = 7 / 11 only under pair_cfg 93 / 99 / 111) ->
   // 512-row in-place tiles, window / residual fetched after P2 (-5 % against the 384-row kernel)
   if (K <= 3) return pair_launch<64, 1, 8, 2, true, 1>(a, B, st);
   return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);

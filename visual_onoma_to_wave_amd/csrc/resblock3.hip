@@ -549,33 +549,12 @@ static int rb3_launch(Rb3Args a, int B, hipStream_t st) {
     vo_set_error("resblock3: LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  auto kern = mrf_rb3_kernel<C, WC, WT, NJ, RESW, SPLIT, NBUF, VD, TPG, PIPE>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NW * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_rb3_kernel<C, WC, WT, NJ, RESW, SPLIT, NBUF, VD, TPG, PIPE>, a, a.ntiles, NW * 64, lds, true, st);
 }
 
 }  // namespace vo
 
 using namespace vo;
-
-int vo_rb3_wave_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                    const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                    float out_scale, int cfg, hipStream_t st, int* handled);  // resblock5.hip
-int vo_rb3_rr_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                  float out_scale, int cfg, hipStream_t st, int* handled);  // resblock_rr.hip
-int vo_rb3_pb_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                  float out_scale, hipStream_t st, int* handled, int frag);  // resblock_pb3.hip
 
 extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                             const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
@@ -601,25 +580,35 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
   a.T = T; a.slope = slope; a.out_scale = out_scale;
   a.tiles_per_b = a.ntiles = 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // measured on MI355X at B = 32 (tools/ab_rb3.py, with the MRF accumulator), against three
-  // vo_resblock_pair launches: C = 128 0.84 vs 1.02 ms, C = 64 0.61 vs 0.67, C = 32 0.39 vs 0.52.
-  // rb3_cfg (A/B): 1 = 128-row frames (C = 32: 512-row), 4 = a 3-deep LDS-DMA ring of half / whole
-  // taps (C = 128 / 64; within 2 % of double buffering: the DMA latency is not what binds).
+  const MrfBlock3Call c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st};
+  int handled = 0;
+  // Shipped dispatch (measured on MI355X at B = 32 with the MRF accumulator, tools/ab_rb3.py, tools/mrf_bench.py):
+  //   C = 64 / 128: wave-owned output planes (resblock_pb3.hip), for every shape accepted above;
+  //   C = 32, dilations (1, 3, 5): register-resident frames (resblock_rr.hip);
+  //   C = 32 otherwise, and under any rb3_cfg != 0: the LDS-frame kernel of this file.
+  // Every other use of rb3_cfg selects a measured-and-dropped variant and means something in the A/B library only
+  // (make abl, VO_ABLATIONS): there any rb3_cfg != 0 also sends C = 64 / 128 to the LDS-frame kernels (90 by
+  // convention), 77-89 pick the frame shapes of resblock_rr.hip, 1 / 4-7 / 20 / 40-45 the tilings below (1 = 128-row
+  // frames, C = 32: 512-row; 4 = a 3-deep LDS-DMA ring of half / whole taps, within 2 % of double buffering).
+  // The LDS-frame kernels against three vo_resblock_pair launches: C = 128 0.84 vs 1.02 ms, C = 64 0.61 vs 0.67,
+  // C = 32 0.39 vs 0.52.
   const int cfg = vo_tune_get("rb3_cfg");
-  if (cfg == 0) {  // round 6: wave-owned output planes (resblock_pb3.hip) for C = 64 / 128; rb3_cfg 90: the LDS-tile block
-    int handled = 0;
-    const int rc = vo_rb3_pb_try(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st, &handled, 0);
+#ifdef VO_ABLATIONS
+  const bool plane = cfg == 0;
+#else
+  const bool plane = true;  // the shipped library has no other C = 64 / 128 kernel
+#endif
+  if (plane) {
+    const int rc = vo_rb3_pb_try(c, &handled);
     if (handled) return rc;
   }
-  {  // round 4: register-resident frames (resblock_rr.hip) for C = 32, dilations (1, 3, 5); rb3_cfg 77-89 (A/B)
-    int handled = 0;
-    const int rc = vo_rb3_rr_try(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, cfg, st, &handled);
+  {
+    const int rc = vo_rb3_rr_try(c, cfg, &handled);
     if (handled) return rc;
   }
 #ifdef VO_ABLATIONS  // measured-and-dropped variants (A/B builds only: make abl)
   if (C == 32 && (cfg == 30 || cfg == 31)) {  // round 3: wave-private frames (resblock5.hip)
-    int handled = 0;
-    const int rc = vo_rb3_wave_try(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, cfg, st, &handled);
+    const int rc = vo_rb3_wave_try(c, cfg, &handled);
     if (handled) return rc;
   }
   if (cfg == 20) {  // the round-2 kernels (epilogues without the VALU diet), for A/B
@@ -648,16 +637,18 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
     if (cfg == 4) return rb3_launch<128, 2, 4, 4, false, 2, 4>(a, B, st);
     if (cfg == 42) return rb3_launch<128, 2, 4, 4, false>(a, B, st);  // without the PIPE steps
   }
-#else
-  (void)cfg;
-#endif
-  // C = 32: 256-row frames, all weights resident: 2 workgroups (4 waves / SIMD) per CU
-  if (C == 32) return rb3_launch<32, 1, 8, 2, true>(a, B, st);
   // C = 64: a whole conv (3 taps, 24 KB) per streamed group: 6 barriers per tile instead of 24, 0.476
   // -> 0.448 ms (tools/mrf_bench.py --stages 2 --tune rb3_cfg=0,40, round 3, bit-identical); with the
   // software-pipelined steps (PIPE) 0.443 -> 0.437 ms
   if (C == 64) return rb3_launch<64, 1, 8, 4, false, 1, 2, true, 3, true>(a, B, st);
   // C = 128: software-pipelined steps (PIPE: the next (tap, plane) step's fragments read during the
   // current step's MFMAs): 0.720 -> 0.686 ms, bit-identical (tools/mrf_bench.py --tune rb3_cfg=0,42)
-  return rb3_launch<128, 2, 4, 4, false, 1, 2, true, 1, true>(a, B, st);
+  if (C == 128) return rb3_launch<128, 2, 4, 4, false, 1, 2, true, 1, true>(a, B, st);
+#endif
+  if (C != 32) {  // (the plane kernel's guard is this entry's own: not reached)
+    vo_set_error("resblock3: no kernel for C=%d", C);
+    return VO_ERR_INVALID;
+  }
+  // C = 32: 256-row frames, all weights resident: 2 workgroups (4 waves / SIMD) per CU
+  return rb3_launch<32, 1, 8, 2, true>(a, B, st);
 }

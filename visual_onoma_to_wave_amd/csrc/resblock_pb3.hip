@@ -22,8 +22,7 @@
 //   * LDS rows [plane][row][32 ch], 16-byte chunk q of row r at q ^ ((r >> 1) & 3) (rw_off): the B-fragment
 //     reads at any row shift, the T1 / window stores of the epilogues and the window staging (odd plane
 //     stride) are bank-conflict free.
-// Weights: [K][C_out][C_in] bf16 packs (vo_pack_weight) or the fragment order of vo_pack_frag (FR);
-// biases fp32.
+// Weights: [K][C_out][C_in] bf16 packs (vo_pack_weight); biases fp32.
 
 #include <algorithm>
 #include <cmath>
@@ -67,7 +66,7 @@ constexpr size_t pb_lds(int C) { return (size_t)2 * pb_np(C) * pb_rp(C) * 32 * s
 
 __device__ __forceinline__ int pb_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
-template <int C, int ACC, bool FR, bool ST = false>
+template <int C, int ACC, bool ST = false>
 __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   constexpr int NP = pb_np(C), F = pb_f(C), NJ = pb_nj(C), RP = pb_rp(C), PL = RP * 32;
   constexpr int BT = F - 2 * PB_HALO;
@@ -121,7 +120,6 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   // Three tap slots (tap u in slot u % 3; 18 taps per tile): a conv's taps 1 and 2 run interleaved (phase 1),
   // so both are resident while the next conv's tap 0 is fetched into the slot tap 0 freed
   const int aoff = ((32 * pw + 8 * (lr >> 2) + (lr & 3)) * C + 8 * lg) * (int)sizeof(bf16_t);
-  const int afr = pw * NAP * 1024 + lane * 16;
   __amdgpu_buffer_rsrc_t rw[6];
 #pragma unroll
   for (int v = 0; v < 6; ++v) rw[v] = __builtin_amdgcn_make_buffer_rsrc((void*)a.w[v], (short)0, 3 * C * C * 2, 0x00020000);
@@ -129,7 +127,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   auto loadA_piece = [&](int u, int i) __attribute__((always_inline)) {
     const int uu = u % NU, v = uu / 3, k = uu % 3;
     const int s = i >> 1, t = i & 1;
-    const int lo = FR ? afr + i * 1024 : aoff + t * 4 * C * 2 + s * 64;
+    const int lo = aoff + t * 4 * C * 2 + s * 64;
     A[uu % 3][s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw[v], lo, k * (C * C * 2), 0));
   };
   auto utt = [&](const bf16_t* p, int b) __attribute__((always_inline)) {  // one utterance of a (B, T, C) tensor: rows outside read 0
@@ -399,73 +397,52 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   }
 }
 
-template <int C, int ACC, bool FR>
+template <int C, int ACC>
 static int pb3_launch(Pb3Args a, int B, hipStream_t st) {
   constexpr int BT = pb_f(C) - 2 * PB_HALO;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
-  auto kern = mrf_pb3_kernel<C, ACC, FR>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>((int64_t)cus, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), pb_lds(C), st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_pb3_kernel<C, ACC>, a, a.ntiles, 256, pb_lds(C), false, st);
 }
 
 }  // namespace vo
 
 using namespace vo;
 
-// Entry from vo_resblock3 / vo_resblock3_frag: *handled = 1 when this kernel covers the shape (C = 64 / 128,
-// every dilation <= 8 and their halo sum <= 12).
-int vo_rb3_pb_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                  float out_scale, hipStream_t st, int* handled, int frag) {
+// Entry from vo_resblock3: *handled = 1 when this kernel covers the shape (C = 64 / 128, every dilation <= 8 and
+// their halo sum <= 12: at those C, everything vo_resblock3 accepts).
+int vo_rb3_pb_try(const MrfBlock3Call& c, int* handled) {
   *handled = 0;
-  if (!(C == 64 || C == 128)) return VO_OK;
+  if (!(c.C == 64 || c.C == 128)) return VO_OK;
   int halo = 0;
   for (int s = 0; s < 3; ++s) {
-    if (dil[s] < 1 || dil[s] > PB_HP) return VO_OK;
-    halo += dil[s] + 1;
+    if (c.dil[s] < 1 || c.dil[s] > PB_HP) return VO_OK;
+    halo += c.dil[s] + 1;
   }
   if (halo > PB_HALO) return VO_OK;
   Pb3Args a;
-  a.x = (const bf16_t*)x;
+  a.x = (const bf16_t*)c.x;
   for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)w1[s]; a.b[2 * s] = b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)w2[s]; a.b[2 * s + 1] = b2[s];
-    a.dil[s] = dil[s];
+    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.b[2 * s] = c.b1[s];
+    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.b[2 * s + 1] = c.b2[s];
+    a.dil[s] = c.dil[s];
   }
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.slope = slope; a.out_scale = out_scale;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
   a.tiles_per_b = a.ntiles = 0;
   a.stamps = nullptr;
   *handled = 1;
-  int accm = 0;
-  if (acc) {  // acc_in / out_scale through the identity MFMA when 1 / out_scale is a bf16 value (3)
-    const float inv = 1.0f / out_scale;
-    const float invb = __bfloat162float(__float2bfloat16(inv));
-    accm = (invb == inv && std::isfinite(inv) && inv * out_scale == 1.0f) ? 2 : 1;
-  }
-#define VO_PB3_DISPATCH(CC, FF) \
-  return accm == 2 ? pb3_launch<CC, 2, FF>(a, B, st) : accm == 1 ? pb3_launch<CC, 1, FF>(a, B, st) \
-                                                   : pb3_launch<CC, 0, FF>(a, B, st)
-  if (C == 64) {
-    if (frag) VO_PB3_DISPATCH(64, true);
-    VO_PB3_DISPATCH(64, false);
-  }
-  if (frag) VO_PB3_DISPATCH(128, true);
-  VO_PB3_DISPATCH(128, false);
+  const int accm = mrf_acc_mode(c.acc, c.out_scale);
+#define VO_PB3_DISPATCH(CC) \
+  return accm == 2 ? pb3_launch<CC, 2>(a, c.B, c.st) : accm == 1 ? pb3_launch<CC, 1>(a, c.B, c.st) : pb3_launch<CC, 0>(a, c.B, c.st)
+  if (c.C == 64) VO_PB3_DISPATCH(64);
+  VO_PB3_DISPATCH(128);
 #undef VO_PB3_DISPATCH
 }
 
 #ifdef VO_PB3_STAMPS
 // Diagnostic entry (tools/probes/pb3_stamps.py builds its own library with -DVO_PB3_STAMPS): one stamped launch
-// of the k = 3 block (dilations 1 / 3 / 5, MRF accumulator on, out_scale 1/3, [K][Co][Ci] weights) at C = 64 / 128;
+// of the k = 3 block (dilations 1 / 3 / 5, MRF accumulator on, out_scale 1/3) at C = 64 / 128;
 // host_out receives PB_NSTW x 4 waves x PB_NSTT tiles x PB_NPT stamps.
 extern "C" int vo_pb3_stamps(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                              const float* const* b2, void* y, int B, int T, int C, unsigned long long* host_out) {
@@ -487,9 +464,9 @@ extern "C" int vo_pb3_stamps(const void* x, const void* const* w1, const float* 
   a.ntiles = a.tiles_per_b * B;
   const int grid = std::min(256, a.ntiles);
   if (C == 64)
-    hipLaunchKernelGGL((mrf_pb3_kernel<64, 2, false, true>), dim3(grid), dim3(256), pb_lds(64), 0, a);
+    hipLaunchKernelGGL((mrf_pb3_kernel<64, 2, true>), dim3(grid), dim3(256), pb_lds(64), 0, a);
   else
-    hipLaunchKernelGGL((mrf_pb3_kernel<128, 2, false, true>), dim3(grid), dim3(256), pb_lds(128), 0, a);
+    hipLaunchKernelGGL((mrf_pb3_kernel<128, 2, true>), dim3(grid), dim3(256), pb_lds(128), 0, a);
   (void)hipDeviceSynchronize();
   (void)hipMemcpy(host_out, d, n * 8, hipMemcpyDeviceToHost);
   (void)hipFree(d);

@@ -330,6 +330,7 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
   }
 }
 
+#ifdef VO_ABLATIONS  // measured and dropped (rb3_cfg 82 / 83): in the A/B library only
 // ------------------------------------------------------------------------------------------------
 // The same block on v_mfma_f32_32x32x16_bf16 ("w"): 32-row blocks, 16-channel K-steps, 32-channel
 // output blocks.  A 32x32x16 MFMA holds the SIMD's vector issue for 8 of its 32 cycles, so one wave
@@ -646,17 +647,9 @@ static int rr3w_launch(RrArgs a, int B, hipStream_t st) {
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
   a.ntiles = a.tiles_per_b * B;
-  auto kern = mrf_rr3w_kernel<C, NB, NWV, PF, RM>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>(cus, (a.ntiles + NWV - 1) / NWV);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NWV * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_rr3w_kernel<C, NB, NWV, PF, RM>, a, (a.ntiles + NWV - 1) / NWV, NWV * 64, lds, false, st);
 }
+#endif  // VO_ABLATIONS
 
 template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false>
 static int rr3_launch(RrArgs a, int B, hipStream_t st) {
@@ -665,18 +658,11 @@ static int rr3_launch(RrArgs a, int B, hipStream_t st) {
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
   a.ntiles = a.tiles_per_b * B;
-  auto kern = mrf_rr3_kernel<C, NB, NWV, PF, PA, PL>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>(cus, (a.ntiles + NWV - 1) / NWV);  // one workgroup per CU
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NWV * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  // one workgroup per CU, a tile per wave
+  return mrf_launch(mrf_rr3_kernel<C, NB, NWV, PF, PA, PL>, a, (a.ntiles + NWV - 1) / NWV, NWV * 64, lds, false, st);
 }
 
+#ifdef VO_ABLATIONS  // measured and dropped (pair_cfg 90-100): in the A/B library only
 // ------------------------------------------------------------------------------------------------
 // The same formulation for a k = 7 / 11 ResBlock iteration (vo_resblock_pair):
 //   y = (x + c2(lrelu(c1_D(lrelu x)))) * out_scale (+ acc)
@@ -930,16 +916,7 @@ static int rrp_launch(RrpArgs a, int B, hipStream_t st) {
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
   a.ntiles = a.tiles_per_b * B;
-  auto kern = mrf_rrp_kernel<C, K, D, NB, NWV, RT>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>(cus, (a.ntiles + NWV - 1) / NWV);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NWV * 64), lds, st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_rrp_kernel<C, K, D, NB, NWV, RT>, a, (a.ntiles + NWV - 1) / NWV, NWV * 64, lds, false, st);
 }
 
 template <int C, int K, int NB, int NWV, bool RT = false>
@@ -948,27 +925,28 @@ static int rrp_launch_d(RrpArgs a, int B, int dil, hipStream_t st) {
   if (dil == 3) return rrp_launch<C, K, 3, NB, NWV, RT>(a, B, st);
   return rrp_launch<C, K, 5, NB, NWV, RT>(a, B, st);
 }
+#endif  // VO_ABLATIONS
 
 }  // namespace vo
 
 using namespace vo;
 
-// vo_resblock3's register-resident path (C = 32 / 64, dilations (1, 3, 5)); *handled = 0 leaves
-// the call to the LDS-frame kernel
-int vo_rb3_rr_try(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C, float slope,
-                  float out_scale, int cfg, hipStream_t st, int* handled) {
+// vo_resblock3's register-resident path (C = 32; C = 64 in the A/B library; dilations (1, 3, 5)); *handled = 0
+// leaves the call to the LDS-frame kernel
+int vo_rb3_rr_try(const MrfBlock3Call& c, int cfg, int* handled) {
+  const int B = c.B, C = c.C;
+  hipStream_t st = c.st;
   *handled = 0;
-  if (!(C == 32 || C == 64) || dil[0] != 1 || dil[1] != 3 || dil[2] != 5) return VO_OK;
-  if ((int64_t)T * C * 2 >= (int64_t)1 << 31) return VO_OK;  // buffer ranges are 32-bit
+  if (!(C == 32 || C == 64) || c.dil[0] != 1 || c.dil[1] != 3 || c.dil[2] != 5) return VO_OK;
+  if ((int64_t)c.T * C * 2 >= (int64_t)1 << 31) return VO_OK;  // buffer ranges are 32-bit
   RrArgs a;
-  a.x = (const bf16_t*)x;
+  a.x = (const bf16_t*)c.x;
   for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)w1[s]; a.bias[2 * s] = b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)w2[s]; a.bias[2 * s + 1] = b2[s];
+    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.bias[2 * s] = c.b1[s];
+    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.bias[2 * s + 1] = c.b2[s];
   }
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.slope = slope; a.out_scale = out_scale;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
 #ifdef VO_ABLATIONS  // the other frame shapes / MFMA forms, measured
   *handled = 1;
   if (C == 32) {
@@ -1000,19 +978,20 @@ int vo_rb3_rr_try(const void* x, const void* const* w1, const float* const* b1, 
   return rr3_launch<32, 8, 8, false>(a, B, st);
 }
 
-// vo_resblock_pair's register-resident path (C = 32, K = 7 / 11, dilations 1 / 3 / 5)
-int vo_pair_rr_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled) {
+#ifdef VO_ABLATIONS
+// vo_resblock_pair's register-resident path (C = 32 / 64, K = 7 / 11, dilations 1 / 3 / 5), measured and dropped
+// (DESIGN.md section 3, round 4): reached under pair_cfg 90-100 only
+int vo_pair_rr_try(const MrfPairCall& c, int cfg, int* handled) {
+  const int B = c.B, C = c.C, K = c.K, dil = c.dil;
+  hipStream_t st = c.st;
   *handled = 0;
   if (!(C == 32 || C == 64) || !(K == 7 || K == 11) || !(dil == 1 || dil == 3 || dil == 5)) return VO_OK;
-  if ((int64_t)T * C * 2 >= (int64_t)1 << 31) return VO_OK;
+  if ((int64_t)c.T * C * 2 >= (int64_t)1 << 31) return VO_OK;
   RrpArgs a;
-  a.x = (const bf16_t*)x;
-  a.w[0] = (const bf16_t*)w1; a.bias[0] = b1; a.w[1] = (const bf16_t*)w2; a.bias[1] = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.slope = slope; a.out_scale = out_scale;
-#ifdef VO_ABLATIONS  // other frame shapes
+  a.x = (const bf16_t*)c.x;
+  a.w[0] = (const bf16_t*)c.w1; a.bias[0] = c.b1; a.w[1] = (const bf16_t*)c.w2; a.bias[1] = c.b2;
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
   *handled = C == 32;
   if (C == 32 && cfg == 90) return K == 7 ? rrp_launch_d<32, 7, 12, 8>(a, B, dil, st) : rrp_launch_d<32, 11, 12, 8>(a, B, dil, st);
   if (C == 32 && cfg == 91) return K == 7 ? rrp_launch_d<32, 7, 16, 4>(a, B, dil, st) : rrp_launch_d<32, 11, 16, 4>(a, B, dil, st);
@@ -1033,20 +1012,16 @@ int vo_pair_rr_try(const void* x, const void* w1, const float* b1, const void* w
       if (K == 7) return dil == 5 ? rrp_launch_d<64, 7, 9, 4>(a, B, dil, st) : rrp_launch_d<64, 7, 8, 4>(a, B, dil, st);
       if (dil == 1) return rrp_launch<64, 11, 1, 8, 4, true>(a, B, st);
     }
+    // 100: k = 7, one wave per SIMD, 144-row frames (9 blocks), the shipped C = 64 k = 7 kernel of round 4: 0.326 ->
+    // 0.264 / 0.293 / 0.313 ms at d = 1 / 3 / 5 against the version-2 kernel (128-row frames, pair_cfg 95: 0.262 /
+    // 0.289 / 0.328); the plane kernel (resblock_rw.hip) replaced it
+    if (K == 7 && cfg == 100) return rrp_launch_d<64, 7, 9, 4>(a, B, dil, st);
     *handled = 0;
   }
-#endif
-  if (cfg != 0) return VO_OK;
-  if (C == 64) {
-    // k = 7, one wave per SIMD, 144-row frames (9 blocks): 0.326 -> 0.264 / 0.293 / 0.313 ms at d = 1 / 3 / 5
-    // (pair_cfg 0 / 98 before the switch; 128-row frames, pair_cfg 95: 0.262 / 0.289 / 0.328)
-    if (K != 7) return VO_OK;
-    *handled = 1;
-    return rrp_launch_d<64, 7, 9, 4>(a, B, dil, st);
-  }
-  // C = 32 keeps the LDS-tile kernels: at d = 1 the frames (pair_cfg 93 in the A/B library) measure
-  // faster alone (k = 7 0.197 -> 0.187 ms, k = 11 0.238 -> 0.217) but ~9 us per launch slower inside the
-  // bench step (tools/bench_ab.sh: s3 0.1947 vs 0.1921 ms per launch, two rounds); at d = 3 / 5 the
-  // halo, (K - 1) / 2 * (d + 1) rows per side, costs more than the frames save
+  // C = 32 keeps the LDS-tile kernels: at d = 1 the frames (pair_cfg 93) measure faster alone (k = 7 0.197 ->
+  // 0.187 ms, k = 11 0.238 -> 0.217) but ~9 us per launch slower inside the bench step (tools/bench_ab.sh: s3
+  // 0.1947 vs 0.1921 ms per launch, two rounds); at d = 3 / 5 the halo, (K - 1) / 2 * (d + 1) rows per side, costs
+  // more than the frames save
   return VO_OK;
 }
+#endif  // VO_ABLATIONS

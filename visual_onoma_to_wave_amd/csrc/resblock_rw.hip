@@ -385,50 +385,33 @@ static int prw_launch(PrwArgs a, int B, hipStream_t st) {
   constexpr int BT = rw_r1(C) - 2 * ((K - 1) / 2);
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
-  auto kern = mrf_prw_kernel<C, K, ACC, FR>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
-  const int grid = (int)std::min<int64_t>((int64_t)cus, a.ntiles);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), rw_lds(C), st, a);
-  VO_RETURN_LAUNCH();
+  return mrf_launch(mrf_prw_kernel<C, K, ACC, FR>, a, a.ntiles, 256, rw_lds(C), false, st);
 }
 
 }  // namespace vo
 
 using namespace vo;
 
-// Entry from vo_resblock_pair (resblock.hip): *handled = 1 when this kernel covers the shape
-// (C = 64 / 128, K = 7 / 11, (K - 1) * dil <= 64).  pair_cfg 93 / 99 (C = 128) and 111 (C = 64) select the
-// earlier LDS-tile kernels for A/B runs.  Measured at B = 32 (tools/mrf_bench.py, with the MRF accumulator):
-// C = 64 k = 11 355 us vs 426, k = 7 275 vs 286 (mean over d = 1 / 3 / 5).
-int vo_pair_rw_try(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
-                   const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale, int cfg,
-                   hipStream_t st, int* handled, int frag) {
+// Entry from vo_resblock_pair (resblock.hip) and, with frag, vo_resblock_pair_frag: *handled = 1 when this kernel
+// covers the shape (C = 64 / 128, K = 7 / 11, (K - 1) * dil <= 64).  pair_cfg 93 / 99 (and 111 at C = 64) leave the
+// shape to the LDS-tile kernels: the generic ones of resblock.hip in the shipped library; in the A/B library the
+// version-2 kernel at C = 64.  Measured at B = 32 against that version-2 kernel (tools/mrf_bench.py, with the MRF
+// accumulator): C = 64 k = 11 355 us vs 426, k = 7 275 vs 286 (mean over d = 1 / 3 / 5).
+int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
+  const int B = c.B, C = c.C, K = c.K;
+  hipStream_t st = c.st;
   *handled = 0;
   // (C = 32 instantiates too, but measured 4-9 % slower than the LDS-tile kernel at B = 32: 210-258 us vs
   // 197-242 for k = 7 / 11, tools/mrf_bench.py --stages 3 -- one 32-channel plane per wave leaves 16
   // steps per tap for the same per-tap A pieces, staging and epilogue work; not dispatched)
-  if (!((C == 128 || C == 64) && (K == 7 || K == 11) && dil >= 1 && dil * (K - 1) <= 64)) return VO_OK;
-  if (!frag && (cfg == 93 || cfg == 99)) return VO_OK;  // 93: the LDS-tile kernels (A/B)
+  if (!((C == 128 || C == 64) && (K == 7 || K == 11) && c.dil >= 1 && c.dil * (K - 1) <= 64)) return VO_OK;
+  if (!frag && (cfg == 93 || cfg == 99)) return VO_OK;
   if (!frag && C == 64 && cfg == 111) return VO_OK;
   PrwArgs a;
-  a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2;
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
-  a.T = T; a.dil = dil; a.slope = slope; a.out_scale = out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  mrf_pair_args(a, c);
   a.stamps = nullptr;
   *handled = 1;
-  // acc_in / out_scale through the identity MFMA when 1 / out_scale is a bf16 value (the MRF's 1/3 -> 3)
-  int accm = 0;
-  if (acc) {
-    const float inv = 1.0f / out_scale;
-    const float invb = __bfloat162float(__float2bfloat16(inv));
-    accm = (invb == inv && std::isfinite(inv) && inv * out_scale == 1.0f) ? 2 : 1;
-  }
+  const int accm = mrf_acc_mode(c.acc, c.out_scale);
 #define VO_PRW_DISPATCH(CC, KK, FF) \
   return accm == 2 ? prw_launch<CC, KK, 2, FF>(a, B, st) : accm == 1 ? prw_launch<CC, KK, 1, FF>(a, B, st) \
                                                         : prw_launch<CC, KK, 0, FF>(a, B, st)
@@ -475,17 +458,10 @@ extern "C" int vo_pack_frag(const void* src, void* dst, int C, int K, void* stre
 extern "C" int vo_resblock_pair_frag(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                                      void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
                                      float out_scale, void* stream) {
-  VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && y, "resblock_pair_frag: null pointer");
-  VO_CHECK_ARG((C == 64 || C == 128) && (K == 7 || K == 11) && dil >= 1 && dil * (K - 1) <= 64,
-               "resblock_pair_frag: C=%d K=%d dil=%d unsupported (C = 64 / 128, K = 7 / 11, (K-1)*dil <= 64)", C, K,
-               dil);
-  VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "resblock_pair_frag: slope %g outside [0, 1]", slope);
-  VO_CHECK_ARG(B > 0 && T > 0, "resblock_pair_frag: empty");
-  VO_CHECK_ARG(y != x, "resblock_pair_frag: y must not alias x (neighbouring tiles re-read x)");
-  VO_CHECK_ARG(acc == nullptr || acc == y || acc != x, "resblock_pair_frag: acc must not alias x");
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, reinterpret_cast<hipStream_t>(stream)};
+  if (const int rc = vo_pair_check(c, true)) return rc;
   int handled = 0;
-  return vo_pair_rw_try(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, 0,
-                        reinterpret_cast<hipStream_t>(stream), &handled, 1);
+  return vo_pair_rw_try(c, 0, 1, &handled);
 }
 
 #ifdef VO_PRW_STAMPS

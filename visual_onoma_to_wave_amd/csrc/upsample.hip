@@ -384,19 +384,13 @@ static int launch_upsw(const vo_conv1d_desc* d, hipStream_t st) {
   a.slope = d->pre_act == VO_ACT_LRELU ? d->pre_slope : (d->pre_act == VO_ACT_RELU ? 0.f : 1.f);
   w.nc = d->Co;
   w.ncb_n = d->Co / NCB;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
   // resident workgroups only (persistent); run groups in multiples of 8 (one per XCD slot)
   const size_t lds_b = 2 * (size_t)NCB * CI * sizeof(bf16_t) + NCB * sizeof(float);
   int per_cu = 0;  // LDS- and register-limited resident workgroups per CU
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, upsw_kernel<CI, NCB, NJ, NW>, NW * 64, lds_b) != hipSuccess ||
       per_cu < 1)
     per_cu = 1;
-  const int slots = std::max(1, cus * per_cu / 8);         // workgroup slots per XCD
+  const int slots = std::max(1, cu_count() * per_cu / 8);         // workgroup slots per XCD
   const int rg_per_xcd = std::max(1, slots / w.ncb_n);
   const int need = (a.units + 8 * NW - 1) / (8 * NW);      // >= 8 units per wave
   w.rgroups = std::min(8 * rg_per_xcd, std::max(1, need));
@@ -420,15 +414,9 @@ static int launch_ups(const vo_conv1d_desc* d, hipStream_t st) {
   a.units = a.nblk * d->B;
   a.slope = d->pre_act == VO_ACT_LRELU ? d->pre_slope : (d->pre_act == VO_ACT_RELU ? 0.f : 1.f);
   auto kern = ups_kernel<CI, NC, NJ>;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-  }
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int grid = (int)std::min<int64_t>((int64_t)cus * per_cu, (a.units + 3) / 4);  // a wave per run
+  const int grid = (int)std::min<int64_t>((int64_t)cu_count() * per_cu, (a.units + 3) / 4);  // a wave per run
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, a);
   VO_RETURN_LAUNCH();
 }

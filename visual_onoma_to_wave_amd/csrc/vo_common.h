@@ -225,6 +225,19 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- host: device query
+// compute units of the current device, queried once (256, the MI355X's, when the query fails):
+// what the persistent launchers size their grids by
+inline int cu_count() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+  }
+  return n;
+}
+
 }  // namespace vo
 
 // error plumbing shared by the launchers (vo_runtime.cpp)

@@ -45,15 +45,15 @@ static void knobs_from_env() {
   }
 }
 
-// pair_cfg values that select timing ablations (kernels that skip loads: garbage results); only
-// a build with -DVO_ABLATIONS dispatches them, and vo_tune rejects them in the shipped library
+// knob values that select timing ablations (kernels that skip loads: garbage results); only
+// a build with -DVO_ABLATIONS accepts them, and vo_tune rejects them in the shipped library
 static bool is_ablation(const char* key, int value) {
 #ifdef VO_ABLATIONS
   (void)key; (void)value;
   return false;
 #else
   return (!strcmp(key, "pair_cfg") && (value == 13 || value == 16 || value == 17 || value == 25)) ||
-         (!strcmp(key, "pc_cfg") && value >= 8);
+         (!strcmp(key, "pc_cfg") && value >= 8) || (!strcmp(key, "wgrad_cfg") && value == 11);
 #endif
 }
 
