@@ -46,8 +46,9 @@ const char* vo_last_error(void);
 /* ABI version of this header; vo_version() returns the library's.  A binding checks they are equal
  * at load time.  2 (round 4): vo_bucket_embed gained n_table (before n), vo_conv1d_desc gained
  * ymask / ymask_slope at its end -- a version-1 binding would pass shifted arguments or leave the
- * new fields uninitialised. */
-#define VO_ABI_VERSION 2
+ * new fields uninitialised.  3: vo_conv1d_desc gained lens / lens_scale at its end (a version-2 binding would
+ * leave them uninitialised), and the vo_*_lens entries below. */
+#define VO_ABI_VERSION 3
 int vo_version(void);
 /* number of entry points and their names (used by the loader test) */
 int vo_num_symbols(void);
@@ -108,8 +109,23 @@ typedef struct vo_conv1d_desc {
                          -- an input gradient masked by the leaky-ReLU output it flows into, as
                          vo_lrelu_mask would mask it (HiFi-GAN discriminators, D step)          */
   float ymask_slope;
+  const int32_t* lens; /* optional (NULL = dense): ragged batch, see "per-utterance lengths" below.  Same-length
+                         convs only (T_out = T_in, 2 pad = (K - 1) dil; polyphase: T_out = T_in + 1); refused
+                         with stride > 1, groups > 1, a workspace, ymask, VO_F32X3 and T_out <= 16 in fp32     */
+  int lens_scale;      /* rows of x per unit of lens (>= 1 when lens is given)                              */
 } vo_conv1d_desc;
 int vo_conv1d(const vo_conv1d_desc* d, void* stream);
+/* Per-utterance lengths (ragged batches; the HiFi-GAN vocoder path: vo_conv1d with lens, vo_resblock_pair_lens,
+ * vo_resblock_pair_frag_lens, vo_resblock3_lens, vo_conv_post_lens).  lens: B device int32; utterance b of a
+ * (B, T, C) tensor has R_b = clamp(lens[b] * lens_scale, 0, T) valid rows (lens in mel frames, lens_scale the rows
+ * per frame at that layer: 1, 8, 64, 128, 256 in HiFi-GAN V1).  The call computes what the dense call computes on the
+ * tensor x[b, :R_b] alone: every read of a row outside [0, R_b) -- input, residuals, the MRF accumulator and the
+ * fused kernels' on-chip intermediates -- yields zero, and rows >= R_b of the output are neither read nor written
+ * (vo_conv_post_lens stores 0.0f there).  For the polyphase upsampler R_b counts input rows; its output has
+ * R_b * up_stride rows.  The lengths are read on the device only: no host synchronisation, graph-capturable, and a
+ * replay follows lengths changed in place.  The persistent kernels walk a compacted tile list (no tile past an
+ * utterance's end), so the work is proportional to sum_b R_b.  A vo_tune knob that selects a kernel without a
+ * ragged form is refused with an error naming the knob. */
 /* scratch bytes the split-reduction path of vo_conv1d wants for d (0 = it does not split d) */
 int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d);
 /* The tile the last vo_conv1d call of the calling thread launched (host bookkeeping only: the tests
@@ -310,6 +326,9 @@ int vo_mask_from_lengths(const void* lens, int lens_dtype, int B, int L, bool* m
  * (scripts/hifigan/models.py:161-163).  w packed [K][C] fp32. */
 int vo_conv_post(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
                  int K, float slope, float* y, void* stream);
+/* vo_conv_post on a ragged batch (per-utterance lengths, above): y[b, t] = 0.0f for t >= R_b. */
+int vo_conv_post_lens(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
+                      int K, float slope, float* y, void* stream, const int32_t* lens, int lens_scale);
 /* Fused ResBlock1 pair for C = 32 / 64 / 128 (bf16, channels-last (B, T, C)):
  *   y = (x + c2(lrelu(c1_dil(lrelu(x, slope)), slope))) * out_scale (+ acc)
  * c1 / c2: K taps, packed [K][C][C] bf16 (vo_pack_weight VO_PACK_CONV), biases fp32;
@@ -320,6 +339,11 @@ int vo_conv_post(const void* x, int x_dtype, const float* w, float bias, int B, 
 int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2,
                      const float* b2, void* y, const void* acc, int B, int T, int C, int K,
                      int dil, float slope, float out_scale, void* stream);
+/* vo_resblock_pair on a ragged batch (per-utterance lengths, above): K = 7 / 11 (the shapes the vocoder runs as
+ * pairs), shipped dispatch only. */
+int vo_resblock_pair_lens(const void* x, const void* w1, const float* b1, const void* w2,
+                          const float* b2, void* y, const void* acc, int B, int T, int C, int K,
+                          int dil, float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale);
 /* vo_resblock_pair for C = 64 / 128, K = 7 / 11 with w1 / w2 in the fragment order that the pair
  * kernel streams into registers (vo_pack_frag of the [K][C][C] pack): every weight load is one
  * contiguous KiB.  C = 128: results equal vo_resblock_pair's on the same weights bit for bit.  Same
@@ -327,6 +351,11 @@ int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void*
 int vo_resblock_pair_frag(const void* x, const void* w1, const float* b1, const void* w2,
                           const float* b2, void* y, const void* acc, int B, int T, int C, int K,
                           int dil, float slope, float out_scale, void* stream);
+/* vo_resblock_pair_frag on a ragged batch (per-utterance lengths, above). */
+int vo_resblock_pair_frag_lens(const void* x, const void* w1, const float* b1, const void* w2,
+                               const float* b2, void* y, const void* acc, int B, int T, int C, int K,
+                               int dil, float slope, float out_scale, void* stream, const int32_t* lens,
+                               int lens_scale);
 /* [K][C][C] bf16 (vo_pack_weight VO_PACK_CONV), C = 64 / 128 -> [K][C/32][C/32][2][64][8] fragment order:
  * dst[k][p][s][t][l][e] = src[k][32p + 8((l & 15) >> 2) + 4t + (l & 3)][32s + 8(l >> 4) + e]. */
 int vo_pack_frag(const void* src, void* dst, int C, int K, void* stream);
@@ -343,6 +372,11 @@ int vo_pack_frag(const void* src, void* dst, int C, int K, void* stream);
 int vo_resblock3(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
                  float slope, float out_scale, void* stream);
+/* vo_resblock3 on a ragged batch (per-utterance lengths, above): C = 64 / 128, or C = 32 with dilations (1, 3, 5);
+ * shipped dispatch only. */
+int vo_resblock3_lens(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
+                      const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
+                      float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale);
 
 /* (B, C, T) -> (B, T, ldy) with channels C..ldy-1 zero-filled; fp32 in, dtype out. */
 int vo_transpose_bct(const float* x, int B, int C, int T, void* y, int y_dtype, int ldy,

@@ -43,6 +43,7 @@ class Conv1dDesc(ctypes.Structure):
         ("stride", c_int), ("groups", c_int),
         ("workspace", c_void_p), ("workspace_bytes", ctypes.c_int64),
         ("ymask", c_void_p), ("ymask_slope", c_float),
+        ("lens", c_void_p), ("lens_scale", c_int),
     ]
 
 
@@ -106,6 +107,15 @@ _SIGNATURES = {
     "vo_resblock_pair_frag": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "vo_pack_frag": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    # the ragged-batch entries: their dense siblings' signatures + (lens, lens_scale)
+    "vo_resblock_pair_lens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
+    "vo_resblock_pair_frag_lens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
+    "vo_resblock3_lens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
+    "vo_conv_post_lens": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_int]),
     "vo_resblock3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                              c_int, c_int, c_float, c_float, c_void_p]),
     "vo_conv1d": (c_int, [ctypes.POINTER(Conv1dDesc), c_void_p]),
@@ -230,7 +240,7 @@ _SIGNATURES = {
                                c_int, c_int, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 2  # include/vonoma.h VO_ABI_VERSION
+ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION
 _lib = None
 
 

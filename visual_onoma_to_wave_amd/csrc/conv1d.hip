@@ -50,6 +50,8 @@ struct ConvArgs {
   int kcs;         // 32-channel chunks per split (grid z = split)
   const void* ymask;  // outputs stored as round(round(v) * (ymask > 0 ? 1 : ymask_slope)) (y's layout)
   float ymask_slope;
+  const int32_t* lens;  // ragged batch (vonoma.h): utterance b has clamp(lens[b] * lens_scale, 0, T_in) input rows
+  int lens_scale;
 };
 
 template <typename T> struct Raw8;  // 8 elements of T held in registers
@@ -364,9 +366,11 @@ __device__ __forceinline__ void wait_vmcnt() {
 // reads for 9.4 MB of weights).  Halo <= SEG_HALO.
 constexpr int SEG_HALO = 8;
 template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS, bool NICE, int ROLE,
-          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false>
+          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false,
+          bool RAG = false>
 __global__ void __launch_bounds__(WCO * WT * 64)
 conv1d_kernel(ConvArgs a) {
+  static_assert(!RAG || (!SEG && S == 1), "conv1d RAG: whole-utterance tiles, stride 1");
   static_assert(!SEG || (sizeof(TC) == 4 && S == 1 && !GL), "conv1d SEG: 4-byte compute, stride 1");
   constexpr int NT = WCO * WT * 64;
   constexpr int BCO = 16 * NI * WCO;
@@ -404,6 +408,17 @@ conv1d_kernel(ConvArgs a) {
   const int b = SEG ? blockIdx.x * (BT / 16) : blockIdx.x / a.tiles_per_b;  // SEG: the tile's first utterance
   const int t0 = SEG ? 0 : (blockIdx.x - b * a.tiles_per_b) * BT;
   const int co_blk = blockIdx.y * BCO;
+  if constexpr (RAG) {
+    // ragged batch (a.lens; never SEG / strided / split: vo_conv1d rejects those): utterance b is a tensor of R rows -- its
+    // bounds replace the batch's in this workgroup's copy of the arguments (the batch strides stay), and a tile that
+    // starts past its output rows has nothing to do.  Polyphase form: R + 1 phase rows, (R + 1) s - 2 p output rows.
+    const int R = rag_rows(a.lens, a.lens_scale, b, a.T_in);
+    const int rows = a.transposed ? R + 1 : R;
+    if (R == 0 || t0 >= rows) return;
+    a.T_in = R;
+    a.T_out = rows;
+    a.up_tout = min(a.up_tout, (R + 1) * a.up_stride - 2 * a.up_pad);
+  }
 
   const TIN* __restrict__ X = reinterpret_cast<const TIN*>(a.x) + (int64_t)b * a.xbs;
   const TC* __restrict__ Wp = reinterpret_cast<const TC*>(a.w);
@@ -981,7 +996,8 @@ __global__ void __launch_bounds__(WCO * WT * 64) lin_kernel(ConvArgs a) {
 // ------------------------------------------------------------------ host dispatch
 static bool splitk_plan(const vo_conv1d_desc* d, int* splits, int* kcs);
 template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS_BF16, int ROLE = 0,
-          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false>
+          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false,
+          bool RAG = false>
 static int launch_cfg_s(const vo_conv1d_desc* d, hipStream_t st) {
   constexpr int BCO = 16 * NI * WCO;
   constexpr int BT = 16 * NJ * WT;
@@ -1001,6 +1017,11 @@ static int launch_cfg_s(const vo_conv1d_desc* d, hipStream_t st) {
   a.co_tiles = (d->Co + BCO - 1) / BCO;
   a.B = d->B;
   a.ymask = d->ymask; a.ymask_slope = d->ymask_slope;
+  a.lens = d->lens; a.lens_scale = d->lens_scale;
+  // the ragged instantiations (RAG) exist for the tiles launch_types picks and the MRF stage-0 role: a call with
+  // lens that reaches any other tile is refused, never run dense
+  VO_CHECK_ARG((d->lens != nullptr) == RAG, "conv1d: no ragged (lens) form of this tile (%s)",
+               SEG ? "utterance-segment tiles: T_out <= 16 in fp32" : "strided / grouped / variant 2-4");
   const int groups = d->groups > 1 ? d->groups : 1;
   a.cig = d->Ci / groups;
   a.cog = d->Co / groups;
@@ -1015,14 +1036,14 @@ static int launch_cfg_s(const vo_conv1d_desc* d, hipStream_t st) {
     vo_set_error("conv1d: LDS request %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  auto kern = nice ? conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, true, ROLE, PRIO, ABL, S, GL, RS, EJ, SEG>
-                   : conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, false, ROLE, PRIO, ABL, S, false, false, 2, SEG>;
+  auto kern = nice ? conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, true, ROLE, PRIO, ABL, S, GL, RS, EJ, SEG, RAG>
+                   : conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, false, ROLE, PRIO, ABL, S, false, false, 2, SEG, RAG>;
   a.partial = nullptr;
   a.kcs = 0;
   int splits = 1;
   if constexpr (S == 1) {
     int kcs = 0;
-    if (d->workspace && splitk_plan(d, &splits, &kcs) &&
+    if (d->workspace && !d->lens && splitk_plan(d, &splits, &kcs) &&
         d->workspace_bytes >= (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float)) {
       a.partial = reinterpret_cast<float*>(d->workspace);
       a.kcs = kcs;
@@ -1047,6 +1068,12 @@ template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int
           int PRIO = 0, int ABL = 0, bool GL = false, bool RS = false, int EJ = 2>
 static int launch_cfg(const vo_conv1d_desc* d, hipStream_t st) {
   return launch_cfg_s<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS_BF16, ROLE, PRIO, ABL, 1, GL, RS, EJ>(d, st);
+}
+// launch_cfg with the ragged flag in front: launch_types passes its own
+template <bool RAG, typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS_BF16, int ROLE = 0,
+          int PRIO = 0, int ABL = 0, bool GL = false, bool RS = false, int EJ = 2>
+static int launch_cfg_r(const vo_conv1d_desc* d, hipStream_t st) {
+  return launch_cfg_s<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS_BF16, ROLE, PRIO, ABL, 1, GL, RS, EJ, false, RAG>(d, st);
 }
 template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT>
 static int launch_seg(const vo_conv1d_desc* d, hipStream_t st) {
@@ -1074,6 +1101,7 @@ static int launch_lin(const vo_conv1d_desc* d, hipStream_t st) {
   a.B = d->B;
   a.cig = d->Ci; a.cog = d->Co;
   a.ymask = d->ymask; a.ymask_slope = d->ymask_slope;
+  a.lens = nullptr; a.lens_scale = 0;
   auto kern = lin_kernel<TOUT, NI, NJ, WCO, WT, D, NC>;
   dim3 grid((unsigned)(a.tiles_per_b * d->B), (unsigned)a.co_tiles);
   hipLaunchKernelGGL(kern, grid, dim3(WCO * WT * 64), 0, st, a);
@@ -1123,7 +1151,8 @@ static int lin_tile(const vo_conv1d_desc* d, hipStream_t st, int lc) {
 }
 #endif  // VO_ABLATIONS
 
-template <typename TIN, typename TC, typename TOUT>
+// RAG: the ragged instantiations of the same tiles (vo_conv1d with lens)
+template <typename TIN, typename TC, typename TOUT, bool RAG = false>
 static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
   const int64_t rows = (int64_t)d->B * d->T_out;
   // short sequences (the glyph encoder / phoneme-level predictors run at T_src ~ 12): one
@@ -1143,21 +1172,21 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
     // workgroups of 128 x 16: FFN w_1 66 -> 51 us, w_2 28 -> 20, predictor k3 20 -> 13
     // (tools/ab_sb.py genf32 5 3); gen_cfg 2 = 64 x 16, 5 = 128 x 16
     const int gc = vo_tune_get("gen_cfg");
-    if (gc == 2) return launch_cfg<TIN, TC, TOUT, 1, 1, 4, 1, 4>(d, st);  // 64 x 16
-    if (gc != 5 && sizeof(TC) == 4) return launch_cfg<TIN, TC, TOUT, 1, 1, 2, 1, 4>(d, st);  // 32 x 16
-    return launch_cfg<TIN, TC, TOUT, 2, 1, 4, 1, 4>(d, st);  // 128 x 16
+    if (gc == 2) return launch_cfg_r<RAG, TIN, TC, TOUT, 1, 1, 4, 1, 4>(d, st);  // 64 x 16
+    if (gc != 5 && sizeof(TC) == 4) return launch_cfg_r<RAG, TIN, TC, TOUT, 1, 1, 2, 1, 4>(d, st);  // 32 x 16
+    return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 1, 4, 1, 4>(d, st);  // 128 x 16
   }
-  if (d->T_out <= 32 && d->Co >= 64) return launch_cfg<TIN, TC, TOUT, 2, 2, 4, 1, 4>(d, st);  // 128 x 32
-  if (d->Co <= 32) return launch_cfg<TIN, TC, TOUT, 2, 4, 1, 4, 4>(d, st);   // 32 x 256
+  if (d->T_out <= 32 && d->Co >= 64) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 2, 4, 1, 4>(d, st);  // 128 x 32
+  if (d->Co <= 32) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 1, 4, 4>(d, st);   // 32 x 256
   if (d->Co <= 64 || d->Co == 80) {
     // Co = 80 (PostNet output conv, mel_linear at B*T = 16384 rows): 64 x 128 tiles, twice the
     // workgroups of 64 x 256 (512 -> 80 k5 36.7 -> 29.7 us; tools/probes/small_convs.py)
     const int gc = vo_tune_get("gen_cfg");
-    if (gc == 6 || (d->Co == 80 && gc != 8)) return launch_cfg<TIN, TC, TOUT, 4, 2, 1, 4, 4>(d, st);  // 64 x 128
-    if (gc == 7) return launch_cfg<TIN, TC, TOUT, 4, 1, 1, 4, 4>(d, st);  // 64 x 64
-    return launch_cfg<TIN, TC, TOUT, 4, 4, 1, 4, 4>(d, st);  // 64 x 256
+    if (gc == 6 || (d->Co == 80 && gc != 8)) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 2, 1, 4, 4>(d, st);  // 64 x 128
+    if (gc == 7) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 1, 1, 4, 4>(d, st);  // 64 x 64
+    return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 1, 4, 4>(d, st);  // 64 x 256
   }
-  if (rows <= 2048) return launch_cfg<TIN, TC, TOUT, 2, 2, 2, 2, 2>(d, st);  // 64 x 64
+  if (rows <= 2048) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 2, 2, 2, 2>(d, st);  // 64 x 64
 #ifdef VO_ABLATIONS
   if constexpr (sizeof(TC) == 2 && sizeof(TIN) == 2) {
     // K = 1 (Linear layers), A/B only: the LDS-free register-ring kernel, lin_cfg 2 / 3 / 4 / 5 =
@@ -1176,15 +1205,15 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
 #ifdef VO_ABLATIONS
   if constexpr (sizeof(TC) == 2) {  // K = 1 staging A/B: one tap per step (TPS 1), weights by LDS-DMA (GL), role split (RS)
     const int gq = vo_tune_get("gen_cfg");
-    if (gq == 13 && d->Co % 256 == 0) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, false>(d, st);
-    if (gq == 14 && d->Co % 256 == 0) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, true>(d, st);
-    if (gq == 15 && d->Co % 128 == 0) return launch_cfg<TIN, TC, TOUT, 4, 4, 2, 2, 1, 0, 0, 0, true, false>(d, st);
-    if (gq == 16 && d->Co % 256 == 0) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 1>(d, st);
-    if (gq == 17) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 1>(d, st);  // 64 x 128, TPS 1
+    if (gq == 13 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, false>(d, st);
+    if (gq == 14 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, true>(d, st);
+    if (gq == 15 && d->Co % 128 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 2, 1, 0, 0, 0, true, false>(d, st);
+    if (gq == 16 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1>(d, st);
+    if (gq == 17) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 1>(d, st);  // 64 x 128, TPS 1
   }
 #endif
   if constexpr (sizeof(TC) == 2) {
-    if (d->workspace && splitk_bf16_ok(d)) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // split 256 x 256
+    if (d->workspace && splitk_bf16_ok(d)) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // split 256 x 256
   }
   if constexpr (sizeof(TC) == 2) {
     // decoder shapes at B*T = 16384 rows (tools/ab_sb.py gen): wide outputs (FFN w_1 k9 1024,
@@ -1202,15 +1231,15 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
       // (utterances of >= 256 rows: at T_out = 128 -- the MSD's 1024-channel layers -- half of every 256-row
       // tile was padding: C5 23.68 -> 23.43 ms with them on the tiles below; tile_cfg 9 = the round-5 rule)
       const bool t_ok = d->T_out >= 256 || vo_tune_get("tile_cfg") == 9;
-      if (vo_tune_get("gen_cfg") != 11 && t_ok && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256
-      if (vo_tune_get("gen_cfg") < 9 && d->K == 1 && d->Co <= 256) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);         // 64 x 128
+      if (vo_tune_get("gen_cfg") != 11 && t_ok && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256
+      if (vo_tune_get("gen_cfg") < 9 && d->K == 1 && d->Co <= 256) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);         // 64 x 128
       // Co <= 256 k > 1 with fewer than 512 128 x 128 tiles (the C4 decoder's FFN w_1 input gradient, 1024 ->
       // 256 k9 at 16384 rows: 125 -> 106 us, tools/probes/dgrad_tiles.py): 64 x 128, twice the workgroups
       const int64_t t128 = (int64_t)d->B * ((d->T_out + 127) / 128) * ((d->Co + 127) / 128);
-      if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+      if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
       // wide convs with fewer than 256 128 x 128 tiles (C5's MPD over joined period columns, 1024 -> 1024
       // k = 5 at 2-5 k rows: 136-312 workgroups) on 64 x 128 tiles too: C5 24.07 -> 23.75 ms (tile_cfg 1 = off)
-      if (vo_tune_get("tile_cfg") != 1 && d->Co % 64 == 0 && t128 < 256) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+      if (vo_tune_get("tile_cfg") != 1 && d->Co % 64 == 0 && t128 < 256) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
     }
     // mid-width convs (PostNet 512 -> 512 k5, conv_pre 80 -> 512 k7 at 16384 rows): 128 x 256
     // tiles (twice the rows per staged weight tap): 512 k5 67.9 -> 63.4 us, 80 k7 27.6 -> 27.0,
@@ -1218,16 +1247,16 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
     // it (210 -> 234 us).  gen_cfg 9 forces it, gen_cfg 10 = 256 x 128 (no gain), gen_cfg 1 = 128 x 128.
     const int gc = vo_tune_get("gen_cfg");
     if (gc == 9 || (gc != 1 && gc != 10 && d->Co >= 512 && d->Co < 768 && d->Co % 128 == 0 && !d->transposed))
-      return launch_cfg<TIN, TC, TOUT, 4, 4, 2, 4, 2>(d, st);  // 128 x 256
-    if (gc == 10) return launch_cfg<TIN, TC, TOUT, 4, 4, 4, 2, 2>(d, st);  // 256 x 128
-    if (gc == 11) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);  // 64 x 128 (A/B)
-    if (gc == 12 && d->Co % 256 == 0) return launch_cfg<TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256 (A/B)
+      return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 4, 2>(d, st);  // 128 x 256
+    if (gc == 10) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 4, 2, 2>(d, st);  // 256 x 128
+    if (gc == 11) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);  // 64 x 128 (A/B)
+    if (gc == 12 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256 (A/B)
   }
   if constexpr (sizeof(TC) == 2) {  // bf16: 64 x 128 in place of the 128 x 128 default (C5 23.68 -> 23.52 ms, C4 and
                                     // inference shapes unaffected); tile_cfg 9 = the round-5 rule
-    if (vo_tune_get("tile_cfg") != 9) return launch_cfg<TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+    if (vo_tune_get("tile_cfg") != 9) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
   }
-  return launch_cfg<TIN, TC, TOUT, 4, 4, 2, 2, 2>(d, st);                    // 128 x 128
+  return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 2, 2>(d, st);                    // 128 x 128
 }
 
 }  // namespace vo
@@ -1281,6 +1310,20 @@ extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
                "conv1d: ymask needs a bf16 output without bias, residuals, activation or scale, slope in [0, 1]");
   // split-bf16 compute has no polyphase form: refused before the streaming upsampler can take the call
   VO_CHECK_ARG(!(d->compute_dtype == VO_F32X3 && d->transposed), "conv1d: VO_F32X3 compute excludes transposed");
+  if (d->lens) {
+    // Ragged batch: the forms the vocoder reaches (conv_pre, the polyphase upsamplers, the ResBlock convs).  Anything
+    // else is refused, not run dense.
+    VO_CHECK_ARG(d->lens_scale >= 1, "conv1d: lens_scale %d < 1", d->lens_scale);
+    VO_CHECK_ARG(d->stride <= 1 && d->groups <= 1, "conv1d: lens excludes stride > 1 and groups > 1");
+    VO_CHECK_ARG(!d->workspace, "conv1d: lens excludes a split-reduction workspace");
+    VO_CHECK_ARG(!d->ymask, "conv1d: lens excludes ymask");
+    VO_CHECK_ARG(d->compute_dtype != VO_F32X3, "conv1d: lens excludes VO_F32X3 compute");
+    VO_CHECK_ARG(d->transposed ? d->T_out == d->T_in + 1 : (d->T_out == d->T_in && (d->K - 1) * d->dil == 2 * d->pad),
+                 "conv1d: lens needs a same-length conv (T_out = T_in, 2 pad = (K - 1) dil; polyphase: T_out = T_in + 1)");
+    const int uc = vo_tune_get("ups_cfg");
+    VO_CHECK_ARG(!d->transposed || uc == 0 || uc == 1 || uc == 4,
+                 "conv1d: ups_cfg=%d selects a kernel without a ragged (lens) form", uc);
+  }
   if (d->transposed) {  // narrow upsamplers: the persistent streaming kernel (upsample.hip)
     int handled = 0;
     const int rc = vo_ups_try(d, st, &handled);
@@ -1307,9 +1350,19 @@ extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
   }
   if (d->compute_dtype == VO_F32) {
     VO_CHECK_ARG(xi == VO_F32 && yo == VO_F32, "conv1d: fp32 compute needs fp32 I/O");
+    if (d->lens) return launch_types<float, float, float, true>(d, st);
     return launch_types<float, float, float>(d, st);
   }
   VO_CHECK_ARG(d->compute_dtype == VO_BF16, "conv1d: bad compute dtype");
+  if (d->lens) {  // the vocoder's forms: bf16 activations (MRF stage 0 in its own role), conv_pre reading an fp32 mel
+    VO_CHECK_ARG(yo == VO_BF16 && d->variant <= 1, "conv1d: lens with bf16 compute needs a bf16 output, variant 0 / 1");
+    if (xi == VO_F32) return launch_types<float, bf16_t, bf16_t, true>(d, st);
+    if (d->variant == 0) return launch_types<bf16_t, bf16_t, bf16_t, true>(d, st);
+    const int cc = vo_tune_get("conv_cfg");
+    VO_CHECK_ARG(cc == 0, "conv1d: conv_cfg=%d selects a kernel without a ragged (lens) form", cc);
+    if (d->K >= 5) return launch_cfg_r<true, bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true, true>(d, st);
+    return launch_cfg_r<true, bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true>(d, st);
+  }
   if (xi == VO_BF16 && yo == VO_BF16) {
     switch (d->variant) {  // HiFi-GAN MRF stages: own instantiations (same tiles as generic)
       case 1: {  // C = 256: 256 x 256 tile, 8 waves of 64 co x 128 rows (each weight tap feeds

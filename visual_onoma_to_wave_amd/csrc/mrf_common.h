@@ -61,6 +61,57 @@ __device__ __forceinline__ void unpack8(u32x4 u, float (&f)[8]) {
   }
 }
 
+// ---------------------------------------------------------------- the persistent kernels' tile walk
+// Ragged batches: utterance b of the (B, T, C) tensors has R_b = clamp(lens[b] * scale, 0, T) valid rows; rows
+// outside [0, R_b) read as zero and rows >= R_b are not written.  lens == nullptr: dense (R_b = T).
+struct MrfLens {
+  const int32_t* lens;  // [B] on the device
+  int scale, B;
+};
+struct MrfTile { int b, t0, R; };  // utterance, first row of the tile, valid rows of the utterance
+
+// tile -> (b, t0, R_b) of a kernel whose tiles are BT rows.  Dense: b = tile / tiles_per_b.  RAG: the tiles past an
+// utterance's end do not exist -- utterance b owns ceil((R_b + EX) / BT) consecutive tile ids (none when R_b = 0;
+// EX = rows a kernel computes past R_b: the upsamplers' last phase row), total() of them in the launch, so a
+// workgroup's share of total() is all work.  The prefix sums are never stored: a kernel walks its tile ids upwards,
+// so at() keeps a cursor (utterance, its first tile id, its tile count) and steps it forward, a scalar load of
+// lens[b] per utterance passed; total() and the first at() cost one pass over lens each (B scalar loads).
+// at() wants non-decreasing tile ids below total().  No LDS, no scratch buffer, nothing on the host.
+template <bool RAG, int EX = 0>
+struct MrfWalk {
+  int tiles_per_b, ntiles, T, BT;
+  MrfLens rg;
+  int cb, cbase, cn, cR;
+  __device__ __forceinline__ MrfWalk(int tiles_per_b_, int ntiles_, int T_, int BT_, const MrfLens& rg_)
+      : tiles_per_b(tiles_per_b_), ntiles(ntiles_), T(T_), BT(BT_), rg(rg_), cb(0), cbase(0), cn(0), cR(0) {
+    if constexpr (RAG) {
+      cR = rag_rows(rg.lens, rg.scale, 0, T);
+      cn = count(cR);
+    }
+  }
+  __device__ __forceinline__ int count(int R) const { return R > 0 ? (R + EX + BT - 1) / BT : 0; }
+  __device__ __forceinline__ int total() const {
+    if constexpr (!RAG) return ntiles;
+    int n = 0;
+    for (int b = 0; b < rg.B; ++b) n += count(rag_rows(rg.lens, rg.scale, b, T));
+    return n;
+  }
+  __device__ __forceinline__ MrfTile at(int tile) {
+    if constexpr (!RAG) {
+      const int b = tile / tiles_per_b;
+      return MrfTile{b, (tile - b * tiles_per_b) * BT, T};
+    } else {
+      while (tile >= cbase + cn && cb + 1 < rg.B) {
+        cbase += cn;
+        ++cb;
+        cR = rag_rows(rg.lens, rg.scale, cb, T);
+        cn = count(cR);
+      }
+      return MrfTile{cb, (tile - cbase) * BT, cR};
+    }
+  }
+};
+
 // ---------------------------------------------------------------- host side: launch and dispatch
 // Every MRF kernel is persistent: a workgroup walks its share of `work` items (tiles, or groups of NWV tiles in
 // the kernels whose waves take a tile each).  The grid is min(CUs * per_cu, work) with per_cu = 1, or, with
@@ -93,6 +144,7 @@ struct MrfPairCall {
   int B, T, C, K, dil;
   float slope, out_scale;
   hipStream_t st;
+  const int32_t* lens; int lens_scale;  // ragged batch (vo_*_lens entries); nullptr: dense
 };
 struct MrfBlock3Call {
   const void* x; const void* const* w1; const float* const* b1; const void* const* w2; const float* const* b2;
@@ -101,6 +153,7 @@ struct MrfBlock3Call {
   int B, T, C;
   float slope, out_scale;
   hipStream_t st;
+  const int32_t* lens; int lens_scale;
 };
 
 // the fields every pair kernel's argument struct has, from the call

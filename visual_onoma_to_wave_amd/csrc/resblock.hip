@@ -32,6 +32,7 @@ struct PairArgs {
   bf16_t* y; const bf16_t* acc;
   int T, K, dil, tiles_per_b, ntiles;
   float slope, out_scale;
+  MrfLens rg;  // RAG instantiations: per-utterance lengths (mrf_common.h)
 };
 
 // WC x WT waves: wave (wc, wt) owns channels [wc*C/WC, (wc+1)*C/WC) of rows [wt*16*NJ, ..+16*NJ)
@@ -50,8 +51,10 @@ struct PairArgs {
 // after P2 instead of during it.
 // VD (round 3, "VALU diet"): each conv's bias is the C operand of its first MFMAs (no accumulator
 // zeroing, no bias adds), leaky ReLU in packed fp32, the T1 mask only in boundary tiles.
+// RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
+// T does in the dense form (window / residual clamps, the T1 mask, stored rows); T stays the row stride
 template <int C, int WC, int WT, int NJ, bool RES, int TG, int ABL = 0, int PRIO = 0, bool SB = false, bool GL = false,
-          bool IP = false, bool HP = false, bool LATE = HP, bool VD = true>
+          bool IP = false, bool HP = false, bool LATE = HP, bool VD = true, bool RAG = false>
 __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {  // >= 2 waves per SIMD
   constexpr int NW = WC * WT;
   constexpr int NT = NW * 64;
@@ -90,10 +93,13 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
   const int n0 = cw0 + NI * 4 * lq;  // epilogue: this lane's 4*NI contiguous output channels
 
   // contiguous tile run of this workgroup (uniform per workgroup: the early exit is safe)
+  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
+  const int ntl = walk.total();
   const int G = gridDim.x;
-  int tile = (int)(((int64_t)blockIdx.x * a.ntiles) / G);
-  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * a.ntiles) / G);
+  int tile = (int)(((int64_t)blockIdx.x * ntl) / G);
+  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
   if (tile >= tile_end) return;
+  MrfTile nx = walk.at(tile);  // RAG: the tile whose window load_win fetches (the first, then each tile's successor)
 
   // ---- weights
   const int NG = HP ? 2 * K : (K + TG - 1) / TG;  // streamed groups per phase (HP: half taps)
@@ -212,17 +218,18 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
   u32x4 xw[MAXW];
   bool xw_ok[MAXW];
   auto load_win = [&](int tl) {
-    const int b = tl / a.tiles_per_b;
-    const int R0 = (tl - b * a.tiles_per_b) * BT - h2 - h1;
+    const MrfTile lt = RAG ? nx : walk.at(tl);
+    const int b = lt.b, Tl = lt.R;
+    const int R0 = lt.t0 - h2 - h1;
     const bf16_t* base = a.x + (int64_t)b * T * C;
 #pragma unroll
     for (int s = 0; s < MAXW; ++s) {
       const int t = R0 + xr0 + s * RSTEP;
-      xw_ok[s] = t >= 0 && t < T && xr0 + s * RSTEP < win_rows;
+      xw_ok[s] = t >= 0 && t < Tl && xr0 + s * RSTEP < win_rows;
       if constexpr ((ABL & 2) != 0)
         xw[s] = u32x4{(unsigned)t, 0u, 0u, 0u};
       else
-        xw[s] = *reinterpret_cast<const u32x4*>(base + (int64_t)min(max(t, 0), T - 1) * C + xg0);
+        xw[s] = *reinterpret_cast<const u32x4*>(base + (int64_t)min(max(t, 0), Tl - 1) * C + xg0);
     }
   };
   auto store_win = [&]() {
@@ -275,9 +282,12 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
   };
 
   for (; tile < tile_end; ++tile) {
-    const int b = tile / a.tiles_per_b;
-    const int t0 = (tile - b * a.tiles_per_b) * BT;
+    const MrfTile ti = RAG ? nx : walk.at(tile);
+    const int b = ti.b;
+    const int t0 = ti.t0;
+    const int Tv = ti.R;  // the utterance's valid rows (dense: T)
     const bool has_next = tile + 1 < tile_end;
+    if constexpr (RAG) nx = walk.at(has_next ? tile + 1 : tile);
 
     // residual / accumulator rows of this tile (epilogue layout), consumed after P2
     u32x4 xres[NJ][NH], ares[NJ][NH];
@@ -285,7 +295,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
       const bf16_t* accp = a.acc ? a.acc : a.x;  // loaded either way (no branch), added only with acc
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, T - 1);  // rows past the tile are not stored
+        const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, Tv - 1);  // rows past the tile are not stored
         const int64_t off = ((int64_t)b * T + pos) * C + n0;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
@@ -325,12 +335,12 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
     };
     auto p1_epilogue = [&]() {
       if constexpr (VD) {  // the bias is in the accumulators
-        const bool interior = t0 - h2 >= 0 && t0 - h2 + R1 <= T;
+        const bool interior = t0 - h2 >= 0 && t0 - h2 + R1 <= Tv;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const int r = wt * 16 * NJ + 16 * j + lr;
           const int pos = t0 - h2 + r;
-          const uint32_t km = (interior || (pos >= 0 && pos < T)) ? 0xffffffffu : 0u;
+          const uint32_t km = (interior || (pos >= 0 && pos < Tv)) ? 0xffffffffu : 0u;
 #pragma unroll
           for (int h = 0; h < NH; ++h) {
             uint32_t w[4];
@@ -352,13 +362,13 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
       float bz[8 * NH];
       lane_bias(0, bz);
       // rows outside [0, T) exist only in the first / last tile of an utterance
-      const bool interior = t0 - h2 >= 0 && t0 - h2 + R1 <= T;
+      const bool interior = t0 - h2 >= 0 && t0 - h2 + R1 <= Tv;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int r = wt * 16 * NJ + 16 * j + lr;
         const int pos = t0 - h2 + r;
         // c2's zero padding: one AND per packed dword (rows outside [0, T) -> +0)
-        const uint32_t km = (interior || (pos >= 0 && pos < T)) ? 0xffffffffu : 0u;
+        const uint32_t km = (interior || (pos >= 0 && pos < Tv)) ? 0xffffffffu : 0u;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
           uint32_t w[4];
@@ -486,7 +496,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
       const bf16_t* accp = a.acc ? a.acc : a.x;  // loaded either way (no branch), added only with acc
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, T - 1);
+        const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, Tv - 1);
         const int64_t off = ((int64_t)b * T + pos) * C + n0;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
@@ -502,7 +512,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
       if (a.acc) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, T - 1);
+          const int pos = min(t0 + wt * 16 * NJ + 16 * j + lr, Tv - 1);
           const int64_t off = ((int64_t)b * T + pos) * C + n0;
 #pragma unroll
           for (int h = 0; h < NH; ++h) ares[j][h] = *reinterpret_cast<const u32x4*>(a.acc + off + 8 * h);
@@ -519,7 +529,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
     // y rows through a buffer resource covering exactly this tile's valid rows: the rows past
     // it (r >= BT, or past T) fall outside the resource and their stores are dropped by the
     // hardware -- no per-lane branch, and a fixed number of stores per wave
-    const int valid = min(BT, T - t0);
+    const int valid = min(BT, Tv - t0);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.y + ((int64_t)b * T + t0) * C), (short)0, valid * C * (int)sizeof(bf16_t), 0x00020000);
     u32x4 yv[NJ][NH];
@@ -571,7 +581,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
 }
 
 template <int C, int WC, int WT, int NJ, bool RES, int TG, int ABL = 0, int PRIO = 0, bool SB = false, bool GL = false,
-          bool IP = false, bool HP = false, bool LATE = HP, bool VD = true>
+          bool IP = false, bool HP = false, bool LATE = HP, bool VD = true, bool RAG = false>
 static int pair_launch(PairArgs a, int B, hipStream_t st) {
   constexpr int NW = WC * WT;
   constexpr int R1 = WT * 16 * NJ;
@@ -587,8 +597,8 @@ static int pair_launch(PairArgs a, int B, hipStream_t st) {
     vo_set_error("resblock_pair: LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  return mrf_launch(mrf_pair_kernel<C, WC, WT, NJ, RES, TG, ABL, PRIO, SB, GL, IP, HP, LATE, VD>, a, a.ntiles, NW * 64,
-                    lds, true, st);
+  return mrf_launch(mrf_pair_kernel<C, WC, WT, NJ, RES, TG, ABL, PRIO, SB, GL, IP, HP, LATE, VD, RAG>, a, a.ntiles,
+                    NW * 64, lds, true, st);
 }
 
 }  // namespace vo
@@ -613,15 +623,17 @@ int vo_pair_check(const MrfPairCall& c, bool frag) {
   return VO_OK;
 }
 
-extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                                void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
-                                float out_scale, void* stream) {
+// vo_resblock_pair (lens == nullptr) and vo_resblock_pair_lens
+static int resblock_pair_entry(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
+                               const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale,
+                               void* stream, const int32_t* lens, int lens_scale) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, st};
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, st, lens, lens_scale};
   if (const int rc = vo_pair_check(c, false)) return rc;
   PairArgs a;
   mrf_pair_args(a, c);
   a.K = K;
+  a.rg = MrfLens{lens, lens_scale, B};
   // Shipped dispatch (measured on MI355X at the B = 32 MRF shapes, tools/ab_pair.py, tools/ab_sb.py, tools/mrf_bench.py):
   //   C = 64 / 128, K = 7 / 11: wave-owned output planes (resblock_rw.hip);
   //   everything else: the LDS-tile kernels of this file, tiled per C and K at the end of this function.
@@ -630,6 +642,17 @@ extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, 
   // (make abl, VO_ABLATIONS); the shipped library does not contain those kernels and runs its defaults.
   const int cfg = vo_tune_get("pair_cfg");
   int handled = 0;
+  if (lens) {
+    // A ragged call takes the shipped dispatch of the shapes the vocoder reaches: C = 64 / 128 on the plane kernel,
+    // C = 32 on the LDS-tile kernel, K = 7 / 11 (K = 3 blocks run as vo_resblock3_lens).  The kernels pair_cfg selects
+    // have no ragged form.
+    VO_CHECK_ARG(cfg == 0, "resblock_pair: pair_cfg=%d selects a kernel without a ragged (lens) form", cfg);
+    VO_CHECK_ARG(K == 7 || K == 11, "resblock_pair: no ragged (lens) kernel for K=%d (7 or 11)", K);
+    const int rc = vo_pair_rw_try(c, cfg, 0, &handled);
+    if (handled) return rc;
+    VO_CHECK_ARG(C == 32, "resblock_pair: no ragged (lens) kernel for C=%d K=%d dil=%d", C, K, dil);
+    return pair_launch<32, 1, 8, 4, true, 1, 0, 0, false, false, true, false, true, false, true>(a, B, st);
+  }
 #ifdef VO_ABLATIONS
   // round 4: register-resident frames (resblock_rr.hip): C = 32 K = 7 / 11 pair_cfg 90-93, 99; C = 64 94-98 and
   // 100 = the 144-row k = 7 frames that shipped before the plane kernel
@@ -747,4 +770,17 @@ extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, 
   // 512-row in-place tiles, window / residual fetched after P2 (-5 % against the 384-row kernel)
   if (K <= 3) return pair_launch<64, 1, 8, 2, true, 1>(a, B, st);
   return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);
+}
+
+extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
+                                void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
+                                float out_scale, void* stream) {
+  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, stream, nullptr, 0);
+}
+
+extern "C" int vo_resblock_pair_lens(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
+                                     void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
+                                     float out_scale, void* stream, const int32_t* lens, int lens_scale) {
+  VO_CHECK_ARG(lens && lens_scale >= 1, "resblock_pair_lens: lens is null or lens_scale %d < 1", lens_scale);
+  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, stream, lens, lens_scale);
 }

@@ -556,9 +556,10 @@ static int rb3_launch(Rb3Args a, int B, hipStream_t st) {
 
 using namespace vo;
 
-extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
-                            const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
-                            float slope, float out_scale, void* stream) {
+// vo_resblock3 (lens == nullptr) and vo_resblock3_lens
+static int resblock3_entry(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
+                           const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
+                           float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && dil && y, "resblock3: null pointer");
   VO_CHECK_ARG(C == 32 || C == 64 || C == 128, "resblock3: C=%d unsupported (32, 64 or 128)", C);
   VO_CHECK_ARG(B > 0 && T > 0, "resblock3: empty");
@@ -580,7 +581,7 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
   a.T = T; a.slope = slope; a.out_scale = out_scale;
   a.tiles_per_b = a.ntiles = 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const MrfBlock3Call c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st};
+  const MrfBlock3Call c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st, lens, lens_scale};
   int handled = 0;
   // Shipped dispatch (measured on MI355X at B = 32 with the MRF accumulator, tools/ab_rb3.py, tools/mrf_bench.py):
   //   C = 64 / 128: wave-owned output planes (resblock_pb3.hip), for every shape accepted above;
@@ -593,6 +594,8 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
   // The LDS-frame kernels against three vo_resblock_pair launches: C = 128 0.84 vs 1.02 ms, C = 64 0.61 vs 0.67,
   // C = 32 0.39 vs 0.52.
   const int cfg = vo_tune_get("rb3_cfg");
+  // a ragged call takes the shipped dispatch: the kernels rb3_cfg selects have no ragged form
+  VO_CHECK_ARG(!lens || cfg == 0, "resblock3: rb3_cfg=%d selects a kernel without a ragged (lens) form", cfg);
 #ifdef VO_ABLATIONS
   const bool plane = cfg == 0;
 #else
@@ -606,6 +609,8 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
     const int rc = vo_rb3_rr_try(c, cfg, &handled);
     if (handled) return rc;
   }
+  VO_CHECK_ARG(!lens, "resblock3: no ragged (lens) kernel for C=%d with dilations (%d, %d, %d)", C, dil[0], dil[1],
+               dil[2]);
 #ifdef VO_ABLATIONS  // measured-and-dropped variants (A/B builds only: make abl)
   if (C == 32 && (cfg == 30 || cfg == 31)) {  // round 3: wave-private frames (resblock5.hip)
     const int rc = vo_rb3_wave_try(c, cfg, &handled);
@@ -651,4 +656,17 @@ extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* c
   }
   // C = 32: 256-row frames, all weights resident: 2 workgroups (4 waves / SIMD) per CU
   return rb3_launch<32, 1, 8, 2, true>(a, B, st);
+}
+
+extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
+                            const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
+                            float slope, float out_scale, void* stream) {
+  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, stream, nullptr, 0);
+}
+
+extern "C" int vo_resblock3_lens(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
+                                 const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
+                                 float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
+  VO_CHECK_ARG(lens && lens_scale >= 1, "resblock3_lens: lens is null or lens_scale %d < 1", lens_scale);
+  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, stream, lens, lens_scale);
 }

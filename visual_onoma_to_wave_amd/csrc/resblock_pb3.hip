@@ -43,6 +43,7 @@ struct Pb3Args {
   int T, dil[3], tiles_per_b, ntiles;
   float slope, out_scale;
   unsigned long long* stamps;  // diagnostic builds only (-DVO_PB3_STAMPS, tools/probes/pb3_stamps.py)
+  MrfLens rg;  // RAG instantiations: per-utterance lengths (mrf_common.h)
 };
 constexpr int PB_NSTW = 16, PB_NSTT = 4, PB_NPT = 30;  // stamp geometry: workgroups, tiles, stamps per tile
 
@@ -66,7 +67,9 @@ constexpr size_t pb_lds(int C) { return (size_t)2 * pb_np(C) * pb_rp(C) * 32 * s
 
 __device__ __forceinline__ int pb_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
-template <int C, int ACC, bool ST = false>
+// RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
+// T does in the dense form (buffer ranges, zeroed frame rows, stored rows); T stays the row stride between utterances
+template <int C, int ACC, bool ST = false, bool RAG = false>
 __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   constexpr int NP = pb_np(C), F = pb_f(C), NJ = pb_nj(C), RP = pb_rp(C), PL = RP * 32;
   constexpr int BT = F - 2 * PB_HALO;
@@ -102,10 +105,13 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     }
   };
 
+  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
+  const int ntl = RAG ? walk.total() : a.ntiles;
   const int G = gridDim.x;
-  int tile = (int)(((int64_t)blockIdx.x * a.ntiles) / G);
-  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * a.ntiles) / G);
+  int tile = (int)(((int64_t)blockIdx.x * ntl) / G);
+  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
   if (tile >= tile_end) return;  // uniform per workgroup
+  MrfTile nx = RAG ? walk.at(tile) : MrfTile{0, 0, T};  // RAG: the tile whose window load_win fetches (the first, then each tile's successor)
 
   for (int i = tid; i < 6 * C; i += 256) sbias[i] = a.b[i / C][i % C];
   // pad rows (read only by taps of frame rows whose outputs the halo discards): zeros, never NaN
@@ -130,8 +136,8 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     const int lo = aoff + t * 4 * C * 2 + s * 64;
     A[uu % 3][s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw[v], lo, k * (C * C * 2), 0));
   };
-  auto utt = [&](const bf16_t* p, int b) __attribute__((always_inline)) {  // one utterance of a (B, T, C) tensor: rows outside read 0
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, T * C * 2, 0x00020000);
+  auto utt = [&](const bf16_t* p, int b, int Tv) __attribute__((always_inline)) {  // rows [0, Tv) of one utterance of a (B, T, C) tensor: rows outside read 0
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
   };
   // op i of n spread over the steps [lo, lo + span) of a phase: does step jj carry it?
   auto at = [](int jj, int lo, int span, int n, int i) __attribute__((always_inline)) { return jj == lo + i * span / n; };
@@ -141,10 +147,10 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   const int xl = (xc >> 2) * PL + pb_off(xr + PB_HP, xc & 3);  // + slot * RPS rows (swizzle unchanged)
   u32x4 xw[NWV];
   auto load_win = [&](int tl, int sl) __attribute__((always_inline)) {
-    const int b = tl / a.tiles_per_b;
-    const int p0 = (tl - b * a.tiles_per_b) * BT - PB_HALO;
+    const int b = RAG ? nx.b : tl / a.tiles_per_b;
+    const int p0 = (RAG ? nx.t0 : (tl - b * a.tiles_per_b) * BT) - PB_HALO;
     // positions before 0 wrap to huge offsets and past T exceed the range: both read 0 (zero padding)
-    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b), ((p0 + xr + RPS * sl) * C + xc * 8) * 2, 0, 0);
+    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b, RAG ? nx.R : T), ((p0 + xr + RPS * sl) * C + xc * 8) * 2, 0, 0);
   };
   auto store_win = [&](int sl) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(win + xl + sl * RPS * 32) = lrelu8(xw[sl], slope); };
 
@@ -240,16 +246,18 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
 
   const int cofs = 32 * pw + 8 * lg;
   for (; tile < tile_end; ++tile) {
-    const int b = tile / a.tiles_per_b;
-    const int t0 = (tile - b * a.tiles_per_b) * BT;
+    const int b = RAG ? nx.b : tile / a.tiles_per_b;
+    const int t0 = RAG ? nx.t0 : (tile - b * a.tiles_per_b) * BT;
+    const int Tv = RAG ? nx.R : T;  // the utterance's valid rows
     const int p0 = t0 - PB_HALO;  // position of frame row 0
     const int ntile = tile + 1 < tile_end ? tile + 1 : tile;
+    if constexpr (RAG) nx = walk.at(ntile);
     // Zero padding: the epilogues write every frame row unmasked (a mask per row tile cost 5 of its ~38 vector
     // instructions, in the VALU-bound epilogue phase; a branch around it made hipcc copy eight accumulators out
     // of the AGPRs at every join); in the tiles whose frame crosses an utterance end, the rows outside [0, T) of
     // the wave's own plane are zeroed after the epilogue, before the barrier that publishes them
-    const bool edge = p0 < 0 || p0 + F > T;
-    const int zlo = p0 < 0 ? -p0 : 0, zhi = T - p0;  // frame rows [zlo, zhi) are inside the utterance
+    const bool edge = p0 < 0 || p0 + F > Tv;
+    const int zlo = p0 < 0 ? -p0 : 0, zhi = Tv - p0;  // frame rows [zlo, zhi) are inside the utterance
     auto zero_rows = [&](bf16_t* buf) __attribute__((always_inline)) {
       if (!edge) return;
       for (int f = row0 + lane; f < row0 + 16 * NJ; f += 64)
@@ -257,8 +265,8 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x4*>(buf + pw * PL + pb_off(f + PB_HP, q)) = u32x4{0u, 0u, 0u, 0u};
     };
-    const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b);
-    const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b);
+    const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b, Tv);
+    const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b, Tv);
 
     stamp(0);
     lds_barrier();  // window staged; the previous tile's T1 reads are done
@@ -349,7 +357,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     // ---- stage 2, c2: y = (x2 + c2) * out_scale (+ acc) -> HBM.  Phase 0, after its A pieces: the next window
     // written lrelu'd, and the MRF accumulator rows requested (x2's registers are free after the residual
     // MFMAs of plane 0); they enter in phase 1 (identity MFMA, ACC == 2) or the epilogue (ACC == 1)
-    const int valid = min(BT, T - t0);
+    const int valid = min(BT, Tv - t0);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.y + ((int64_t)b * T + t0) * C), (short)0, valid * C * (int)sizeof(bf16_t), 0x00020000);
     auto s2b_hook = [&](int ph, int jj) __attribute__((always_inline)) {
@@ -397,12 +405,12 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   }
 }
 
-template <int C, int ACC>
+template <int C, int ACC, bool RAG = false>
 static int pb3_launch(Pb3Args a, int B, hipStream_t st) {
   constexpr int BT = pb_f(C) - 2 * PB_HALO;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
-  return mrf_launch(mrf_pb3_kernel<C, ACC>, a, a.ntiles, 256, pb_lds(C), false, st);
+  return mrf_launch(mrf_pb3_kernel<C, ACC, false, RAG>, a, a.ntiles, 256, pb_lds(C), false, st);
 }
 
 }  // namespace vo
@@ -431,12 +439,18 @@ int vo_rb3_pb_try(const MrfBlock3Call& c, int* handled) {
   a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
   a.tiles_per_b = a.ntiles = 0;
   a.stamps = nullptr;
+  a.rg = MrfLens{c.lens, c.lens_scale, c.B};
   *handled = 1;
   const int accm = mrf_acc_mode(c.acc, c.out_scale);
-#define VO_PB3_DISPATCH(CC) \
-  return accm == 2 ? pb3_launch<CC, 2>(a, c.B, c.st) : accm == 1 ? pb3_launch<CC, 1>(a, c.B, c.st) : pb3_launch<CC, 0>(a, c.B, c.st)
-  if (c.C == 64) VO_PB3_DISPATCH(64);
-  VO_PB3_DISPATCH(128);
+#define VO_PB3_DISPATCH(CC, RG)                                                                                   \
+  return accm == 2 ? pb3_launch<CC, 2, RG>(a, c.B, c.st) : accm == 1 ? pb3_launch<CC, 1, RG>(a, c.B, c.st) \
+                                                                     : pb3_launch<CC, 0, RG>(a, c.B, c.st)
+  if (c.lens) {
+    if (c.C == 64) VO_PB3_DISPATCH(64, true);
+    VO_PB3_DISPATCH(128, true);
+  }
+  if (c.C == 64) VO_PB3_DISPATCH(64, false);
+  VO_PB3_DISPATCH(128, false);
 #undef VO_PB3_DISPATCH
 }
 

@@ -48,6 +48,7 @@ struct RrArgs {
   const bf16_t* acc;
   int T, tiles_per_b, ntiles;
   float slope, out_scale;
+  MrfLens rg;  // RAG instantiations: per-utterance lengths (mrf_common.h)
 };
 
 constexpr int RR_HALO = 12;  // rows lost per side over the six convs (dilations 1, 3, 5)
@@ -93,7 +94,9 @@ __device__ __forceinline__ u32x4 shifted(const u32x4 (&in)[NB][NS], int s) {
 
 // NWV waves per workgroup (NWV / 4 per SIMD); PF: the next frame requested at the start of a tile
 // (registers permitting; otherwise the partner wave covers the latency)
-template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false>
+// RAG: ragged batch -- the wave walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where T
+// does in the dense form (buffer ranges, edge masks, stored rows); T stays the row stride between utterances
+template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false, bool RAG = false>
 __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
   constexpr int NS = C / 32;   // K-steps (32-channel planes)
   constexpr int NCB = C / 16;  // 16-channel output blocks
@@ -126,20 +129,25 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
   for (int i = tid; i < 6 * C; i += NT) sb[i] = a.bias[i / C][i % C];
   __syncthreads();
 
+  static_assert(!RAG || !(PF || PL), "ragged: the frame is loaded in its own tile");
+  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, OR, a.rg);
+  const int ntl = walk.total();
   const int gw = blockIdx.x * NWV + wave, nw = gridDim.x * NWV;
-  int tile = (int)(((int64_t)gw * a.ntiles) / nw);
-  const int tile_end = (int)(((int64_t)(gw + 1) * a.ntiles) / nw);
+  int tile = (int)(((int64_t)gw * ntl) / nw);
+  const int tile_end = (int)(((int64_t)(gw + 1) * ntl) / nw);
   if (tile >= tile_end) return;  // per wave: no barrier follows
+  MrfTile ti{0, 0, T};  // the tile in hand (RAG: decoded once per tile, at the top of the loop)
 
   const int lane_off = 2 * (lr * NB * C + 8 * lq);  // bytes: frame row lr * NB, channels 8 lq.. of plane 0
-  auto utt_rsrc = [&](const bf16_t* base, int b) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (int64_t)b * T * C), (short)0, T * C * 2, 0x00020000);
+  auto utt_rsrc = [&](const bf16_t* base, int b, int Tv) {  // rows [0, Tv) of utterance b
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
   };
   // frame of tile tl: rows w0 .. w0 + F - 1 of utterance b (rows outside it read as 0)
   auto load_rows = [&](const bf16_t* base, int tl, u32x4 (&fr)[NB][NS]) {
-    const int b = tl / a.tiles_per_b;
-    const int w0 = (tl - b * a.tiles_per_b) * OR - RR_HALO;
-    const __amdgpu_buffer_rsrc_t rs = utt_rsrc(base, b);
+    const MrfTile lt = RAG ? ti : walk.at(tl);
+    const int b = lt.b;
+    const int w0 = lt.t0 - RR_HALO;
+    const __amdgpu_buffer_rsrc_t rs = utt_rsrc(base, b, lt.R);
 #pragma unroll
     for (int n = 0; n < NB; ++n)
 #pragma unroll
@@ -156,10 +164,12 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
   for (int cb = 0; cb < NCB; ++cb) af[0][cb] = wfr[(NS * NCB + cb) * 64 + lane];  // (conv 0, tap 1, K-step 0)
 
   for (; tile < tile_end; ++tile) {
-    const int b = tile / a.tiles_per_b;
-    const int t0 = (tile - b * a.tiles_per_b) * OR;  // first output row
+    ti = walk.at(tile);
+    const int b = ti.b;
+    const int t0 = ti.t0;  // first output row
+    const int Tv = ti.R;   // the utterance's valid rows (dense: T)
     const int w0 = t0 - RR_HALO;
-    const bool interior = w0 >= 0 && w0 + F <= T;
+    const bool interior = w0 >= 0 && w0 + F <= Tv;
     u32x4 xb[NB][NS], in[NB][NS];
     if constexpr (PF || PL) {
 #pragma unroll
@@ -230,7 +240,7 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
           uint32_t km = 0xffffffffu;
           if constexpr (EDGE) {
             const int pos = w0 + lr * NB + n;
-            km = (pos >= 0 && pos < T) ? 0xffffffffu : 0u;
+            km = (pos >= 0 && pos < Tv) ? 0xffffffffu : 0u;
           }
 #pragma unroll
           for (int s = 0; s < NS; ++s) {
@@ -282,7 +292,7 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3_kernel(RrArgs a) {
     // y = (x2 + c2 + b2) * out_scale (+ acc) on rows t0 .. t0 + valid - 1 = frame rows HALO ..: a
     // resource over exactly those rows drops the halo rows' stores (rows before it: an offset past
     // any resource)
-    const int valid = min(OR, T - t0);
+    const int valid = min(OR, Tv - t0);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.y + ((int64_t)b * T + t0) * C), (short)0, valid * C * 2, 0x00020000);
     auto fin = [&](auto with_acc) {
@@ -651,7 +661,7 @@ static int rr3w_launch(RrArgs a, int B, hipStream_t st) {
 }
 #endif  // VO_ABLATIONS
 
-template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false>
+template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false, bool RAG = false>
 static int rr3_launch(RrArgs a, int B, hipStream_t st) {
   constexpr int OR = 16 * NB - 2 * RR_HALO;
   constexpr size_t lds = (size_t)6 * 3 * (C / 32) * (C / 16) * 1024 + 6 * C * sizeof(float);
@@ -659,7 +669,7 @@ static int rr3_launch(RrArgs a, int B, hipStream_t st) {
   a.tiles_per_b = (a.T + OR - 1) / OR;
   a.ntiles = a.tiles_per_b * B;
   // one workgroup per CU, a tile per wave
-  return mrf_launch(mrf_rr3_kernel<C, NB, NWV, PF, PA, PL>, a, (a.ntiles + NWV - 1) / NWV, NWV * 64, lds, false, st);
+  return mrf_launch(mrf_rr3_kernel<C, NB, NWV, PF, PA, PL, RAG>, a, (a.ntiles + NWV - 1) / NWV, NWV * 64, lds, false, st);
 }
 
 #ifdef VO_ABLATIONS  // measured and dropped (pair_cfg 90-100): in the A/B library only
@@ -947,6 +957,13 @@ int vo_rb3_rr_try(const MrfBlock3Call& c, int cfg, int* handled) {
   }
   a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
   a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
+  a.rg = MrfLens{c.lens, c.lens_scale, B};
+  if (c.lens) {  // ragged: the shipped kernel only
+    VO_CHECK_ARG(cfg == 0, "resblock3: rb3_cfg=%d selects a kernel without a ragged (lens) form", cfg);
+    if (C != 32) return VO_OK;
+    *handled = 1;
+    return rr3_launch<32, 8, 8, false, false, false, true>(a, B, st);
+  }
 #ifdef VO_ABLATIONS  // the other frame shapes / MFMA forms, measured
   *handled = 1;
   if (C == 32) {

@@ -39,6 +39,7 @@ struct PrwArgs {
   int T, dil, tiles_per_b, ntiles;
   float slope, out_scale;
   unsigned long long* stamps;  // diagnostic builds only (-DVO_PRW_STAMPS, tools/probes/prw_stamps.py)
+  MrfLens rg;  // RAG instantiations: per-utterance lengths (mrf_common.h)
 };
 
 // Geometry by channel count C (32, 64 or 128): NP = C / 32 planes; the 4 waves are NP output planes x RG = 4 / NP
@@ -54,7 +55,9 @@ constexpr int RW_NSTW = 16, RW_NSTT = 4, RW_NPT = 2 * 11 + 6;  // stamp geometry
 
 __device__ __forceinline__ int rw_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
-template <int C, int K, int ACC, bool FR = false, bool ST = false>
+// RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
+// T does in the dense form (buffer ranges, the T1 mask, stored rows); T stays the row stride between utterances
+template <int C, int K, int ACC, bool FR = false, bool ST = false, bool RAG = false>
 __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
   constexpr int NP = rw_np(C), R1 = rw_r1(C), NJ = 16;  // planes, c1 rows per tile, row tiles per wave
   constexpr int WP = rw_wp(C), TP = rw_tp(C);
@@ -119,10 +122,13 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
   };
 
   // contiguous tile run of this workgroup (uniform per workgroup: the early exit is safe)
+  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
+  const int ntl = RAG ? walk.total() : a.ntiles;
   const int G = gridDim.x;
-  int tile = (int)(((int64_t)blockIdx.x * a.ntiles) / G);
-  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * a.ntiles) / G);
+  int tile = (int)(((int64_t)blockIdx.x * ntl) / G);
+  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
   if (tile >= tile_end) return;
+  MrfTile nx = RAG ? walk.at(tile) : MrfTile{0, 0, T};  // RAG: the tile whose window load_win1 fetches (the first, then each tile's successor)
 
   for (int i = tid; i < 2 * C; i += 256) sbias[i] = i < C ? a.b1[i] : a.b2[i - C];
 
@@ -147,8 +153,8 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     A[uu & 1][s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(uu < K ? rw1 : rw2,
                                              lo, tap_off, 0));
   };
-  auto utt = [&](const bf16_t* p, int b) {  // one utterance of a (B, T, C) tensor
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, T * C * 2, 0x00020000);
+  auto utt = [&](const bf16_t* p, int b, int Tv) {  // rows [0, Tv) of one utterance of a (B, T, C) tensor
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
   };
 
   // ---- window staging: vector v = tid + 256 * slot = (row xr + RPS slot, 16-byte column xc)
@@ -160,11 +166,11 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
   // 17 % of the window's HBM reads)
   const int wneed = R1 + (K - 1) * a.dil;
   auto load_win1 = [&](int tl, int sl) {
-    const int b = tl / a.tiles_per_b;
-    const int R0 = (tl - b * a.tiles_per_b) * BT - H2 - h1;
+    const int b = RAG ? nx.b : tl / a.tiles_per_b;
+    const int R0 = (RAG ? nx.t0 : (tl - b * a.tiles_per_b) * BT) - H2 - h1;
     // rows before 0 / past T are out of the utterance's range and read 0 (the conv's zero padding)
     const int off = xr + RPS * sl < wneed ? ((R0 + xr + RPS * sl) * C + xc * 8) * 2 : 0x7ffffff0;
-    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b), off, 0, 0);
+    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b, RAG ? nx.R : T), off, 0, 0);
   };
   auto store_win1 = [&](int sl) { *reinterpret_cast<u32x4*>(win + xl + sl * RPS * 32) = lrelu8(xw[sl], slope); };
 
@@ -255,9 +261,11 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
   };
 
   for (; tile < tile_end; ++tile) {
-    const int b = tile / a.tiles_per_b;
-    const int t0 = (tile - b * a.tiles_per_b) * BT;
+    const int b = RAG ? nx.b : tile / a.tiles_per_b;
+    const int t0 = RAG ? nx.t0 : (tile - b * a.tiles_per_b) * BT;
+    const int Tv = RAG ? nx.R : T;  // the utterance's valid rows
     const int ntile = tile + 1 < tile_end ? tile + 1 : tile;  // next window (unconditional loads)
+    if constexpr (RAG) nx = walk.at(ntile);
 
     stamp(0);
     lds_barrier();  // window staged; the previous P2's T1 reads are done
@@ -266,11 +274,11 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     // ---- P1: T1 = lrelu(c1(window) + b1), rows outside [0, T) = 0 (c2's zero padding).  During its last
     // two taps this tile's residual rows x are requested in the accumulator layout: they enter P2 as the
     // C operand of its first MFMAs (acc = b2 + x + c2), a whole tap and the B1 barrier after the request
-    const bool interior = t0 - H2 >= 0 && t0 - H2 + R1 <= T;
+    const bool interior = t0 - H2 >= 0 && t0 - H2 + R1 <= Tv;
     const int cofs = 32 * pw + 8 * lg;
-    const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b);
+    const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b, Tv);
     u32x4 xres[NJ], ares[NJ];
-    const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b);
+    const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b, Tv);
     // requested after each tap's A pieces (steps 16, 22, .., 58 of taps K-2 and K-1): vmcnt retires in
     // issue order, so a residual load issued before an A piece would hold up the MFMAs that wait for it
     // (spread over the last K-2 taps, a few row tiles each, they measured slower: 2.5 % per tile)
@@ -301,7 +309,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
         const int r = row0 + 16 * j + lr;
         const int pos = t0 - H2 + r;
         u32x4 v = u32x4{pv[0], pv[1], pv[2], pv[3]};
-        if (!interior) v &= (pos >= 0 && pos < T) ? 0xffffffffu : 0u;
+        if (!interior) v &= (pos >= 0 && pos < Tv) ? 0xffffffffu : 0u;
         *reinterpret_cast<u32x4*>(t1 + pw * TP * 32 + rw_off(r, lg)) = v;
       }
     };
@@ -312,7 +320,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
 
     // ---- P2: y = (b2 + x + c2(T1)) * out_scale (+ acc); the next window is staged meanwhile:
     // SPT slots loaded per tap in taps 0 .. K-3 and written (lrelu'd) two taps later
-    const int valid = min(BT, T - t0);
+    const int valid = min(BT, Tv - t0);
     const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.y + ((int64_t)b * T + t0) * C), (short)0, valid * C * (int)sizeof(bf16_t), 0x00020000);
     auto p2_hook = [&](int k, int jj) {
@@ -385,6 +393,7 @@ static int prw_launch(PrwArgs a, int B, hipStream_t st) {
   constexpr int BT = rw_r1(C) - 2 * ((K - 1) / 2);
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
+  if (a.rg.lens) return mrf_launch(mrf_prw_kernel<C, K, ACC, FR, false, true>, a, a.ntiles, 256, rw_lds(C), false, st);
   return mrf_launch(mrf_prw_kernel<C, K, ACC, FR>, a, a.ntiles, 256, rw_lds(C), false, st);
 }
 
@@ -410,6 +419,7 @@ int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
   PrwArgs a;
   mrf_pair_args(a, c);
   a.stamps = nullptr;
+  a.rg = MrfLens{c.lens, c.lens_scale, B};
   *handled = 1;
   const int accm = mrf_acc_mode(c.acc, c.out_scale);
 #define VO_PRW_DISPATCH(CC, KK, FF) \
@@ -459,6 +469,18 @@ extern "C" int vo_resblock_pair_frag(const void* x, const void* w1, const float*
                                      void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
                                      float out_scale, void* stream) {
   const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, reinterpret_cast<hipStream_t>(stream)};
+  if (const int rc = vo_pair_check(c, true)) return rc;
+  int handled = 0;
+  return vo_pair_rw_try(c, 0, 1, &handled);
+}
+
+extern "C" int vo_resblock_pair_frag_lens(const void* x, const void* w1, const float* b1, const void* w2,
+                                          const float* b2, void* y, const void* acc, int B, int T, int C, int K, int dil,
+                                          float slope, float out_scale, void* stream, const int32_t* lens,
+                                          int lens_scale) {
+  VO_CHECK_ARG(lens && lens_scale >= 1, "resblock_pair_frag_lens: lens is null or lens_scale %d < 1", lens_scale);
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, reinterpret_cast<hipStream_t>(stream),
+                      lens, lens_scale};
   if (const int rc = vo_pair_check(c, true)) return rc;
   int handled = 0;
   return vo_pair_rw_try(c, 0, 1, &handled);

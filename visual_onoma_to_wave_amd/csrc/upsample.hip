@@ -37,6 +37,7 @@ struct UpsArgs {
   int T_in, up_tout, up_stride, up_pad, cout;
   int nblk, units;
   float slope;         // pre-lrelu slope (1 = none)
+  MrfLens rg;          // RAG instantiations: per-utterance input lengths (mrf_common.h)
 };
 
 // DPP row rotate by one lane (row_ror:1): lane lr of each 16-lane row receives lane
@@ -55,7 +56,9 @@ __device__ __forceinline__ u32x4 ror1(u32x4 v) {
 // for the first unit of a run).  The loop body is a compiler barrier away from the weight
 // reads, so the loop-invariant LDS fragments are re-read per unit instead of being hoisted
 // into registers (256 VGPRs and one wave per SIMD for CI = 128).
-template <int CI, int NC, int NJ>
+// RAG: ragged batch -- utterance b has R_b input steps: its units are those of the R_b + 1 phase rows (MrfWalk's
+// compacted list, EX = 1), R_b stands where T_in does and its output rows end at (R_b + 1) up_stride - 2 up_pad.
+template <int CI, int NC, int NJ, bool RAG = false>
 __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
   constexpr int NI = NC / 16;        // 16-column i-tiles
   constexpr int KS = CI / 32;        // 32-deep k-steps per tap
@@ -93,24 +96,28 @@ __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
   const int col = n0 - phase * a.cout;
   __syncthreads();
 
-  const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6);
+  MrfWalk<RAG, 1> walk(a.nblk, a.units, a.T_in, MB, a.rg);
+  const int units = walk.total();
+  const int wave_id = blockIdx.x * 4 + (RAG ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6);
   const int nwaves = gridDim.x * 4;
-  const int per = (a.units + nwaves - 1) / nwaves;
+  const int per = (units + nwaves - 1) / nwaves;
   const int u_begin = wave_id * per;
-  const int u_end = min(u_begin + per, a.units);
+  const int u_end = min(u_begin + per, units);
   if (u_begin >= u_end) return;
+  MrfTile cu{0, 0, a.T_in}, nx = walk.at(u_begin);  // RAG: the unit in hand and the one load_unit fetches
 
-  auto unit_pos = [&](int u, int& b, int& m0) {
-    b = u / a.nblk;
-    m0 = (u - b * a.nblk) * MB;
+  // (b, first step, valid input steps) of unit u; RAG: of the unit in hand (next = false) or the one being fetched
+  auto unit_pos = [&](int u, int& b, int& m0, int& Tv, bool next) {
+    const MrfTile t = RAG ? (next ? nx : cu) : walk.at(u);
+    b = t.b; m0 = t.t0; Tv = t.R;
   };
   auto load_unit = [&](int u, u32x4 (&dst)[NJ][KS]) {
-    int b, m0;
-    unit_pos(min(u, u_end - 1), b, m0);  // past the run: re-read its last unit (unused)
+    int b, m0, Tl;
+    unit_pos(min(u, u_end - 1), b, m0, Tl, true);  // past the run: re-read its last unit (unused)
     const bf16_t* X = a.x + (int64_t)b * a.xbs;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int rc = min(m0 + 16 * j + lr, a.T_in - 1);
+      const int rc = min(m0 + 16 * j + lr, Tl - 1);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
         dst[j][ks] = *reinterpret_cast<const u32x4*>(X + (int64_t)rc * CI + 32 * ks + 8 * lq);
@@ -119,8 +126,8 @@ __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
 
   u32x4 xf[NJ][KS], xn[NJ][KS], prev[KS];
   {  // halo of the run's first unit: row m0 - 1 (lane 15 is what the rotate hands to lane 0)
-    int b, m0;
-    unit_pos(u_begin, b, m0);
+    int b, m0, Tl;
+    unit_pos(u_begin, b, m0, Tl, true);
     const bf16_t* X = a.x + (int64_t)b * a.xbs + (int64_t)max(m0 - 1, 0) * CI;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -131,9 +138,14 @@ __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
   load_unit(u_begin, xf);
   for (int u = u_begin; u < u_end; ++u) {
     asm volatile("" ::: "memory");
+    if constexpr (RAG) {
+      cu = nx;
+      nx = walk.at(min(u + 1, u_end - 1));
+    }
     load_unit(u + 1, xn);
-    int b, m0;
-    unit_pos(u, b, m0);
+    int b, m0, Tv;
+    unit_pos(u, b, m0, Tv, false);
+    const int tout = RAG ? min(a.up_tout, (Tv + 1) * a.up_stride - 2 * a.up_pad) : a.up_tout;
     if (m0 == 0) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) prev[ks] = u32x4{0u, 0u, 0u, 0u};
@@ -142,7 +154,7 @@ __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
     // pre-activation; rows at or past T_in are the conv's zero padding
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const bool ok = m0 + 16 * j + lr < a.T_in;
+      const bool ok = m0 + 16 * j + lr < Tv;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const u32x4 v = lrelu8(xf[j][ks], a.slope);
@@ -183,7 +195,7 @@ __global__ void __launch_bounds__(256) ups_kernel(UpsArgs a) {
     for (int j = 0; j < NJ; ++j) {
       const int m = m0 + 16 * j + lr;
       const int trow = m * a.up_stride + phase - a.up_pad;
-      if (m > a.T_in || trow < 0 || trow >= a.up_tout) continue;
+      if (m > Tv || trow < 0 || trow >= tout) continue;
       bf16_t* dst = Y + (int64_t)trow * a.cout + col;
 #pragma unroll
       for (int h = 0; h < NI / 2; ++h) {
@@ -218,7 +230,7 @@ struct UpswArgs {
   int rgroups;  // run groups (grid = ncb_n * rgroups)
 };
 
-template <int CI, int NCB, int NJ, int NW>
+template <int CI, int NCB, int NJ, int NW, bool RAG = false>
 __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
   const UpsArgs& a = w.u;
   constexpr int NI = NCB / 16;
@@ -261,24 +273,28 @@ __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
   __syncthreads();
 
   // this wave's contiguous run of units
+  MrfWalk<RAG, 1> walk(a.nblk, a.units, a.T_in, MB, a.rg);
+  const int units = walk.total();
   const int workers = w.rgroups * NW;
-  const int wid = rgrp * NW + (threadIdx.x >> 6);
-  const int per = (a.units + workers - 1) / workers;
+  const int wid = rgrp * NW + (RAG ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6);
+  const int per = (units + workers - 1) / workers;
   const int u_begin = wid * per;
-  const int u_end = min(u_begin + per, a.units);
+  const int u_end = min(u_begin + per, units);
   if (u_begin >= u_end) return;
+  MrfTile cu{0, 0, a.T_in}, nx = walk.at(u_begin);  // RAG: the unit in hand and the one load_unit fetches
 
-  auto unit_pos = [&](int u, int& b, int& m0) {
-    b = u / a.nblk;
-    m0 = (u - b * a.nblk) * MB;
+  // (b, first step, valid input steps) of unit u; RAG: of the unit in hand (next = false) or the one being fetched
+  auto unit_pos = [&](int u, int& b, int& m0, int& Tv, bool next) {
+    const MrfTile t = RAG ? (next ? nx : cu) : walk.at(u);
+    b = t.b; m0 = t.t0; Tv = t.R;
   };
   auto load_unit = [&](int u, u32x4 (&dst)[NJ][KS]) {
-    int b, m0;
-    unit_pos(min(u, u_end - 1), b, m0);
+    int b, m0, Tl;
+    unit_pos(min(u, u_end - 1), b, m0, Tl, true);
     const bf16_t* X = a.x + (int64_t)b * a.xbs;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int rc = min(m0 + 16 * j + lr, a.T_in - 1);
+      const int rc = min(m0 + 16 * j + lr, Tl - 1);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
         dst[j][ks] = *reinterpret_cast<const u32x4*>(X + (int64_t)rc * CI + 32 * ks + 8 * lq);
@@ -287,8 +303,8 @@ __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
 
   u32x4 xf[NJ][KS], xn[NJ][KS], prev[KS];
   {
-    int b, m0;
-    unit_pos(u_begin, b, m0);
+    int b, m0, Tl;
+    unit_pos(u_begin, b, m0, Tl, true);
     const bf16_t* X = a.x + (int64_t)b * a.xbs + (int64_t)max(m0 - 1, 0) * CI;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -299,16 +315,21 @@ __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
   load_unit(u_begin, xf);
   for (int u = u_begin; u < u_end; ++u) {
     asm volatile("" ::: "memory");
+    if constexpr (RAG) {
+      cu = nx;
+      nx = walk.at(min(u + 1, u_end - 1));
+    }
     load_unit(u + 1, xn);
-    int b, m0;
-    unit_pos(u, b, m0);
+    int b, m0, Tv;
+    unit_pos(u, b, m0, Tv, false);
+    const int tout = RAG ? min(a.up_tout, (Tv + 1) * a.up_stride - 2 * a.up_pad) : a.up_tout;
     if (m0 == 0) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) prev[ks] = u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const bool ok = m0 + 16 * j + lr < a.T_in;
+      const bool ok = m0 + 16 * j + lr < Tv;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const u32x4 v = lrelu8(xf[j][ks], a.slope);
@@ -347,7 +368,7 @@ __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
     for (int j = 0; j < NJ; ++j) {
       const int m = m0 + 16 * j + lr;
       const int trow = m * a.up_stride + phase - a.up_pad;
-      if (m > a.T_in || trow < 0 || trow >= a.up_tout) continue;
+      if (m > Tv || trow < 0 || trow >= tout) continue;
       bf16_t* dst = Y + (int64_t)trow * a.cout + col;
 #pragma unroll
       for (int h = 0; h < NI / 2; ++h) {
@@ -368,7 +389,7 @@ __global__ void __launch_bounds__(NW * 64) upsw_kernel(UpswArgs w) {
   }
 }
 
-template <int CI, int NCB, int NJ, int NW = 8>
+template <int CI, int NCB, int NJ, int NW = 8, bool RAG = false>
 static int launch_upsw(const vo_conv1d_desc* d, hipStream_t st) {
   UpswArgs w;
   UpsArgs& a = w.u;
@@ -382,12 +403,13 @@ static int launch_upsw(const vo_conv1d_desc* d, hipStream_t st) {
   a.nblk = (d->T_in + 1 + 16 * NJ - 1) / (16 * NJ);
   a.units = a.nblk * d->B;
   a.slope = d->pre_act == VO_ACT_LRELU ? d->pre_slope : (d->pre_act == VO_ACT_RELU ? 0.f : 1.f);
+  a.rg = MrfLens{d->lens, d->lens_scale, d->B};
   w.nc = d->Co;
   w.ncb_n = d->Co / NCB;
   // resident workgroups only (persistent); run groups in multiples of 8 (one per XCD slot)
   const size_t lds_b = 2 * (size_t)NCB * CI * sizeof(bf16_t) + NCB * sizeof(float);
   int per_cu = 0;  // LDS- and register-limited resident workgroups per CU
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, upsw_kernel<CI, NCB, NJ, NW>, NW * 64, lds_b) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, upsw_kernel<CI, NCB, NJ, NW, RAG>, NW * 64, lds_b) != hipSuccess ||
       per_cu < 1)
     per_cu = 1;
   const int slots = std::max(1, cu_count() * per_cu / 8);         // workgroup slots per XCD
@@ -396,11 +418,11 @@ static int launch_upsw(const vo_conv1d_desc* d, hipStream_t st) {
   w.rgroups = std::min(8 * rg_per_xcd, std::max(1, need));
   const int grid = 8 * w.ncb_n * ((w.rgroups + 7) / 8);
   const size_t lds = 2 * (size_t)NCB * CI * sizeof(bf16_t) + NCB * sizeof(float);
-  hipLaunchKernelGGL((upsw_kernel<CI, NCB, NJ, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, st, w);
+  hipLaunchKernelGGL((upsw_kernel<CI, NCB, NJ, NW, RAG>), dim3((unsigned)grid), dim3(NW * 64), lds, st, w);
   VO_RETURN_LAUNCH();
 }
 
-template <int CI, int NC, int NJ>
+template <int CI, int NC, int NJ, bool RAG = false>
 static int launch_ups(const vo_conv1d_desc* d, hipStream_t st) {
   UpsArgs a;
   a.x = reinterpret_cast<const bf16_t*>(d->x);
@@ -413,7 +435,8 @@ static int launch_ups(const vo_conv1d_desc* d, hipStream_t st) {
   a.nblk = (d->T_in + 1 + 16 * NJ - 1) / (16 * NJ);
   a.units = a.nblk * d->B;
   a.slope = d->pre_act == VO_ACT_LRELU ? d->pre_slope : (d->pre_act == VO_ACT_RELU ? 0.f : 1.f);
-  auto kern = ups_kernel<CI, NC, NJ>;
+  a.rg = MrfLens{d->lens, d->lens_scale, d->B};
+  auto kern = ups_kernel<CI, NC, NJ, RAG>;
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
   const int grid = (int)std::min<int64_t>((int64_t)cu_count() * per_cu, (a.units + 3) / 4);  // a wave per run
@@ -429,6 +452,7 @@ static int launch_ups(const vo_conv1d_desc* d, hipStream_t st) {
 int vo_ups_try(const vo_conv1d_desc* d, hipStream_t st, int* handled) {
   using namespace vo;
   *handled = 0;
+  const bool rag = d->lens != nullptr;  // ragged: the shipped dispatch (vo_conv1d rejects ups_cfg != 0)
   if (vo_tune_get("ups_cfg") == 1) return VO_OK;
   if (!d->transposed || d->compute_dtype != VO_BF16 || d->x_dtype != VO_BF16 || d->y_dtype != VO_BF16) return VO_OK;
   if (d->res1 || d->res2 || d->post_act != VO_ACT_NONE || d->out_scale != 1.f) return VO_OK;
@@ -442,12 +466,14 @@ int vo_ups_try(const vo_conv1d_desc* d, hipStream_t st, int* handled) {
     *handled = 1;
     if (cfg == 2) return launch_ups<128, 128, 2>(d, st);
     if (cfg == 3) return launch_ups<128, 128, 1>(d, st);
+    if (rag) return launch_ups<128, 128, 4, true>(d, st);
     return launch_ups<128, 128, 4>(d, st);
   }
   // wide upsamplers: ups_cfg 4 forces the generic path for these alone
   if (cfg != 4 && d->Ci == 256 && d->Co % 128 == 0 && d->up_cout % 32 == 0 && d->Co >= 256) {
     *handled = 1;
     if (cfg == 5) return launch_upsw<256, 64, 2>(d, st);
+    if (rag) return launch_upsw<256, 128, 1, 8, true>(d, st);
     return launch_upsw<256, 128, 1>(d, st);
   }
   // ups0 (512 -> 256, k16 s8) as 64-column blocks on 4-wave workgroups (one wave per SIMD; its
@@ -457,6 +483,7 @@ int vo_ups_try(const vo_conv1d_desc* d, hipStream_t st, int* handled) {
     *handled = 1;
     if (cfg == 2) return launch_ups<64, 64, 2>(d, st);
     if (cfg == 3) return launch_ups<64, 64, 8>(d, st);
+    if (rag) return launch_ups<64, 64, 4, true>(d, st);
     return launch_ups<64, 64, 4>(d, st);
   }
   return VO_OK;

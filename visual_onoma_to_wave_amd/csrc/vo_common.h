@@ -49,6 +49,13 @@ __device__ __forceinline__ int table_find(const int* start, int n, int x) {
   return lo;
 }
 
+// Ragged batches (vonoma.h, "per-utterance lengths"): the valid rows of utterance b of a (B, T, C) tensor,
+// clamp(lens[b] * scale, 0, T).  b is uniform where the kernels call it: a scalar load.
+__device__ __forceinline__ int rag_rows(const int32_t* lens, int scale, int b, int T) {
+  const int64_t r = (int64_t)max(lens[b], 0) * scale;
+  return (int)min(r, (int64_t)T);
+}
+
 // Workgroups are dispatched round-robin over the 8 XCDs by linear id (w -> XCD w % 8), and each
 // XCD has its own L2.  xcd_grouped_id(w, n) maps linear id w of an n-workgroup grid to a logical id
 // in [0, n) such that consecutive logical ids run on one XCD: workgroups that read the same bytes

@@ -18,20 +18,30 @@ constexpr int CP_ROWS = 256;
 // CC > 0: compile-time channel count (HiFi-GAN V1: 32) -- the staging loads are then issued
 // as one batch (a runtime-trip loop serialises one HBM round trip per iteration); CC = 0:
 // any C (multiple of 8).
-template <typename TX, int CC>
+// RAG (both kernels): ragged batch -- utterance b has Tv = clamp(lens[b] * lens_scale, 0, T_) samples: Tv stands where
+// T does (T_ stays the row stride), and the samples [Tv, T_) are stored as 0.0f.
+template <typename TX, int CC, bool RAG = false>
 __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x, const float* __restrict__ w,
-                                                        float bias, int T, int C_, int K, float slope,
-                                                        float* __restrict__ y) {
+                                                        float bias, int T_, int C_, int K, float slope,
+                                                        float* __restrict__ y, const int32_t* __restrict__ lens,
+                                                        int lens_scale) {
   const int C = CC > 0 ? CC : C_;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * CP_ROWS;
+  const int T = RAG ? rag_rows(lens, lens_scale, b, T_) : T_;
+  if constexpr (RAG) {
+    if (t0 >= T) {  // the whole tile is past the utterance's end
+      if (t0 + threadIdx.x < T_) y[(int64_t)b * T_ + t0 + threadIdx.x] = 0.f;
+      return;
+    }
+  }
   const int pad = (K - 1) / 2;
   const int rows = CP_ROWS + K - 1;
   // pitch C + 4 floats: 16-byte aligned rows, and the 16 lanes of a ds_read_b128 group
   // (consecutive rows, same channels) land on distinct 4-bank groups
   const int P = C + 4;
-  const TX* xb = x + (int64_t)b * T * C;
+  const TX* xb = x + (int64_t)b * T_ * C;
   const int vpr = C / 4;
   // staging: unconditional (clamped) loads, zeroed out of range -- a load under a divergent
   // branch is waited for immediately
@@ -70,6 +80,9 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
   }
   __syncthreads();
   const int t = t0 + threadIdx.x;
+  if constexpr (RAG) {
+    if (t >= T && t < T_) y[(int64_t)b * T_ + t] = 0.f;
+  }
   if (t >= T) return;
   float acc0 = bias, acc1 = 0.f;
   for (int k = 0; k < K; ++k) {
@@ -82,7 +95,7 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
       acc1 += wk[c + 4] * d.x + wk[c + 5] * d.y + wk[c + 6] * d.z + wk[c + 7] * d.w;
     }
   }
-  y[(int64_t)b * T + t] = tanhf(acc0 + acc1);
+  y[(int64_t)b * T_ + t] = tanhf(acc0 + acc1);
 }
 
 // conv_post_rows_kernel (bf16, compile-time C and K; HiFi-GAN V1: 32, 7): each thread reads
@@ -91,18 +104,26 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
 // sum_k z[k][r + k]).  A row is read once (LDS traffic 2K floats per sample) instead of K
 // times from an LDS tile by every output (the stencil kernel above: K*C floats per sample).
 // 256 rows per workgroup give 256 - (K - 1) outputs.
-template <int C, int K>
+template <int C, int K, bool RAG = false>
 __global__ void __launch_bounds__(256) conv_post_rows_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
-                                                             float bias, int T, float slope, float* __restrict__ y) {
+                                                             float bias, int T_, float slope, float* __restrict__ y,
+                                                             const int32_t* __restrict__ lens, int lens_scale) {
   constexpr int OUT = 256 - (K - 1);
   constexpr int PAD = (K - 1) / 2;
   __shared__ float z[K][256];
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * OUT;
   const int r = threadIdx.x;
+  const int T = RAG ? rag_rows(lens, lens_scale, b, T_) : T_;
+  if constexpr (RAG) {
+    if (t0 >= T) {  // the whole tile is past the utterance's end
+      if (r < OUT && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = 0.f;
+      return;
+    }
+  }
   const int t = t0 - PAD + r;
   const bool in = t >= 0 && t < T;
-  const bf16_t* src = x + ((int64_t)b * T + min(max(t, 0), T - 1)) * C;
+  const bf16_t* src = x + ((int64_t)b * T_ + min(max(t, 0), T - 1)) * C;
   float f[C];
 #pragma unroll
   for (int c = 0; c < C; c += 8) load8(src + c, *reinterpret_cast<float(*)[8]>(f + c));
@@ -119,11 +140,14 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const bf16_t* __res
     z[k][r] = p0 + p1;
   }
   __syncthreads();
+  if constexpr (RAG) {
+    if (r < OUT && t0 + r >= T && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = 0.f;
+  }
   if (r >= OUT || t0 + r >= T) return;
   float acc = bias;
 #pragma unroll
   for (int k = 0; k < K; ++k) acc += z[k][r + k];
-  y[(int64_t)b * T + t0 + r] = tanhf(acc);
+  y[(int64_t)b * T_ + t0 + r] = tanhf(acc);
 }
 
 template <typename TY>
@@ -224,8 +248,10 @@ __global__ void __launch_bounds__(256) pack_weight_lin_kernel(const float* __res
 
 using namespace vo;
 
-extern "C" int vo_conv_post(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
-                            float slope, float* y, void* stream) {
+// vo_conv_post (RAG = false, lens unused) and vo_conv_post_lens
+template <bool RAG>
+static int conv_post_entry(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
+                           float slope, float* y, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(x && w && y, "conv_post: null pointer");
   VO_CHECK_ARG(C % 8 == 0 && K % 2 == 1 && C <= 512 && K <= 31, "conv_post: C=%d K=%d unsupported", C, K);
   VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "conv_post: slope %g outside [0, 1]", slope);
@@ -234,18 +260,33 @@ extern "C" int vo_conv_post(const void* x, int x_dtype, const float* w, float bi
   if (x_dtype == VO_BF16 && C == 32 && K == 7 && vo_tune_get("post_cfg") != 1) {  // post_cfg 1: stencil kernel
     constexpr int OUT = 256 - 6;
     dim3 g2((unsigned)((T + OUT - 1) / OUT), (unsigned)B);
-    hipLaunchKernelGGL((conv_post_rows_kernel<32, 7>), g2, dim3(256), 0, st, (const bf16_t*)x, w, bias, T, slope, y);
+    hipLaunchKernelGGL((conv_post_rows_kernel<32, 7, RAG>), g2, dim3(256), 0, st, (const bf16_t*)x, w, bias, T, slope, y,
+                       lens, lens_scale);
     VO_RETURN_LAUNCH();
   }
   dim3 grid((unsigned)((T + CP_ROWS - 1) / CP_ROWS), (unsigned)B);
   const size_t lds = (size_t)(CP_ROWS + K - 1) * (C + 4) * sizeof(float);
   if (x_dtype == VO_BF16 && C == 32)
-    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 32>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K, slope, y);
+    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 32, RAG>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K,
+                       slope, y, lens, lens_scale);
   else if (x_dtype == VO_BF16)
-    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 0>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K, slope, y);
+    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 0, RAG>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K,
+                       slope, y, lens, lens_scale);
   else
-    hipLaunchKernelGGL((conv_post_kernel<float, 0>), grid, dim3(256), lds, st, (const float*)x, w, bias, T, C, K, slope, y);
+    hipLaunchKernelGGL((conv_post_kernel<float, 0, RAG>), grid, dim3(256), lds, st, (const float*)x, w, bias, T, C, K,
+                       slope, y, lens, lens_scale);
   VO_RETURN_LAUNCH();
+}
+
+extern "C" int vo_conv_post(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
+                            float slope, float* y, void* stream) {
+  return conv_post_entry<false>(x, x_dtype, w, bias, B, T, C, K, slope, y, stream, nullptr, 0);
+}
+
+extern "C" int vo_conv_post_lens(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
+                                 float slope, float* y, void* stream, const int32_t* lens, int lens_scale) {
+  VO_CHECK_ARG(lens && lens_scale >= 1, "conv_post_lens: lens is null or lens_scale %d < 1", lens_scale);
+  return conv_post_entry<true>(x, x_dtype, w, bias, B, T, C, K, slope, y, stream, lens, lens_scale);
 }
 
 extern "C" int vo_transpose_bct(const float* x, int B, int C, int T, void* y, int y_dtype, int ldy, void* stream) {

@@ -103,23 +103,27 @@ class ResBlock(HipModule):
         """True when this ResBlock runs as fused pair / block launches (else two convs per pair)."""
         return self.channels in self.fused_pair_channels and x.dtype == self.compute_dtype == torch.bfloat16
 
-    def run(self, x, out=None, out_scale=1.0, accumulate=None, stage=None, before_last=None):
+    def run(self, x, out=None, out_scale=1.0, accumulate=None, stage=None, before_last=None, lens=None, lens_scale=1):
         """x (B, T, C) channels-last -> ResBlock(x) * out_scale (+ accumulate), written to out.
         ``stage`` (0..3) selects the MRF stage's own kernel instantiation and timer tag.
         ``before_last`` (conv path only) is called right before the launch that reads
-        ``accumulate`` -- the MRF's concurrent chains order their accumulations there."""
+        ``accumulate`` -- the MRF's concurrent chains order their accumulations there.
+        ``lens`` (int32 (B,) on the device) / ``lens_scale``: ragged batch -- utterance b is its first
+        lens[b] * lens_scale rows (ops.conv1d); rows past them are neither read nor written, so with ``lens``
+        a fresh ``out`` holds uninitialised memory there."""
         var = 0 if stage is None else stage + 1
         tag = None if stage is None else f"mrf_s{stage}"
         packs = self._packed(x.device, self._build)
         k, C = self.kernel_size, self.channels
         cur = x
+        rag = {} if lens is None else dict(lens=lens, lens_scale=lens_scale)
         if (RB3_ENABLED and k == 3 and len(self.dilation) == 3 and C in self.fused_pair_channels
                 and x.dtype == self.compute_dtype == torch.bfloat16
                 and sum(d + 1 for d in self.dilation) <= 12 and max(self.dilation) <= 8):
             # k = 3: the whole ResBlock (three pairs) in one launch; x1 / x2 stay on chip
             (w1s, b1s), (w2s, b2s) = zip(*[p[0] for p in packs]), zip(*[p[1] for p in packs])
             return ops.resblock3(cur, w1s, b1s, w2s, b2s, self.dilation, LRELU_SLOPE, out=out,
-                                 out_scale=out_scale, acc=accumulate, tag=tag)
+                                 out_scale=out_scale, acc=accumulate, tag=tag, **rag)
         if C in self.fused_pair_channels and x.dtype == self.compute_dtype == torch.bfloat16:
             # narrow stages: one fused launch per (c1, c2) pair, the intermediate stays in LDS
             for n, (d, p) in enumerate(zip(self.dilation, packs)):
@@ -130,20 +134,20 @@ class ResBlock(HipModule):
                 last = n == len(self.dilation) - 1
                 cur = ops.resblock_pair(cur, w1, b1, w2, b2, k, d, LRELU_SLOPE, out=out if last else None,
                                         out_scale=out_scale if last else 1.0,
-                                        acc=accumulate if last else None, tag=tag, frag=frag)
+                                        acc=accumulate if last else None, tag=tag, frag=frag, **rag)
             return cur
         for n, (d, p) in enumerate(zip(self.dilation, packs)):
             (w1, b1), (w2, b2) = p[0], p[1]
             t = ops.conv1d(cur, w1, b1, Co=C, K=k, dil=d, pad=get_padding(k, d), pre_act=ops.ACT_LRELU,
                            pre_slope=LRELU_SLOPE, post_act=ops.ACT_LRELU, post_slope=LRELU_SLOPE,
-                           compute_dtype=self.compute_dtype, out_dtype=x.dtype, variant=var, tag=tag)
+                           compute_dtype=self.compute_dtype, out_dtype=x.dtype, variant=var, tag=tag, **rag)
             last = n == len(self.dilation) - 1
             if last and before_last is not None:
                 before_last()
             cur = ops.conv1d(t, w2, b2, Co=C, K=k, pad=get_padding(k, 1), res1=cur,
                              out=out if last else None, out_scale=out_scale if last else 1.0,
                              res2=accumulate if last else None, compute_dtype=self.compute_dtype,
-                             out_dtype=x.dtype, variant=var, tag=tag)
+                             out_dtype=x.dtype, variant=var, tag=tag, **rag)
         return cur
 
     def forward(self, x):
@@ -188,24 +192,57 @@ class Generator(HipModule):
                     post=(wpost.reshape(wpost.shape[0], -1).contiguous(),
                           float(self.conv_post.bias.detach().float().cpu())))
 
-    def run(self, mel_cl):
-        """mel_cl (B, T, 80) channels-last (fp32 or compute dtype) -> wav (B, 256*T) fp32."""
+    def _lens32(self, lengths, B, T, device):
+        """``lengths`` of a ragged ``run`` -> int32 (B,) on ``device``.  A device tensor (int32 / int64) is converted
+        by one kernel and never read on the host (the kernels clamp it to [0, T]); a host sequence is validated here."""
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            if lengths.dtype not in (torch.int32, torch.int64) or lengths.shape != (B,):
+                raise ValueError(f"lengths must be an int32 / int64 tensor of shape ({B},), got {lengths.dtype} "
+                                 f"{tuple(lengths.shape)}")
+            if lengths.device != device:
+                raise ValueError(f"lengths is on {lengths.device}, the mel on {device}")
+            return ops.mask_from_lengths(lengths.contiguous(), T, want_mask=False)[1]
+        host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(host) != B or any(v < 0 or v > T for v in host):
+            raise ValueError(f"lengths must be {B} frame counts in [0, {T}], got {host}")
+        return ops.mask_from_lengths(torch.tensor(host, dtype=torch.int32, device=device), T, want_mask=False)[1]
+
+    def run(self, mel_cl, lengths=None):
+        """mel_cl (B, T, 80) channels-last (fp32 or compute dtype) -> wav (B, 256*T) fp32.
+        ``lengths`` (optional; int32 / int64 device tensor or host sequence of B frame counts in [0, T]): ragged
+        batch -- row b is what ``run(mel_cl[b:b+1, :lengths[b]])`` gives, followed by exact zeros: every layer treats
+        utterance b as a tensor of lengths[b] * (rows per frame) rows, so the padded frames are neither computed nor
+        seen through the convs' halos.  Device lengths are never read on the host: the call is
+        graph-capturable and a replay follows lengths changed in place."""
         p = self._packed(mel_cl.device, self._build)
         dt = self.compute_dtype
+        lens = None if lengths is None else self._lens32(lengths, mel_cl.shape[0], mel_cl.shape[1], mel_cl.device)
+        scale = 1  # rows per mel frame at the current layer
+
+        def rag():
+            return {} if lens is None else dict(lens=lens, lens_scale=scale)
         w, b = p["pre"]
-        x = ops.conv1d(mel_cl, w, b, Co=w.shape[1], K=7, pad=3, out_dtype=dt, compute_dtype=dt)
+        x = ops.conv1d(mel_cl, w, b, Co=w.shape[1], K=7, pad=3, out_dtype=dt, compute_dtype=dt, **rag())
         for i in range(self.num_upsamples):
             w, b, cout, u, pad = p["ups"][i]
             x = ops.conv1d(x, w, b, Co=u * cout, K=2, pad=1, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE,
-                           transposed=dict(stride=u, pad=pad, cout=cout), out_dtype=dt, compute_dtype=dt)
-            x = self.mrf(i, x)
+                           transposed=dict(stride=u, pad=pad, cout=cout), out_dtype=dt, compute_dtype=dt, **rag())
+            scale *= u
+            x = self.mrf(i, x, lens=lens, lens_scale=scale)
         wk, bp = p["post"]
-        return ops.conv_post(x, wk, bp, slope=0.01)
+        return ops.conv_post(x, wk, bp, slope=0.01, **rag())
 
-    def mrf(self, i, x):
+    def mrf(self, i, x, lens=None, lens_scale=None):
         """Multi-receptive-field fusion of upsampling stage i (hifigan/models.py:155-160):
         (sum_j ResBlock_{i,j}(x)) / num_kernels on channels-last x (B, T, C) in the compute
-        dtype; the ResBlocks accumulate into one output in their epilogues."""
+        dtype; the ResBlocks accumulate into one output in their epilogues.
+        ``lens`` (int32 (B,) device tensor, frames): ragged batch; ``lens_scale`` = rows of x per frame (default:
+        the stage's, the product of upsample_rates[:i + 1])."""
+        if lens is not None and lens_scale is None:
+            lens_scale = 1
+            for u in self.h.upsample_rates[:i + 1]:
+                lens_scale *= u
+        rag = {} if lens is None else dict(lens=lens, lens_scale=lens_scale)
         xs = torch.empty_like(x)
         stage = i if self.num_upsamples == 4 else None
         timer = profiling.active()
@@ -218,14 +255,14 @@ class Generator(HipModule):
             rb.compute_dtype = self.compute_dtype
         with grp:
             if MRF_STREAMS and x.is_cuda and len(rbs) > 1 and not any(rb.fused(x) for rb in rbs):
-                self._mrf_concurrent(rbs, x, xs, stage)
+                self._mrf_concurrent(rbs, x, xs, stage, rag)
             else:
                 for j, rb in enumerate(rbs):
                     rb.run(x, out=xs, out_scale=1.0 / self.num_kernels, accumulate=xs if j > 0 else None,
-                           stage=stage)
+                           stage=stage, **rag)
         return xs
 
-    def _mrf_concurrent(self, rbs, x, xs, stage):
+    def _mrf_concurrent(self, rbs, x, xs, stage, rag=None):
         """The MRF's ResBlock chains are independent until their sum: chain j runs on its own
         stream, and only its last launch (the one that adds into ``xs``) waits for chain j - 1's
         last launch, so the sum is formed in the same order as the sequential loop (bit-identical
@@ -239,6 +276,8 @@ class Generator(HipModule):
             s.wait_stream(main)  # x (and xs's allocation) are ordered on main
             x.record_stream(s)
             xs.record_stream(s)
+            if rag:
+                rag["lens"].record_stream(s)
         done = [None] * len(rbs)
         for j, (rb, s) in enumerate(zip(rbs, chain_streams)):
             def before_last(j=j, s=s):
@@ -246,7 +285,7 @@ class Generator(HipModule):
                     s.wait_event(done[j - 1])
             with torch.cuda.stream(s):
                 rb.run(x, out=xs, out_scale=1.0 / self.num_kernels, accumulate=xs if j > 0 else None,
-                       stage=stage, before_last=before_last)
+                       stage=stage, before_last=before_last, **(rag or {}))
                 done[j] = torch.cuda.Event()
                 done[j].record(s)
         main.wait_event(done[-1])  # chain j's completion implies chains < j (their last launches)
@@ -319,11 +358,11 @@ class Generator(HipModule):
         plan.append((self.conv_post, G.ConvSpec(K=7, pad=3, pre_slope=0.01, post="tanh", co_pad=4), (B, T, C), False))
         return plan
 
-    def forward(self, x):
-        """x (B, 80, T) mel -> (B, 1, 256 * T) waveform (reference: models.py:149-165)."""
+    def forward(self, x, lengths=None):
+        """x (B, 80, T) mel -> (B, 1, 256 * T) waveform (reference: models.py:149-165); ``lengths``: as ``run``."""
         self._check_inference()
         mel_cl = ops.transpose_bct(x, torch.float32)
-        return self.run(mel_cl).unsqueeze(1)
+        return self.run(mel_cl, lengths).unsqueeze(1)
 
     def remove_weight_norm(self):
         print("Removing weight norm...")

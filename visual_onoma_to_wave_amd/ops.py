@@ -59,12 +59,29 @@ def _contig(t, name):
     return t
 
 
+def _check_lens(lens, lens_scale, B, ref, name):
+    """Validate the per-utterance lengths of a ragged call: a contiguous int32 (B,) tensor on ``ref``'s device
+    (never read on the host) and an integer lens_scale >= 1."""
+    if not isinstance(lens, torch.Tensor):
+        raise TypeError(f"{name}: lens must be a device tensor (a host sequence goes through Generator.run)")
+    if lens.dtype != torch.int32:
+        raise TypeError(f"{name}: lens must be int32, got {lens.dtype}")
+    if lens.dim() != 1 or lens.shape[0] != B:
+        raise ValueError(f"{name}: lens must have shape ({B},), got {tuple(lens.shape)}")
+    if lens.device != ref.device:
+        raise ValueError(f"{name}: lens is on {lens.device}, the activations on {ref.device}")
+    _contig(lens, "lens")
+    if int(lens_scale) != lens_scale or lens_scale < 1:
+        raise ValueError(f"{name}: lens_scale must be an integer >= 1, got {lens_scale}")
+    return int(lens_scale)
+
+
 # ----------------------------------------------------------------------------- conv1d
 
 def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_dtype=None,
            pre_act=ACT_NONE, pre_slope=0.0, post_act=ACT_NONE, post_slope=0.0, res1=None,
            res2=None, out_scale=1.0, compute_dtype=torch.bfloat16, transposed=None, variant=0,
-           tag=None, stride=1, groups=1, ymask=None, ymask_slope=0.0):
+           tag=None, stride=1, groups=1, ymask=None, ymask_slope=0.0, lens=None, lens_scale=1):
     """Channels-last conv: x (B, T_in, Ci) -> y (B, T_out, Co).
 
     ``w_packed``: [K][Co][Ci] in ``compute_dtype`` (see pack_conv_weight).
@@ -75,6 +92,11 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
     ``ymask`` (the output's shape and strides, bf16): each output stored as
     round(round(v) * (ymask > 0 ? 1 : ymask_slope)) -- an input gradient put through the leaky-ReLU
     backward of the layer whose output ymask is (bit for bit vo_lrelu_mask on the stored output).
+    ``lens`` (int32 (B,) on the device) / ``lens_scale``: ragged batch -- utterance b is the tensor of its first
+    clamp(lens[b] * lens_scale, 0, T_in) rows: rows past it read as zero (x, res1, res2) and are not written
+    (include/vonoma.h, "per-utterance lengths"; same-length convs and the polyphase form only).  The profiling
+    timer's FLOPs and bytes of a ragged call are still those of the padded shape: a true count would need the
+    lengths on the host.
     """
     if x.dim() == 2:
         x = x.unsqueeze(0)
@@ -136,8 +158,11 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
         if ymask.shape != out.shape or ymask.stride() != out.stride() or ymask.dtype != out.dtype:
             raise ValueError("conv1d: ymask must match the output (shape, strides, dtype)")
         d.ymask, d.ymask_slope = ymask.data_ptr(), float(ymask_slope)
+    if lens is not None:
+        d.lens_scale = _check_lens(lens, lens_scale, B, x, "conv1d")
+        d.lens = lens.data_ptr()
     ws = None
-    plain = (transposed is None and stride <= 1 and groups <= 1)
+    plain = (transposed is None and stride <= 1 and groups <= 1 and lens is None)
     deep_bf16 = (compute_dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and bias is None and res1 is None and
                  res2 is None and ymask is None and pre_act == ACT_NONE and post_act == ACT_NONE and out_scale == 1.0 and
                  Co <= 256 and Ci * K >= 2048 and B * T_rows >= 8192)
@@ -537,12 +562,19 @@ def mask_from_lengths(lens, max_len, want_mask=True):
 
 # ----------------------------------------------------------------------------- vocoder glue
 
-def conv_post(x, w_kc, bias, slope=0.01):
-    """x (B, T, C) -> tanh(conv(lrelu(x))) (B, T) fp32; w_kc (K, C) fp32."""
+def conv_post(x, w_kc, bias, slope=0.01, lens=None, lens_scale=1):
+    """x (B, T, C) -> tanh(conv(lrelu(x))) (B, T) fp32; w_kc (K, C) fp32.
+    ``lens`` / ``lens_scale`` (ragged batch, as ``conv1d``): sample t of utterance b is computed from its first
+    R_b = clamp(lens[b] * lens_scale, 0, T) rows alone for t < R_b and is exactly 0.0 from R_b on."""
     _contig(x, "x")
     B, T, C = x.shape
     K = w_kc.shape[0]
     y = torch.empty((B, T), dtype=torch.float32, device=x.device)
+    if lens is not None:
+        sc = _check_lens(lens, lens_scale, B, x, "conv_post")
+        _lib.check(_lib.lib().vo_conv_post_lens(_ptr(x), vo_dtype(x), _ptr(w_kc), float(bias), B, T, C, K,
+                                                float(slope), _ptr(y), _stream(x), _ptr(lens), sc), "vo_conv_post_lens")
+        return y
     _lib.check(_lib.lib().vo_conv_post(_ptr(x), vo_dtype(x), _ptr(w_kc), float(bias), B, T, C, K,
                                        float(slope), _ptr(y), _stream(x)), "vo_conv_post")
     return y
@@ -573,9 +605,13 @@ def pack_frag(w_packed):
     return out
 
 
-def resblock_pair(x, w1, b1, w2, b2, K, dil, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None, frag=False):
+def resblock_pair(x, w1, b1, w2, b2, K, dil, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None, frag=False,
+                  lens=None, lens_scale=1):
     """y = (x + c2(lrelu(c1_dil(lrelu(x))))) * out_scale (+ acc); x (B, T, C) bf16, C in {32, 64, 128}.
-    frag: w1 / w2 are pack_frag packs (C = 64 / 128, K = 7 / 11; vo_resblock_pair_frag)."""
+    frag: w1 / w2 are pack_frag packs (C = 64 / 128, K = 7 / 11; vo_resblock_pair_frag).
+    ``lens`` / ``lens_scale`` (ragged batch, as ``conv1d``; K = 7 / 11): rows past R_b read as zero -- x, acc and the
+    c1 output held on chip -- and rows >= R_b of ``out`` are not written.  The timer's FLOPs stay those of the
+    padded shape."""
     _contig(x, "x")
     B, T, C = x.shape
     if x.dtype != torch.bfloat16 or w1.dtype != torch.bfloat16 or w2.dtype != torch.bfloat16:
@@ -585,10 +621,11 @@ def resblock_pair(x, w1, b1, w2, b2, K, dil, slope=0.1, out=None, out_scale=1.0,
         raise ValueError("resblock_pair: acc must match x")
     timer = profiling.active()
     ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
-    fn = _lib.lib().vo_resblock_pair_frag if frag else _lib.lib().vo_resblock_pair
+    name = ("vo_resblock_pair_frag" if frag else "vo_resblock_pair") + ("_lens" if lens is not None else "")
+    fn = getattr(_lib.lib(), name)
+    rag = () if lens is None else (_ptr(lens), _check_lens(lens, lens_scale, B, x, "resblock_pair"))
     _lib.check(fn(_ptr(x), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out), _ptr(acc),
-                  B, T, C, K, dil, float(slope), float(out_scale), _stream(x)),
-               "vo_resblock_pair_frag" if frag else "vo_resblock_pair")
+                  B, T, C, K, dil, float(slope), float(out_scale), _stream(x), *rag), name)
     if ev is not None:
         flops = 2.0 * 2.0 * B * T * C * C * K
         nbytes = 2.0 * x.numel() * 2 + (x.numel() * 2 if acc is not None else 0) + 2 * w1.numel() * 2
@@ -597,10 +634,13 @@ def resblock_pair(x, w1, b1, w2, b2, K, dil, slope=0.1, out=None, out_scale=1.0,
     return out
 
 
-def resblock3(x, w1s, b1s, w2s, b2s, dils, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None):
+def resblock3(x, w1s, b1s, w2s, b2s, dils, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None, lens=None,
+              lens_scale=1):
     """A whole K = 3 ResBlock1 (three (c1_d, c2) pairs) in one launch (vo_resblock3):
     y = x_3 * out_scale (+ acc); x (B, T, C) bf16, C in {32, 64, 128}; w1s / w2s: three packed
-    [3][C][C] bf16 weights each, b1s / b2s three fp32 biases, dils the three dilations."""
+    [3][C][C] bf16 weights each, b1s / b2s three fp32 biases, dils the three dilations.
+    ``lens`` / ``lens_scale`` (ragged batch, as ``conv1d``): rows past R_b read as zero -- x, acc and the on-chip
+    T1, x_1, x_2 -- and rows >= R_b of ``out`` are not written.  The timer's FLOPs stay those of the padded shape."""
     _contig(x, "x")
     B, T, C = x.shape
     if x.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in list(w1s) + list(w2s)):
@@ -614,8 +654,10 @@ def resblock3(x, w1s, b1s, w2s, b2s, dils, slope=0.1, out=None, out_scale=1.0, a
     dil = (ctypes.c_int * 3)(*[int(d) for d in dils])
     timer = profiling.active()
     ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
-    _lib.check(_lib.lib().vo_resblock3(_ptr(x), arr(w1s), arr(b1s), arr(w2s), arr(b2s), dil, _ptr(out), _ptr(acc),
-                                       B, T, C, float(slope), float(out_scale), _stream(x)), "vo_resblock3")
+    name = "vo_resblock3" if lens is None else "vo_resblock3_lens"
+    rag = () if lens is None else (_ptr(lens), _check_lens(lens, lens_scale, B, x, "resblock3"))
+    _lib.check(getattr(_lib.lib(), name)(_ptr(x), arr(w1s), arr(b1s), arr(w2s), arr(b2s), dil, _ptr(out), _ptr(acc),
+                                         B, T, C, float(slope), float(out_scale), _stream(x), *rag), name)
     if ev is not None:
         flops = 3 * 2.0 * 2.0 * B * T * C * C * 3
         nbytes = 2.0 * x.numel() * 2 + (x.numel() * 2 if acc is not None else 0) + 6 * w1s[0].numel() * 2

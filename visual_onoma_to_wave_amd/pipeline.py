@@ -23,10 +23,13 @@ import torch
 
 class SynthesisPipeline:
     """``submit(*model_args)`` starts the acoustic model of a batch; ``next_wav()`` vocodes the
-    oldest submitted batch on the current stream and returns (acoustic outputs, wav (B, N))."""
+    oldest submitted batch on the current stream and returns (acoustic outputs, wav (B, N)).
+    ``ragged``: the vocoder runs each batch with the acoustic model's own ``mel_len`` (``out[9]``, on the device:
+    no host read) as ``Generator.run``'s ``lengths`` -- the padded frames are not computed, and every waveform
+    is what its utterance gives alone, exact zeros past its end."""
 
-    def __init__(self, model, vocoder, device=None):
-        self.model, self.vocoder = model, vocoder
+    def __init__(self, model, vocoder, device=None, ragged=False):
+        self.model, self.vocoder, self.ragged = model, vocoder, ragged
         self.device = torch.device(device) if device is not None else next(vocoder.parameters()).device
         self.acoustic_stream = torch.cuda.Stream(self.device)
         self._pending = collections.deque()
@@ -55,4 +58,5 @@ class SynthesisPipeline:
         for t in out:
             if torch.is_tensor(t) and t.is_cuda:
                 t.record_stream(cur)
-        return out, self.vocoder.run(out[1])  # postnet mel is channels-last (B, T, 80): no transpose
+        # postnet mel is channels-last (B, T, 80): no transpose; out[9] (mel_len) was recorded on this stream above
+        return out, self.vocoder.run(out[1], out[9] if self.ragged else None)

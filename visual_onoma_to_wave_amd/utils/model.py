@@ -69,12 +69,25 @@ def get_vocoder(config, device, checkpoint=None):
     return vocoder.to(device)
 
 
-def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True):
+def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True, ragged=False):
+    """``ragged`` (with ``lengths`` in samples, as the reference passes them): the vocoder runs the batch as a
+    ragged one -- utterance i over its first ceil(lengths[i] / hop) mel frames only (``Generator.run``'s
+    ``lengths``), so its waveform is what it gives alone, not a function of the padding it was batched with.
+    The default computes every padded frame, as the reference does."""
     name = model_config["vocoder"]["model"]
     with torch.no_grad():
         if name != "HiFi-GAN":
             raise NotImplementedError(name)
-        wavs = vocoder(mels).squeeze(1)
+        if ragged:
+            if lengths is None:
+                raise ValueError("vocoder_infer: ragged=True needs lengths (samples per utterance)")
+            hop = 1
+            for u in vocoder.h.upsample_rates:
+                hop *= u
+            frames = [-(-int(n) // hop) for n in lengths]
+            wavs = vocoder(mels, lengths=frames).squeeze(1)
+        else:
+            wavs = vocoder(mels).squeeze(1)
     wavs = wavs.cpu().numpy()
     if Normalize:
         # the reference reads preprocess_config["preprocessing"]["audio"]["max_wav_value"]
