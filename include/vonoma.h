@@ -140,6 +140,13 @@ int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d);
  * Returns the number of fields copied. */
 #define VO_CONV1D_LAUNCH_FIELDS 13
 int vo_conv1d_last_launch(int32_t* rec, int n);
+/* The record vo_conv1d(d, stream) would leave, without launching: the same argument checks and the same tile
+ * rule, on the host alone (no tensor pointer of d is dereferenced, no HIP call, no GPU needed; the pointers
+ * only have to be null or not as in the real call).  Writes min(n, VO_CONV1D_LAUNCH_FIELDS) fields into rec
+ * (all zeros: refused, or a descriptor the streaming upsampler takes) and returns what vo_conv1d would return
+ * before its launch: VO_OK, or VO_ERR_INVALID with the same vo_last_error text.  The calling thread's
+ * last-launch record is left as it was. */
+int vo_conv1d_plan(const vo_conv1d_desc* d, int32_t* rec, int n);
 
 /* Weight preparation (load time).  Replaces the weight-norm fold (remove_weight_norm,
  * scripts/hifigan/models.py:105-109,167-174: w = g * v / ||v||, norm over all dims but 0)

@@ -61,7 +61,7 @@ def test_drop_tap_fails_most_elements():
 
 def test_tile_matrix_covers_required_instantiations():
     """Every conv1d_kernel instantiation the dispatcher can reach with default knobs (REQUIRED, written by
-    hand from launch_types / launch_disc) is declared by a case of the GPU matrix, which asserts it at run
+    hand from select_types / select_disc) is declared by a case of the GPU matrix, which asserts it at run
     time through the launch record."""
     import test_gpu_conv1d_tiles as M
     declared = {CC.instantiation(c) for c in M.CASES}

@@ -1,4 +1,4 @@
-"""Every conv1d forward tile the dispatcher ships (launch_types / launch_disc in csrc/conv1d.hip), one NICE
+"""Every conv1d forward tile the dispatcher ships (select_types / select_disc in csrc/conv1d.hip), one NICE
 and one ragged case per instantiation, at its edges against float64 (tests/conv_check.py: bf16-exact
 operands, a derived element-wise bar, rel-L2 < 1e-5 on fp32 output, guard bands around output and input).
 T sits one past a tile multiple, so the last time tile holds a single row.  Every case asserts the launch
@@ -25,9 +25,9 @@ CASES = []
 
 
 # (NI, WCO) of each tile -- 16-channel MFMA tiles per wave, waves across the output channels; BCO = 16 NI WCO --
-# written by hand from the launch_cfg<..., NI, NJ, WCO, WT, ...> lines of the dispatcher.  Two pairs of tiles
+# written by hand from the tile definitions of the dispatcher (tile_of in csrc/conv1d.hip).  Two pairs of tiles
 # share BCO x BT and differ only here: Co = 80 (64 x 128 as 4 x 1) against the bf16 default (2 x 2), and
-# launch_disc's 64 x 64 (4 x 1) against launch_types' (2 x 2).
+# select_disc's 64 x 64 (4 x 1) against select_types' (2 x 2).
 WAVE_TYPES = {(128, 16): (2, 4), (32, 16): (1, 2), (128, 32): (2, 4), (32, 256): (2, 1), (64, 256): (4, 1),
               (64, 64): (2, 2), (64, 128): (2, 2), (128, 256): (4, 2), (256, 256): (4, 4), (128, 128): (4, 2)}
 WAVE_CO80 = (4, 1)
@@ -95,9 +95,9 @@ add(2, 65, 40, 144, 3, io=F32, tile=(64, 64, 1, 0, 0, 1))
 add(9, 257, 32, 128, 3, io=F32, tile=(128, 128, 1, 0, 1, 1))     # the fp32 default
 add(9, 257, 40, 144, 3, io=F32, tile=(128, 128, 1, 0, 0, 1))
 
-# ---------------------------------------------------------------- strided / grouped (launch_disc)
+# ---------------------------------------------------------------- strided / grouped (select_disc)
 for S in (1, 2, 3, 4):
-    G = 4 if S == 1 else 1   # stride 1 reaches launch_disc through groups
+    G = 4 if S == 1 else 1   # stride 1 reaches select_disc through groups
     K = 5
     T65, T129 = t_in(65, K, S), t_in(129, K, S)
     # 32 x 64: cog <= 32 (grouped: 4 groups of 32 / 8 output channels) or Co <= 32
@@ -151,9 +151,9 @@ for _c in CASES:
     _seen[_c["name"]] = _c
 
 # ---------------------------------------------------------------- instantiations that must stay covered
-# (NI, WCO, BT, S, SEG, nice, sizeof TIN, sizeof TC, sizeof TOUT), written by hand from launch_types / launch_disc /
+# (NI, WCO, BT, S, SEG, nice, sizeof TIN, sizeof TC, sizeof TOUT), written by hand from select_types / select_disc /
 # vo_conv1d: every tile reachable with default knobs, NICE and ragged, per dtype triple it ships in.  NI and
-# WCO make each entry one instantiation: without them the Co = 80 tile and launch_disc's stride-1 64 x 64
+# WCO make each entry one instantiation: without them the Co = 80 tile and select_disc's stride-1 64 x 64
 # tile would coincide with other entries, and deleting their cases would go unnoticed.
 
 
@@ -165,16 +165,16 @@ _ALL4 = ((2, 2, 2), (2, 2, 4), (4, 2, 2), (4, 2, 4))
 _F = ((4, 4, 4),)
 _D = ((4, 4, 4), (2, 2, 2), (2, 2, 4))
 REQUIRED = (
-    # launch_types, bf16 compute: 128 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128, 64 x 64, 64 x 128,
+    # select_types, bf16 compute: 128 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128, 64 x 64, 64 x 128,
     # 128 x 256, 256 x 256
     _both(2, 4, 16) + _both(2, 4, 32) + _both(2, 1, 256) + _both(4, 1, 256) + _both(4, 1, 128, nices=(0,)) +
     _both(2, 2, 64, sizes=_ALL4) + _both(2, 2, 128, sizes=_ALL4) + _both(4, 2, 256) + _both(4, 4, 256, sizes=_ALL4) +
-    # launch_types, fp32 compute: the two SEG tiles, 32 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128,
+    # select_types, fp32 compute: the two SEG tiles, 32 x 16, 128 x 32, 32 x 256, 64 x 256, Co = 80 64 x 128,
     # 64 x 64, 128 x 128
     _both(1, 2, 64, seg=1, sizes=_F) + _both(2, 2, 64, seg=1, sizes=_F) + _both(1, 2, 16, sizes=_F) +
     _both(2, 4, 32, sizes=_F) + _both(2, 1, 256, sizes=_F) + _both(4, 1, 256, sizes=_F) +
     _both(4, 1, 128, sizes=_F, nices=(0,)) + _both(2, 2, 64, sizes=_F) + _both(4, 2, 128, sizes=_F) +
-    # launch_disc: 32 x 64, 64 x 64, 128 x 64 per stride; 128 x 32 at stride 8
+    # select_disc: 32 x 64, 64 x 64, 128 x 64 per stride; 128 x 32 at stride 8
     [t for s in (1, 2, 3, 4) for t in _both(2, 1, 64, s, sizes=_D) + _both(4, 1, 64, s, sizes=_D) +
      _both(4, 2, 64, s, sizes=_D)] +
     _both(4, 2, 32, 8, sizes=_D))
@@ -188,10 +188,13 @@ def _run(c):
     dev = torch.device("cuda:0")
     x_buf, y_buf = m["x_buf"].to(dev), m["y_buf"].to(dev)
     d = {k: (m[k].to(dev) if m[k] is not None else None) for k in ("w_packed", "bias", "res1", "res2")}
-    ops.conv1d(CC.x_view(c, x_buf), d["w_packed"], d["bias"], out=CC.y_view(c, y_buf), res1=d["res1"], res2=d["res2"],
-               **CC.conv_kwargs(c))
+    args = (CC.x_view(c, x_buf), d["w_packed"], d["bias"])
+    kw = dict(out=CC.y_view(c, y_buf), res1=d["res1"], res2=d["res2"], **CC.conv_kwargs(c))
+    ops.conv1d(*args, **kw)
     rec = ops.conv1d_last_launch()
     assert rec == CC.record(c), (c["name"], rec, CC.record(c))
+    # the plan of the same arguments (no launch) names the same tile and leaves the record of the launch alone
+    assert ops.conv1d_plan(*args, **kw) == rec and ops.conv1d_last_launch() == rec
     torch.cuda.synchronize()
     int_t = CC._INT[m["x_buf"].dtype]
     assert torch.equal(x_buf.cpu().view(int_t), m["x_buf"].view(int_t)), "the input buffer changed"

@@ -152,7 +152,7 @@ def test_plane_kernels_ragged_with_epilogue_accumulate(C, K):
 
 # ------------------------------------------------------------------------------ streaming upsamplers
 
-# the three shapes of vo_ups_try (upsample.hip): (Ci, C_out, stride) and the input steps per unit, 16 NJ
+# the three shapes of vo_ups_takes (upsample.hip): (Ci, C_out, stride) and the input steps per unit, 16 NJ
 @pytest.mark.parametrize("Ci,cout,u,BT", [(128, 64, 2, 64), (64, 32, 2, 64), (256, 128, 8, 16)])
 def test_streaming_upsampler_ragged(Ci, cout, u, BT):
     from visual_onoma_to_wave_amd import ops
@@ -178,6 +178,16 @@ def _rec():
     return ops.conv1d_last_launch()
 
 
+def _conv1d(*args, **kw):
+    """ops.conv1d; the plan of the same arguments (ops.conv1d_plan: no launch) must be the record the launch left,
+    and must leave that record alone."""
+    from visual_onoma_to_wave_amd import ops
+    y = ops.conv1d(*args, **kw)
+    rec = _rec()
+    assert ops.conv1d_plan(*args, **kw) == rec and _rec() == rec, (ops.conv1d_plan(*args, **kw), rec)
+    return y
+
+
 def _first_bt(op, x):
     op(x, None, None, None)
     return _rec()["BT"]
@@ -192,7 +202,7 @@ def test_conv_pre_ragged(dt):
     x = _rand((B, T, 80), 21, torch.float32)
 
     def op(x, lens, out, acc):
-        return ops.conv1d(x, w, bias, Co=512, K=7, pad=3, out=out, out_dtype=dt, compute_dtype=dt, lens=lens)
+        return _conv1d(x, w, bias, Co=512, K=7, pad=3, out=out, out_dtype=dt, compute_dtype=dt, lens=lens)
     assert _first_bt(op, x) == 64
     run_case(op, x, 64, record=_rec)
 
@@ -209,8 +219,8 @@ def test_ups0_ragged(dt):
     x = _rand((B, T, 512), 23, dt)
 
     def op(x, lens, out, acc):
-        return ops.conv1d(x, w, bias, Co=8 * 256, K=2, pad=1, pre_act=ops.ACT_LRELU, pre_slope=0.1, out=out,
-                          transposed=dict(stride=8, pad=4, cout=256), out_dtype=dt, compute_dtype=dt, lens=lens)
+        return _conv1d(x, w, bias, Co=8 * 256, K=2, pad=1, pre_act=ops.ACT_LRELU, pre_slope=0.1, out=out,
+                       transposed=dict(stride=8, pad=4, cout=256), out_dtype=dt, compute_dtype=dt, lens=lens)
     assert _first_bt(op, x) == 64
     run_case(op, x, 64, up=8, record=_rec)
 
@@ -229,9 +239,9 @@ def test_stage0_conv_ragged(K, dil, dt):
     def op(x, lens, out, acc):
         # acc carries both residuals, so that run_case cuts / poisons them with the input
         r1, r2 = acc[..., :256].contiguous(), acc[..., 256:].contiguous()
-        return ops.conv1d(x, w, bias, Co=256, K=K, dil=dil, pad=dil * (K - 1) // 2, pre_act=ops.ACT_LRELU, pre_slope=0.1,
-                          res1=r1, res2=r2, out=out, out_scale=1.0 / 3, compute_dtype=dt, out_dtype=dt, variant=1,
-                          lens=lens)
+        return _conv1d(x, w, bias, Co=256, K=K, dil=dil, pad=dil * (K - 1) // 2, pre_act=ops.ACT_LRELU, pre_slope=0.1,
+                       res1=r1, res2=r2, out=out, out_scale=1.0 / 3, compute_dtype=dt, out_dtype=dt, variant=1,
+                       lens=lens)
     both = torch.cat([res1, res2], dim=-1)
     op(x, None, None, both)
     assert _rec()["BT"] == BT and _rec()["ROLE"] == (1 if dt == torch.bfloat16 else 0)

@@ -126,7 +126,7 @@ __device__ __forceinline__ void lds_put(bx3_t* p, const Raw8<bx3_t>& v) {
 constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
 
 // vo_conv1d_last_launch: the tile of this thread's last vo_conv1d call (zeroed at its entry, filled
-// by launch_cfg_s; host stores only)
+// from its plan before the launch; host stores only)
 static thread_local int32_t g_last_launch[VO_CONV1D_LAUNCH_FIELDS] = {};
 
 // epilogue: lane (g = lane>>4, lr = lane&15) holds channels [n0, n0 + 4*NI) of position
@@ -994,177 +994,203 @@ __global__ void __launch_bounds__(WCO * WT * 64) lin_kernel(ConvArgs a) {
 #endif  // VO_ABLATIONS
 
 // ------------------------------------------------------------------ host dispatch
-static bool splitk_plan(const vo_conv1d_desc* d, int* splits, int* kcs);
-template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS_BF16, int ROLE = 0,
-          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false,
-          bool RAG = false>
-static int launch_cfg_s(const vo_conv1d_desc* d, hipStream_t st) {
-  constexpr int BCO = 16 * NI * WCO;
-  constexpr int BT = 16 * NJ * WT;
-  constexpr int TPS = sizeof(TC) == 2 ? TPS_BF16 : 1;
+// vo_conv1d = conv1d_check (arguments -> type triple), a select_* rule (descriptor, compute width, vo_tune knobs -> tile),
+// plan_tile (nice, LDS bytes, reduction splits), launch_plan (tile -> instantiation).  All but the last are plain host
+// code without a HIP call: vo_conv1d_plan runs them and stops there.
+//
+// A tile, written once: a wave holds NI x NJ MFMA tiles of 16 channels x 16 rows, a workgroup is WCO x WT waves, so
+// BCO = 16 NI WCO output channels x BT = 16 NJ WT rows.  TPS = taps per pipeline step in bf16 compute (4-byte compute
+// steps one tap; 0 = a lin_kernel tile); ROLE .. SEG are conv1d_kernel's parameters of the same names.  The conv stride
+// is the descriptor's, not the tile's: launch_tile takes it beside the tile.
+struct Tile {
+  int NI, NJ, WCO, WT, TPS, ROLE = 0, PRIO = 0, ABL = 0;
+  bool GL = false, RS = false;
+  int EJ = 2;
+  bool SEG = false;
+  constexpr int bco() const { return 16 * NI * WCO; }
+  constexpr int bt() const { return 16 * NJ * WT; }
+  constexpr Tile role(int r, int prio = 0) const { Tile t = *this; t.ROLE = r; t.PRIO = prio; return t; }
+  constexpr Tile dma(bool rs = false) const { Tile t = *this; t.GL = true; t.RS = rs; return t; }  // weights by LDS-DMA; role split
+  constexpr Tile tps(int n) const { Tile t = *this; t.TPS = n; return t; }
+  constexpr Tile seg() const { Tile t = *this; t.SEG = true; return t; }
+};
+// T<BCO>x<BT> {NI, NJ, WCO, WT, TPS}; _n<NI>w<WCO> names the twin of equal BCO x BT (128 x 32 and 64 x 64: the strided /
+// grouped convs' tiles, 64 x 64 also gen_cfg 7; 64 x 128: the Co = 80 tile); _seg = utterance-segment tile (BT / 16
+// utterances); _mrf<s> = MRF stage s in its own ROLE (stage 0: s_setprio, weights by LDS-DMA, _rs = role-split staging)
+constexpr Tile T32x16{1, 1, 2, 1, 4}, T64x16{1, 1, 4, 1, 4}, T128x16{2, 1, 4, 1, 4}, T128x32{2, 2, 4, 1, 4},
+    T128x32_n4w2{4, 1, 2, 2, 2}, T32x64{2, 1, 1, 4, 4}, T64x64{2, 2, 2, 2, 2}, T64x64_n4w1{4, 1, 1, 4, 4},
+    T128x64{4, 2, 2, 2, 2}, T64x128{2, 4, 2, 2, 2}, T64x128_n4w1{4, 2, 1, 4, 4}, T128x128{4, 4, 2, 2, 2},
+    T256x128{4, 4, 4, 2, 2}, T32x256{2, 4, 1, 4, 4}, T64x256{4, 4, 1, 4, 4}, T128x256{4, 4, 2, 4, 2}, T256x256{4, 8, 4, 2, 2};
+constexpr Tile T32x64_seg = Tile{1, 2, 2, 2, 1}.seg(), T64x64_seg = Tile{2, 2, 2, 2, 1}.seg(),
+               T32x128_seg = Tile{1, 4, 2, 2, 1}.seg(), T64x128_seg = Tile{2, 4, 2, 2, 1}.seg();
+constexpr Tile T256x256_mrf0 = T256x256.role(1, 1).dma(), T256x256_mrf0_rs = T256x256.role(1, 1).dma(true),
+               T128x128_mrf1 = T128x128.role(2), T64x256_mrf2 = T64x256.role(3), T32x256_mrf3 = T32x256.role(4);
+#ifdef VO_ABLATIONS  // A/B library only (measured and dropped): _t<TPS>, _gl / _rs = dma() / dma(true); lin_kernel co x rows
+constexpr Tile A256x256_t1_gl = T256x256.tps(1).dma(), A256x256_t1_rs = T256x256.tps(1).dma(true),
+               A128x128_t1_gl = T128x128.tps(1).dma(), A256x256_t1 = T256x256.tps(1), A64x128_t1 = T64x128.tps(1),
+               A128x128_mrf0 = T128x128.role(1), A256x256_mrf0_plain = T256x256.role(1),
+               A256x256_mrf0_prio = T256x256.role(1, 1), A256x256_mrf0_t3 = T256x256.role(1, 1).tps(3).dma(),
+               A256x256_mrf0_t1 = T256x256.role(1, 1).tps(1).dma(), A256x256_mrf0_t1_rs = T256x256.role(1, 1).tps(1).dma(true);
+constexpr Tile LIN_64x64{2, 2, 2, 2, 0}, LIN_128x128{4, 4, 2, 2, 0}, LIN_64x128{2, 4, 2, 2, 0}, LIN_128x64{4, 2, 2, 2, 0};
+#define VO_AB(...) , __VA_ARGS__
+#else
+#define VO_AB(...)
+#endif
+
+// (TIN, TC, TOUT) of an instantiation: F = float, B = bf16_t, X = bx3_t (split-bf16, VO_F32X3)
+enum ConvTypes { FFF, FXF, BBB, BBF, FBB, FBF };
+constexpr int kTypeBytes[][3] = {{4, 4, 4}, {4, 4, 4}, {2, 2, 2}, {2, 2, 4}, {4, 2, 2}, {4, 2, 4}};
+
+// What one vo_conv1d call launches: all the launch record holds, and what launch_tile needs beyond the tile.
+struct ConvPlan {
+  bool ups;          // the streaming upsampler (upsample.hip) takes the descriptor: no tile, an all-zero record
+  int types, role;   // ConvTypes; d->variant where it selects an MRF stage's own tiles (bf16 in, compute and out)
+  const Tile* tile;  // null = refused by the selector
+  int S;             // conv stride
+  bool nice;         // Ci % 32 == 0 and Co % BCO == 0: the instantiation without channel bounds checks
+  int splits, kcs;   // split reduction: grid z, 32-channel chunks per split (1, 0 = off)
+  size_t lds;
+};
+
+static ConvArgs conv_args(const vo_conv1d_desc* d, int BCO, int BT) {
   ConvArgs a;
-  a.x = d->x; a.xbs = d->x_bstride; a.ldx = d->ldx;
-  a.w = d->w; a.bias = d->bias;
-  a.y = d->y; a.ybs = d->y_bstride; a.ldy = d->ldy;
-  a.res1 = d->res1; a.res2 = d->res2;
-  a.T_in = d->T_in; a.T_out = d->T_out; a.Ci = d->Ci; a.Co = d->Co;
-  a.K = d->K; a.dil = d->dil; a.pad = d->pad;
+  memset(&a, 0, sizeof(a));
+  a.x = d->x; a.xbs = d->x_bstride; a.ldx = d->ldx; a.w = d->w; a.bias = d->bias;
+  a.y = d->y; a.ybs = d->y_bstride; a.ldy = d->ldy; a.res1 = d->res1; a.res2 = d->res2;
+  a.T_in = d->T_in; a.T_out = d->T_out; a.Ci = d->Ci; a.Co = d->Co; a.K = d->K; a.dil = d->dil; a.pad = d->pad;
   a.pre_act = d->pre_act; a.pre_slope = d->pre_slope;
   a.post_act = d->post_act; a.post_slope = d->post_slope; a.out_scale = d->out_scale;
-  a.transposed = d->transposed; a.up_stride = d->up_stride; a.up_pad = d->up_pad;
-  a.up_cout = d->up_cout; a.up_tout = d->up_tout;
-  a.tiles_per_b = SEG ? 1 : (d->T_out + BT - 1) / BT;
+  a.transposed = d->transposed; a.up_stride = d->up_stride; a.up_pad = d->up_pad; a.up_cout = d->up_cout; a.up_tout = d->up_tout;
+  a.tiles_per_b = (d->T_out + BT - 1) / BT;
   a.co_tiles = (d->Co + BCO - 1) / BCO;
   a.B = d->B;
   a.ymask = d->ymask; a.ymask_slope = d->ymask_slope;
   a.lens = d->lens; a.lens_scale = d->lens_scale;
-  // the ragged instantiations (RAG) exist for the tiles launch_types picks and the MRF stage-0 role: a call with
-  // lens that reaches any other tile is refused, never run dense
-  VO_CHECK_ARG((d->lens != nullptr) == RAG, "conv1d: no ragged (lens) form of this tile (%s)",
-               SEG ? "utterance-segment tiles: T_out <= 16 in fp32" : "strided / grouped / variant 2-4");
   const int groups = d->groups > 1 ? d->groups : 1;
   a.cig = d->Ci / groups;
   a.cog = d->Co / groups;
-  const int win_rows = SEG ? (BT / 16) * (16 + (d->K - 1) * d->dil) : (BT - 1) * S + 1 + (d->K - 1) * d->dil;
-  const bool nice = d->Ci % KC == 0 && d->Co % BCO == 0;
-  // role-split kernels (RS): + the raw window staging area of conv1d_kernel (XPW pieces per window wave)
-  constexpr bool SPL = RS && GL && S == 1 && sizeof(TC) == 2 && sizeof(TIN) == 2 && ABL == 0 && (WCO * WT) % 2 == 0;
-  constexpr int NWX = WCO * WT / 2;
-  constexpr size_t RAW = SPL ? 2 * (size_t)((((BT - 1) * S + 1 + HALO_MAX) * (KC / 8) + 64 * NWX - 1) / (64 * NWX)) * NWX * 1024 : 0;
-  const size_t lds = (size_t)(2 * win_rows + 2 * TPS * BCO + 1) * Lds<TC>::PITCH * sizeof(TC) + (nice ? RAW : 0);
-  if (lds > 160 * 1024) {
-    vo_set_error("conv1d: LDS request %zu B exceeds 160 KiB", lds);
-    return VO_ERR_INVALID;
-  }
-  auto kern = nice ? conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, true, ROLE, PRIO, ABL, S, GL, RS, EJ, SEG, RAG>
-                   : conv1d_kernel<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS, false, ROLE, PRIO, ABL, S, false, false, 2, SEG, RAG>;
-  a.partial = nullptr;
-  a.kcs = 0;
-  int splits = 1;
-  if constexpr (S == 1) {
-    int kcs = 0;
-    if (d->workspace && !d->lens && splitk_plan(d, &splits, &kcs) &&
-        d->workspace_bytes >= (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float)) {
-      a.partial = reinterpret_cast<float*>(d->workspace);
-      a.kcs = kcs;
-    } else {
-      splits = 1;
-    }
-  }
-  const int32_t rec[VO_CONV1D_LAUNCH_FIELDS] = {BCO, BT, S, SEG, nice, splits, (int32_t)sizeof(TIN), (int32_t)sizeof(TC),
-                                                (int32_t)sizeof(TOUT), ROLE, d->compute_dtype, NI, WCO};
-  memcpy(g_last_launch, rec, sizeof(rec));
-  const unsigned gx = SEG ? (unsigned)((d->B + BT / 16 - 1) / (BT / 16)) : (unsigned)(a.tiles_per_b * d->B);
-  dim3 grid(gx, (unsigned)a.co_tiles, (unsigned)splits);
-  hipLaunchKernelGGL(kern, grid, dim3(WCO * WT * 64), lds, st, a);
+  return a;
+}
+
+template <const Tile& T, typename TIN, typename TC, typename TOUT, bool RAG = false, int S = 1>
+static int launch_tile(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  constexpr int BT = T.bt(), TPS = sizeof(TC) == 2 ? T.TPS : 1;
+  ConvArgs a = conv_args(d, T.bco(), BT);
+  if (T.SEG) a.tiles_per_b = 1;
+  a.partial = p.splits > 1 ? reinterpret_cast<float*>(d->workspace) : nullptr;
+  a.kcs = p.kcs;
+  auto kern = p.nice ? conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, true, T.ROLE, T.PRIO, T.ABL, S, T.GL, T.RS, T.EJ, T.SEG, RAG>
+                     : conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, false, T.ROLE, T.PRIO, T.ABL, S, false, false, 2, T.SEG, RAG>;
+  const unsigned gx = T.SEG ? (unsigned)((d->B + BT / 16 - 1) / (BT / 16)) : (unsigned)(a.tiles_per_b * d->B);
+  dim3 grid(gx, (unsigned)a.co_tiles, (unsigned)p.splits);
+  hipLaunchKernelGGL(kern, grid, dim3(T.WCO * T.WT * 64), p.lds, st, a);
   if (a.partial) {
     const int64_t n = (int64_t)d->B * d->T_out * (d->Co / 4);
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel<TOUT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, splits);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel<TOUT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, p.splits);
   }
   VO_RETURN_LAUNCH();
 }
 
-template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS_BF16, int ROLE = 0,
-          int PRIO = 0, int ABL = 0, bool GL = false, bool RS = false, int EJ = 2>
-static int launch_cfg(const vo_conv1d_desc* d, hipStream_t st) {
-  return launch_cfg_s<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS_BF16, ROLE, PRIO, ABL, 1, GL, RS, EJ>(d, st);
-}
-// launch_cfg with the ragged flag in front: launch_types passes its own
-template <bool RAG, typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS_BF16, int ROLE = 0,
-          int PRIO = 0, int ABL = 0, bool GL = false, bool RS = false, int EJ = 2>
-static int launch_cfg_r(const vo_conv1d_desc* d, hipStream_t st) {
-  return launch_cfg_s<TIN, TC, TOUT, NI, NJ, WCO, WT, TPS_BF16, ROLE, PRIO, ABL, 1, GL, RS, EJ, false, RAG>(d, st);
-}
-template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT>
-static int launch_seg(const vo_conv1d_desc* d, hipStream_t st) {
-  return launch_cfg_s<TIN, TC, TOUT, NI, NJ, WCO, WT, 1, 0, 0, 0, 1, false, false, 2, true>(d, st);
+// The rest of the plan once the tile is chosen: nice, the LDS request, the reduction splits.
+static int plan_tile(const vo_conv1d_desc* d, ConvPlan* p) {
+  const Tile& t = *p->tile;
+  p->nice = false; p->splits = 1; p->kcs = 0; p->lds = 0;
+  if (t.TPS == 0) return VO_OK;  // lin_kernel
+  const int S = p->S, tin = kTypeBytes[p->types][0], tc = kTypeBytes[p->types][1];
+  const int BCO = t.bco(), BT = t.bt(), tps = tc == 2 ? t.TPS : 1, halo = (d->K - 1) * d->dil;
+  // the ragged instantiations exist for the tiles select_types picks and the MRF stage-0 role (strided / grouped
+  // convs and variants 2-4 with lens never pass conv1d_check): a call with lens is refused, never run dense
+  VO_CHECK_ARG(!(d->lens && t.SEG), "conv1d: no ragged (lens) form of this tile (utterance-segment tiles: T_out <= 16 in fp32)");
+  const int win_rows = t.SEG ? (BT / 16) * (16 + halo) : (BT - 1) * S + 1 + halo;
+  p->nice = d->Ci % KC == 0 && d->Co % BCO == 0;
+  // role-split kernels (RS): + the raw window staging area of conv1d_kernel (XPW pieces per window wave)
+  const bool spl = t.RS && t.GL && S == 1 && tc == 2 && tin == 2 && t.ABL == 0 && (t.WCO * t.WT) % 2 == 0;
+  const int nwx = t.WCO * t.WT / 2;
+  const size_t raw = spl ? 2 * (size_t)((((BT - 1) * S + 1 + HALO_MAX) * (KC / 8) + 64 * nwx - 1) / (64 * nwx)) * nwx * 1024 : 0;
+  p->lds = (size_t)(2 * win_rows + 2 * tps * BCO + 1) * (tc == 2 ? Lds<bf16_t>::PITCH : Lds<float>::PITCH) * tc + (p->nice ? raw : 0);
+  if (p->lds > 160 * 1024) {
+    vo_set_error("conv1d: LDS request %zu B exceeds 160 KiB", p->lds);
+    return VO_ERR_INVALID;
+  }
+  int splits = 1, kcs = 0;
+  if (S == 1 && d->workspace && !d->lens && splitk_plan(d, &splits, &kcs) &&
+      d->workspace_bytes >= (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float)) {
+    p->splits = splits;
+    p->kcs = kcs;
+  }
+  return VO_OK;
 }
 
-#ifdef VO_ABLATIONS
-// lin_kernel: K = 1, bf16 input and compute, Ci = 32 NC, Co % BCO == 0 (checked by the caller)
-template <typename TOUT, int NI, int NJ, int WCO, int WT, int D, int NC>
-static int launch_lin(const vo_conv1d_desc* d, hipStream_t st) {
-  constexpr int BCO = 16 * NI * WCO;
-  constexpr int BT = 16 * NJ * WT;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = d->x; a.xbs = d->x_bstride; a.ldx = d->ldx;
-  a.w = d->w; a.bias = d->bias;
-  a.y = d->y; a.ybs = d->y_bstride; a.ldy = d->ldy;
-  a.res1 = d->res1; a.res2 = d->res2;
-  a.T_in = d->T_in; a.T_out = d->T_out; a.Ci = d->Ci; a.Co = d->Co;
-  a.K = 1; a.dil = 1; a.pad = 0;
-  a.pre_act = VO_ACT_NONE;
-  a.post_act = d->post_act; a.post_slope = d->post_slope; a.out_scale = d->out_scale;
-  a.tiles_per_b = (d->T_out + BT - 1) / BT;
-  a.co_tiles = d->Co / BCO;
-  a.B = d->B;
-  a.cig = d->Ci; a.cog = d->Co;
-  a.ymask = d->ymask; a.ymask_slope = d->ymask_slope;
-  a.lens = nullptr; a.lens_scale = 0;
-  auto kern = lin_kernel<TOUT, NI, NJ, WCO, WT, D, NC>;
-  dim3 grid((unsigned)(a.tiles_per_b * d->B), (unsigned)a.co_tiles);
-  hipLaunchKernelGGL(kern, grid, dim3(WCO * WT * 64), 0, st, a);
-  VO_RETURN_LAUNCH();
+// the VO_CONV1D_LAUNCH_FIELDS record of a plan (rec zeroed by the caller: it stays so for the upsampler and lin_kernel)
+static void plan_record(const vo_conv1d_desc* d, const ConvPlan& p, int32_t* rec) {
+  if (p.ups || p.tile->TPS == 0) return;
+  const Tile& t = *p.tile;
+  const int32_t r[VO_CONV1D_LAUNCH_FIELDS] = {t.bco(), t.bt(), p.S, t.SEG, p.nice, p.splits, kTypeBytes[p.types][0],
+                                              kTypeBytes[p.types][1], kTypeBytes[p.types][2], t.ROLE, d->compute_dtype, t.NI, t.WCO};
+  memcpy(rec, r, sizeof(r));
 }
-#endif  // VO_ABLATIONS
 
-// HiFi-GAN discriminator layers (strided and/or grouped, C5): 64-row tiles so that a stride-4
-// window ((64 - 1) * 4 + 1 + 40 rows) still double-buffers in LDS; output-channel tiles no
-// wider than a group where groups are narrow (block-diagonal weights: a tile spanning g
-// groups reduces over g groups' input channels).
-template <typename TIN, typename TC, typename TOUT, int S>
-static int launch_disc_s(const vo_conv1d_desc* d, hipStream_t st) {
+// HiFi-GAN discriminator layers (strided and/or grouped, C5): 64-row tiles so that a stride-4 window ((64 - 1) * 4 + 1
+// + 40 rows) still double-buffers in LDS; output-channel tiles no wider than a group where groups are narrow
+// (block-diagonal weights: a tile spanning g groups reduces over g groups' input channels).
+static const Tile* select_disc(const vo_conv1d_desc* d) {
   const int groups = d->groups > 1 ? d->groups : 1;
   const int cog = d->Co / groups;
-  if constexpr (S >= 8) return launch_cfg_s<TIN, TC, TOUT, 4, 1, 2, 2, 2, 0, 0, 0, S>(d, st);  // 128 x 32
-  if (d->Co <= 32 || cog <= 32) return launch_cfg_s<TIN, TC, TOUT, 2, 1, 1, 4, 4, 0, 0, 0, S>(d, st);  // 32 x 64
-  if (d->Co <= 64 || cog <= 64) return launch_cfg_s<TIN, TC, TOUT, 4, 1, 1, 4, 4, 0, 0, 0, S>(d, st);  // 64 x 64
+  if (d->stride > 4 && d->stride != 8) vo_set_error("conv1d: stride %d unsupported (1..4, 8)", d->stride);
+  if (d->stride > 4) return d->stride == 8 ? &T128x32_n4w2 : nullptr;  // ConvTranspose1d(k 16, s 8) input gradient
+  if (d->Co <= 32 || cog <= 32) return &T32x64;
+  if (d->Co <= 64 || cog <= 64) return &T64x64_n4w1;
   // 64 x 64 where 128 x 64 tiles would leave fewer than 256 workgroups (the MPD's stride-3 layers over joined
   // period columns): C5 23.63 -> 23.57 ms in one process (tile_cfg 4 = off)
   const int64_t t64 = (int64_t)d->B * ((d->T_out + 63) / 64) * ((d->Co + 127) / 128);
-  if (vo_tune_get("tile_cfg") != 4 && t64 < 256) return launch_cfg_s<TIN, TC, TOUT, 4, 1, 1, 4, 4, 0, 0, 0, S>(d, st);
-  return launch_cfg_s<TIN, TC, TOUT, 4, 2, 2, 2, 2, 0, 0, 0, S>(d, st);                                 // 128 x 64
+  if (vo_tune_get("tile_cfg") != 4 && t64 < 256) return &T64x64_n4w1;
+  return &T128x64;
 }
-template <typename TIN, typename TC, typename TOUT>
-static int launch_disc(const vo_conv1d_desc* d, hipStream_t st) {
-  switch (d->stride > 1 ? d->stride : 1) {
-    case 1: return launch_disc_s<TIN, TC, TOUT, 1>(d, st);
-    case 2: return launch_disc_s<TIN, TC, TOUT, 2>(d, st);
-    case 3: return launch_disc_s<TIN, TC, TOUT, 3>(d, st);
-    case 4: return launch_disc_s<TIN, TC, TOUT, 4>(d, st);
-    case 8: return launch_disc_s<TIN, TC, TOUT, 8>(d, st);  // ConvTranspose1d(k 16, s 8) input gradient
-    default: vo_set_error("conv1d: stride %d unsupported (1..4, 8)", d->stride); return VO_ERR_INVALID;
+
+// The MRF stages' own instantiations (variant 1..4 with bf16 in, compute and out; same tiles as generic)
+static const Tile* select_role(const vo_conv1d_desc* d, int role) {
+  if (role != 1) return role == 2 ? &T128x128_mrf1 : role == 3 ? &T64x256_mrf2 : &T32x256_mrf3;
+  // C = 256: 256 x 256 tile, 8 waves of 64 co x 128 rows (each weight tap feeds twice the rows of the 128 x 128 tile:
+  // 0.095/0.151/0.208 -> 0.077/0.125/0.172 ms for k = 3/7/11 at B = 32, bit-identical).  conv_cfg 1 = the 128 x 128 tile.
+  // s_setprio(1) around each MFMA cluster: +1-3 % (0.1667 -> 0.1654 ms at k = 11); conv_cfg 2 = without
+  // Round 2: weights by LDS-DMA (GL): 0.084 / 0.134 / 0.171 -> 0.083 / 0.126 / 0.163 ms for k = 3 / 7 / 11 alone
+  // (tools/ab_conv_cfg.py, bit-identical), within noise in the bench step; conv_cfg 3 = register-staged weights,
+  // 4 = GL with 3-tap steps (spills)
+  const int cc = vo_tune_get("conv_cfg");
+  if (d->lens && cc != 0) {
+    vo_set_error("conv1d: conv_cfg=%d selects a kernel without a ragged (lens) form", cc);
+    return nullptr;
   }
+#ifdef VO_ABLATIONS  // measured-and-dropped tiles (A/B builds only: make abl)
+  if (cc >= 1 && cc <= 4) return cc == 1 ? &A128x128_mrf0 : cc == 2 ? &A256x256_mrf0_plain : cc == 3 ? &A256x256_mrf0_prio : &A256x256_mrf0_t3;
+  // one tap per step (k = 3's second 2-tap step re-fetches tap 2 as its padding tap)
+  if (cc == 7 || cc == 8) return cc == 7 ? &A256x256_mrf0_t1 : &A256x256_mrf0_t1_rs;
+#endif
+  // Round 2: role-split staging (RS: half the waves issue the weight DMA, half copy the window by LDS-DMA two chunks
+  // ahead; bare step barriers): k = 7 / 11 0.137 / 0.175 -> 0.130 / 0.168 ms, k = 3 0.084 -> 0.096 (two-step chunks: the
+  // weight waves' 8 DMA pieces per step, not the window, bind) -- k >= 5 only; conv_cfg 5 forces it, 6 disables it
+  // (tools/probes/s0_probe.py, bit-identical)
+  // Round 3, measured and dropped (tools/mrf_bench.py --stages 0, conv pairs): 4-wave tiles, two workgroups per CU
+  // (256 co x 128 rows, 1 tap per step, with and without RS; 128 co x 256 rows) -- 27-45 % slower than the 8-wave
+  // 256 x 256 tile at k = 3 / 7 / 11
+  // (EJ, the epilogue's position tiles whose residual / accumulator rows are requested together: 4 measured within
+  // 1 % of 2, 8 spills and runs 10-20 % slower -- kept at 2)
+  return cc == 5 || (cc != 6 && d->K >= 5) ? &T256x256_mrf0_rs : &T256x256_mrf0;
 }
 
-#ifdef VO_ABLATIONS
-// the lin_kernel tile for a launch; kLinSkip = Co fits no tile
-constexpr int kLinSkip = -1000;
-template <typename TOUT, int NC>
-static int lin_tile(const vo_conv1d_desc* d, hipStream_t st, int lc) {
-  if (lc == 2 && d->Co % 64 == 0) return launch_lin<TOUT, 2, 2, 2, 2, 4, NC>(d, st);
-  if (lc == 3 && d->Co % 128 == 0) return launch_lin<TOUT, 4, 4, 2, 2, 3, NC>(d, st);
-  if (lc == 4 && d->Co % 64 == 0) return launch_lin<TOUT, 2, 4, 2, 2, 4, NC>(d, st);
-  if (lc == 5 && d->Co % 128 == 0) return launch_lin<TOUT, 4, 2, 2, 2, 4, NC>(d, st);
-  return kLinSkip;
-}
-#endif  // VO_ABLATIONS
-
-// RAG: the ragged instantiations of the same tiles (vo_conv1d with lens)
-template <typename TIN, typename TC, typename TOUT, bool RAG = false>
-static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
+// Every other conv; tin / tc = sizeof the input and the LDS compute element
+static const Tile* select_types(const vo_conv1d_desc* d, int tin, int tc) {
   const int64_t rows = (int64_t)d->B * d->T_out;
   // short sequences (the glyph encoder / phoneme-level predictors run at T_src ~ 12): one
   // 16- or 32-row time tile, waves spread over output channels
-  if constexpr (sizeof(TC) == 4) {
+  if (tc == 4) {
     // fp32 / split-bf16 at T_out <= 16: utterance-segment tiles (SEG, see conv1d_kernel), 4 utterances
     // x 64 output channels (32 below Co = 512); seg_cfg 3 = 8 utterances, 4 = off (the tiles below)
     const int gc = vo_tune_get("seg_cfg");
     if (d->T_out <= 16 && !d->transposed && d->stride <= 1 && (d->K - 1) * d->dil <= SEG_HALO && d->Co >= 32 &&
         gc != 4 && (int64_t)d->B * d->x_bstride < ((int64_t)1 << 31)) {
-      if (gc == 3) return d->Co >= 512 ? launch_seg<TIN, TC, TOUT, 2, 4, 2, 2>(d, st) : launch_seg<TIN, TC, TOUT, 1, 4, 2, 2>(d, st);
-      return d->Co >= 512 ? launch_seg<TIN, TC, TOUT, 2, 2, 2, 2>(d, st) : launch_seg<TIN, TC, TOUT, 1, 2, 2, 2>(d, st);
+      if (gc == 3) return d->Co >= 512 ? &T64x128_seg : &T32x128_seg;
+      return d->Co >= 512 ? &T64x64_seg : &T32x64_seg;
     }
   }
   if (d->T_out <= 16 && d->Co >= 64) {
@@ -1172,50 +1198,42 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
     // workgroups of 128 x 16: FFN w_1 66 -> 51 us, w_2 28 -> 20, predictor k3 20 -> 13
     // (tools/ab_sb.py genf32 5 3); gen_cfg 2 = 64 x 16, 5 = 128 x 16
     const int gc = vo_tune_get("gen_cfg");
-    if (gc == 2) return launch_cfg_r<RAG, TIN, TC, TOUT, 1, 1, 4, 1, 4>(d, st);  // 64 x 16
-    if (gc != 5 && sizeof(TC) == 4) return launch_cfg_r<RAG, TIN, TC, TOUT, 1, 1, 2, 1, 4>(d, st);  // 32 x 16
-    return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 1, 4, 1, 4>(d, st);  // 128 x 16
+    return gc == 2 ? &T64x16 : (gc != 5 && tc == 4) ? &T32x16 : &T128x16;
   }
-  if (d->T_out <= 32 && d->Co >= 64) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 2, 4, 1, 4>(d, st);  // 128 x 32
-  if (d->Co <= 32) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 1, 4, 4>(d, st);   // 32 x 256
+  if (d->T_out <= 32 && d->Co >= 64) return &T128x32;
+  if (d->Co <= 32) return &T32x256;
   if (d->Co <= 64 || d->Co == 80) {
     // Co = 80 (PostNet output conv, mel_linear at B*T = 16384 rows): 64 x 128 tiles, twice the
     // workgroups of 64 x 256 (512 -> 80 k5 36.7 -> 29.7 us; tools/probes/small_convs.py)
     const int gc = vo_tune_get("gen_cfg");
-    if (gc == 6 || (d->Co == 80 && gc != 8)) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 2, 1, 4, 4>(d, st);  // 64 x 128
-    if (gc == 7) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 1, 1, 4, 4>(d, st);  // 64 x 64
-    return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 1, 4, 4>(d, st);  // 64 x 256
+    return (gc == 6 || (d->Co == 80 && gc != 8)) ? &T64x128_n4w1 : gc == 7 ? &T64x64_n4w1 : &T64x256;
   }
-  if (rows <= 2048) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 2, 2, 2, 2>(d, st);  // 64 x 64
+  if (rows <= 2048) return &T64x64;
 #ifdef VO_ABLATIONS
-  if constexpr (sizeof(TC) == 2 && sizeof(TIN) == 2) {
+  if (tc == 2 && tin == 2) {
     // K = 1 (Linear layers), A/B only: the LDS-free register-ring kernel, lin_cfg 2 / 3 / 4 / 5 =
     // 64 x 64, 128 x 128, 64 co x 128 rows, 128 co x 64 rows (measured slower, see lin_kernel)
     const int lc = vo_tune_get("lin_cfg");
     if (lc >= 2 && d->K == 1 && d->pad == 0 && d->T_in == d->T_out && !d->transposed && d->variant == 0 &&
-        d->pre_act == VO_ACT_NONE && d->Ci % KC == 0 && d->x_bstride % 8 == 0) {
-      int rc = kLinSkip;
-      if (d->Ci == 256) rc = lin_tile<TOUT, 8>(d, st, lc);
-      if (d->Ci == 512) rc = lin_tile<TOUT, 16>(d, st, lc);
-      if (d->Ci == 1024) rc = lin_tile<TOUT, 32>(d, st, lc);
-      if (rc != kLinSkip) return rc;
+        d->pre_act == VO_ACT_NONE && d->Ci % KC == 0 && d->x_bstride % 8 == 0 &&
+        (d->Ci == 256 || d->Ci == 512 || d->Ci == 1024)) {
+      if (lc == 2 && d->Co % 64 == 0) return &LIN_64x64;
+      if (lc == 3 && d->Co % 128 == 0) return &LIN_128x128;
+      if (lc == 4 && d->Co % 64 == 0) return &LIN_64x128;
+      if (lc == 5 && d->Co % 128 == 0) return &LIN_128x64;
     }
   }
-#endif
-#ifdef VO_ABLATIONS
-  if constexpr (sizeof(TC) == 2) {  // K = 1 staging A/B: one tap per step (TPS 1), weights by LDS-DMA (GL), role split (RS)
+  if (tc == 2) {  // K = 1 staging A/B: one tap per step (TPS 1), weights by LDS-DMA (GL), role split (RS)
     const int gq = vo_tune_get("gen_cfg");
-    if (gq == 13 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, false>(d, st);
-    if (gq == 14 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1, 0, 0, 0, true, true>(d, st);
-    if (gq == 15 && d->Co % 128 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 2, 1, 0, 0, 0, true, false>(d, st);
-    if (gq == 16 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 1>(d, st);
-    if (gq == 17) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 1>(d, st);  // 64 x 128, TPS 1
+    if (gq == 13 && d->Co % 256 == 0) return &A256x256_t1_gl;
+    if (gq == 14 && d->Co % 256 == 0) return &A256x256_t1_rs;
+    if (gq == 15 && d->Co % 128 == 0) return &A128x128_t1_gl;
+    if (gq == 16 && d->Co % 256 == 0) return &A256x256_t1;
+    if (gq == 17) return &A64x128_t1;
   }
 #endif
-  if constexpr (sizeof(TC) == 2) {
-    if (d->workspace && splitk_bf16_ok(d)) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // split 256 x 256
-  }
-  if constexpr (sizeof(TC) == 2) {
+  if (tc == 2) {
+    if (d->workspace && splitk_bf16_ok(d)) return &T256x256;  // split reduction
     // decoder shapes at B*T = 16384 rows (tools/ab_sb.py gen): wide outputs (FFN w_1 k9 1024,
     // fused q/k/v 768) -> 256 x 256 tiles (-18 %); 1x1 convs to 256 channels -> 64 x 128
     // (twice the workgroups, -12 %).  gen_cfg 1 forces the 128 x 128 tile (A/B).
@@ -1231,66 +1249,138 @@ static int launch_types(const vo_conv1d_desc* d, hipStream_t st) {
       // (utterances of >= 256 rows: at T_out = 128 -- the MSD's 1024-channel layers -- half of every 256-row
       // tile was padding: C5 23.68 -> 23.43 ms with them on the tiles below; tile_cfg 9 = the round-5 rule)
       const bool t_ok = d->T_out >= 256 || vo_tune_get("tile_cfg") == 9;
-      if (vo_tune_get("gen_cfg") != 11 && t_ok && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256
-      if (vo_tune_get("gen_cfg") < 9 && d->K == 1 && d->Co <= 256) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);         // 64 x 128
+      if (vo_tune_get("gen_cfg") != 11 && t_ok && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return &T256x256;
+      if (vo_tune_get("gen_cfg") < 9 && d->K == 1 && d->Co <= 256) return &T64x128;
       // Co <= 256 k > 1 with fewer than 512 128 x 128 tiles (the C4 decoder's FFN w_1 input gradient, 1024 ->
       // 256 k9 at 16384 rows: 125 -> 106 us, tools/probes/dgrad_tiles.py): 64 x 128, twice the workgroups
       const int64_t t128 = (int64_t)d->B * ((d->T_out + 127) / 128) * ((d->Co + 127) / 128);
-      if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+      if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return &T64x128;
       // wide convs with fewer than 256 128 x 128 tiles (C5's MPD over joined period columns, 1024 -> 1024
       // k = 5 at 2-5 k rows: 136-312 workgroups) on 64 x 128 tiles too: C5 24.07 -> 23.75 ms (tile_cfg 1 = off)
-      if (vo_tune_get("tile_cfg") != 1 && d->Co % 64 == 0 && t128 < 256) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+      if (vo_tune_get("tile_cfg") != 1 && d->Co % 64 == 0 && t128 < 256) return &T64x128;
     }
     // mid-width convs (PostNet 512 -> 512 k5, conv_pre 80 -> 512 k7 at 16384 rows): 128 x 256
     // tiles (twice the rows per staged weight tap): 512 k5 67.9 -> 63.4 us, 80 k7 27.6 -> 27.0,
     // bit-identical (tools/probes/mid_convs.py); the Co = 128 polyphase upsampler is slower with
     // it (210 -> 234 us).  gen_cfg 9 forces it, gen_cfg 10 = 256 x 128 (no gain), gen_cfg 1 = 128 x 128.
     const int gc = vo_tune_get("gen_cfg");
-    if (gc == 9 || (gc != 1 && gc != 10 && d->Co >= 512 && d->Co < 768 && d->Co % 128 == 0 && !d->transposed))
-      return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 4, 2>(d, st);  // 128 x 256
-    if (gc == 10) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 4, 2, 2>(d, st);  // 256 x 128
-    if (gc == 11) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);  // 64 x 128 (A/B)
-    if (gc == 12 && d->Co % 256 == 0) return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 8, 4, 2, 2>(d, st);  // 256 x 256 (A/B)
+    if (gc == 9 || (gc != 1 && gc != 10 && d->Co >= 512 && d->Co < 768 && d->Co % 128 == 0 && !d->transposed)) return &T128x256;
+    if (gc == 10) return &T256x128;
+    if (gc == 11) return &T64x128;                       // (A/B)
+    if (gc == 12 && d->Co % 256 == 0) return &T256x256;  // (A/B)
+    // bf16: 64 x 128 in place of the 128 x 128 default (C5 23.68 -> 23.52 ms, C4 and inference shapes
+    // unaffected); tile_cfg 9 = the round-5 rule
+    if (vo_tune_get("tile_cfg") != 9) return &T64x128;
   }
-  if constexpr (sizeof(TC) == 2) {  // bf16: 64 x 128 in place of the 128 x 128 default (C5 23.68 -> 23.52 ms, C4 and
-                                    // inference shapes unaffected); tile_cfg 9 = the round-5 rule
-    if (vo_tune_get("tile_cfg") != 9) return launch_cfg_r<RAG, TIN, TC, TOUT, 2, 4, 2, 2, 2>(d, st);
+  return &T128x128;
+}
+
+// ---- tile -> instantiation: the one place that says which (tile, types, RAG, S) combinations are compiled
+constexpr int kNoTile = -1000;  // launch_among: p.tile is none of TS
+template <typename TIN, typename TC, typename TOUT, bool RAG, int S, const Tile&... TS>
+static int launch_among(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  int rc = kNoTile;
+  (void)((p.tile == &TS && ((rc = launch_tile<TS, TIN, TC, TOUT, RAG, S>(d, p, st)), true)) || ...);
+  return rc;
+}
+
+#ifdef VO_ABLATIONS
+// lin_kernel: K = 1, bf16 input and compute, Ci = 32 NC (256 / 512 / 1024), Co % BCO == 0 (checked by select_types)
+template <typename TOUT, const Tile& T, int D, int NC>
+static int launch_lin(const vo_conv1d_desc* d, hipStream_t st) {
+  ConvArgs a = conv_args(d, T.bco(), T.bt());
+  a.K = 1; a.dil = 1; a.pad = 0;
+  a.pre_act = VO_ACT_NONE; a.pre_slope = 0.f;
+  a.transposed = a.up_stride = a.up_pad = a.up_cout = a.up_tout = 0;
+  a.lens = nullptr; a.lens_scale = 0;
+  a.cig = d->Ci; a.cog = d->Co;
+  dim3 grid((unsigned)(a.tiles_per_b * d->B), (unsigned)a.co_tiles);
+  hipLaunchKernelGGL((lin_kernel<TOUT, T.NI, T.NJ, T.WCO, T.WT, D, NC>), grid, dim3(T.WCO * T.WT * 64), 0, st, a);
+  VO_RETURN_LAUNCH();
+}
+template <typename TOUT, int NC>
+static int launch_lin_tile(const vo_conv1d_desc* d, const Tile* t, hipStream_t st) {
+  if (t == &LIN_64x64) return launch_lin<TOUT, LIN_64x64, 4, NC>(d, st);
+  if (t == &LIN_128x128) return launch_lin<TOUT, LIN_128x128, 3, NC>(d, st);
+  if (t == &LIN_64x128) return launch_lin<TOUT, LIN_64x128, 4, NC>(d, st);
+  return launch_lin<TOUT, LIN_128x64, 4, NC>(d, st);
+}
+#endif  // VO_ABLATIONS
+
+// RAG: the ragged instantiations of the same tiles (vo_conv1d with lens); SEG tiles: 4-byte compute only, no ragged form
+template <typename TIN, typename TC, typename TOUT, bool RAG = false>
+static int launch_types(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  int rc = kNoTile;
+  if constexpr (sizeof(TC) == 4) rc = launch_among<TIN, TC, TOUT, false, 1, T32x64_seg, T64x64_seg, T32x128_seg, T64x128_seg>(d, p, st);
+  if constexpr (sizeof(TC) == 2)
+    rc = launch_among<TIN, TC, TOUT, RAG, 1, T64x128, T256x128, T128x256, T256x256 VO_AB(
+        A256x256_t1_gl, A256x256_t1_rs, A128x128_t1_gl, A256x256_t1, A64x128_t1)>(d, p, st);
+#ifdef VO_ABLATIONS
+  if constexpr (sizeof(TC) == 2 && sizeof(TIN) == 2)
+    if (p.tile->TPS == 0)
+      return d->Ci == 256 ? launch_lin_tile<TOUT, 8>(d, p.tile, st)
+                          : d->Ci == 512 ? launch_lin_tile<TOUT, 16>(d, p.tile, st) : launch_lin_tile<TOUT, 32>(d, p.tile, st);
+#endif
+  if (rc != kNoTile) return rc;
+  return launch_among<TIN, TC, TOUT, RAG, 1, T32x16, T64x16, T128x16, T128x32, T32x256, T64x256, T64x128_n4w1, T64x64_n4w1,
+                      T64x64, T128x128>(d, p, st);
+}
+
+// strided / grouped: S = 8 compiles all four tiles (only 128 x 32 is selected there), the other strides three
+template <typename TIN, typename TC, typename TOUT, int S>
+static int launch_disc_s(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  if constexpr (S >= 8) return launch_among<TIN, TC, TOUT, false, S, T128x32_n4w2, T32x64, T64x64_n4w1, T128x64>(d, p, st);
+  return launch_among<TIN, TC, TOUT, false, S, T32x64, T64x64_n4w1, T128x64>(d, p, st);
+}
+template <typename TIN, typename TC, typename TOUT>
+static int launch_disc(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  switch (p.S) {
+    case 1: return launch_disc_s<TIN, TC, TOUT, 1>(d, p, st);
+    case 2: return launch_disc_s<TIN, TC, TOUT, 2>(d, p, st);
+    case 3: return launch_disc_s<TIN, TC, TOUT, 3>(d, p, st);
+    case 4: return launch_disc_s<TIN, TC, TOUT, 4>(d, p, st);
+    default: return launch_disc_s<TIN, TC, TOUT, 8>(d, p, st);
   }
-  return launch_cfg_r<RAG, TIN, TC, TOUT, 4, 4, 2, 2, 2>(d, st);                    // 128 x 128
 }
 
-}  // namespace vo
-
-using namespace vo;
-
-int vo_ups_try(const vo_conv1d_desc* d, hipStream_t st, int* handled);  // upsample.hip
-
-extern "C" int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d) {
-  int splits = 1, kcs = 0;
-  if (!d || !splitk_plan(d, &splits, &kcs)) return 0;
-  return (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float);
+static int launch_plan(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  const bool rag = d->lens != nullptr;
+  int rc = kNoTile;
+  if (d->stride > 1 || d->groups > 1)  // discriminator layers: three type triples, no ragged form
+    rc = p.types == FFF ? launch_disc<float, float, float>(d, p, st)
+                        : p.types == BBB ? launch_disc<bf16_t, bf16_t, bf16_t>(d, p, st) : launch_disc<bf16_t, bf16_t, float>(d, p, st);
+  else if (p.role && rag)  // MRF stages: bf16 only, ragged for stage 0 alone
+    rc = launch_among<bf16_t, bf16_t, bf16_t, true, 1, T256x256_mrf0, T256x256_mrf0_rs>(d, p, st);
+  else if (p.role)
+    rc = launch_among<bf16_t, bf16_t, bf16_t, false, 1, T256x256_mrf0, T256x256_mrf0_rs, T128x128_mrf1, T64x256_mrf2, T32x256_mrf3 VO_AB(
+        A128x128_mrf0, A256x256_mrf0_plain, A256x256_mrf0_prio, A256x256_mrf0_t3, A256x256_mrf0_t1, A256x256_mrf0_t1_rs)>(d, p, st);
+  else switch (p.types) {  // ragged: fp32, and bf16 compute with a bf16 output
+    case FXF: rc = launch_types<float, bx3_t, float>(d, p, st); break;
+    case FFF: rc = rag ? launch_types<float, float, float, true>(d, p, st) : launch_types<float, float, float>(d, p, st); break;
+    case BBB: rc = rag ? launch_types<bf16_t, bf16_t, bf16_t, true>(d, p, st) : launch_types<bf16_t, bf16_t, bf16_t>(d, p, st); break;
+    case FBB: rc = rag ? launch_types<float, bf16_t, bf16_t, true>(d, p, st) : launch_types<float, bf16_t, bf16_t>(d, p, st); break;
+    case BBF: rc = launch_types<bf16_t, bf16_t, float>(d, p, st); break;
+    default: rc = launch_types<float, bf16_t, float>(d, p, st);
+  }
+  if (rc == kNoTile) vo_set_error("conv1d: the selected tile is not compiled for type triple %d", p.types);
+  return rc == kNoTile ? VO_ERR_INVALID : rc;
 }
 
-extern "C" int vo_conv1d_last_launch(int32_t* rec, int n) {
-  const int m = rec ? std::max(0, std::min(n, (int)VO_CONV1D_LAUNCH_FIELDS)) : 0;
-  if (m > 0) memcpy(rec, g_last_launch, m * sizeof(int32_t));
-  return m;
-}
+bool vo_ups_takes(const vo_conv1d_desc* d);                  // upsample.hip
+int vo_ups_launch(const vo_conv1d_desc* d, hipStream_t st);  // upsample.hip
 
-extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
-  memset(g_last_launch, 0, sizeof(g_last_launch));
+// The argument checks of vo_conv1d and vo_conv1d_plan; sets p->ups, and p->types and p->role unless p->ups
+static int conv1d_check(const vo_conv1d_desc* d, ConvPlan* p) {
   VO_CHECK_ARG(d != nullptr, "conv1d: null descriptor");
   VO_CHECK_ARG(d->x && d->w && d->y, "conv1d: null tensor pointer");
   VO_CHECK_ARG((d->pre_act != VO_ACT_LRELU || (d->pre_slope >= 0.f && d->pre_slope <= 1.f)) &&
                    (d->post_act != VO_ACT_LRELU || (d->post_slope >= 0.f && d->post_slope <= 1.f)),
                "conv1d: leaky-ReLU slope outside [0, 1]");
   VO_CHECK_ARG(d->B > 0 && d->T_in > 0 && d->T_out > 0 && d->Ci > 0 && d->Co > 0 && d->K > 0,
-               "conv1d: non-positive size (B=%d T_in=%d T_out=%d Ci=%d Co=%d K=%d)", d->B,
-               d->T_in, d->T_out, d->Ci, d->Co, d->K);
+               "conv1d: non-positive size (B=%d T_in=%d T_out=%d Ci=%d Co=%d K=%d)", d->B, d->T_in, d->T_out, d->Ci, d->Co, d->K);
   VO_CHECK_ARG(d->Ci % 8 == 0 && d->ldx % 8 == 0 && d->ldx >= d->Ci,
                "conv1d: Ci (%d) and ldx (%d) must be multiples of 8, ldx >= Ci", d->Ci, d->ldx);
-  VO_CHECK_ARG(d->Co % 4 == 0 && d->ldy % 4 == 0, "conv1d: Co (%d) and ldy (%d) must be multiples of 4",
-               d->Co, d->ldy);
+  VO_CHECK_ARG(d->Co % 4 == 0 && d->ldy % 4 == 0, "conv1d: Co (%d) and ldy (%d) must be multiples of 4", d->Co, d->ldy);
   VO_CHECK_ARG(d->dil >= 1 && (d->K - 1) * d->dil <= HALO_MAX,
                "conv1d: (K-1)*dil = %d exceeds the supported halo %d", (d->K - 1) * d->dil, HALO_MAX);
   VO_CHECK_ARG(d->variant == 0 || (d->variant == 1 && d->Co >= 128) || (d->variant == 2 && d->Co >= 128) ||
@@ -1303,7 +1393,6 @@ extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
   } else {
     VO_CHECK_ARG(d->Co % 16 == 0 || d->Co == 80 || d->Co <= 32, "conv1d: unsupported Co %d", d->Co);
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(const_cast<void*>(stream));
   VO_CHECK_ARG(!d->ymask || (d->y_dtype == VO_BF16 && !d->transposed && !d->bias && !d->res1 && !d->res2 &&
                              d->post_act == VO_ACT_NONE && d->out_scale == 1.f && d->variant == 0 &&
                              d->ymask_slope >= 0.f && d->ymask_slope <= 1.f),
@@ -1324,87 +1413,89 @@ extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
     VO_CHECK_ARG(!d->transposed || uc == 0 || uc == 1 || uc == 4,
                  "conv1d: ups_cfg=%d selects a kernel without a ragged (lens) form", uc);
   }
-  if (d->transposed) {  // narrow upsamplers: the persistent streaming kernel (upsample.hip)
-    int handled = 0;
-    const int rc = vo_ups_try(d, st, &handled);
-    if (handled) return rc;
-  }
+  p->ups = d->transposed && vo_ups_takes(d);  // narrow upsamplers: the persistent streaming kernel (upsample.hip)
+  if (p->ups) return VO_OK;
   const int xi = d->x_dtype, yo = d->y_dtype;
+  p->role = 0;
   if (d->compute_dtype == VO_F32X3) {  // split-bf16 fp32 contractions (vonoma.h)
     VO_CHECK_ARG(xi == VO_F32 && yo == VO_F32 && d->stride <= 1 && d->groups <= 1 && d->variant == 0,
                  "conv1d: VO_F32X3 compute needs fp32 I/O, stride 1, no groups");
-    return launch_types<float, bx3_t, float>(d, st);
+    p->types = FXF;
+    return VO_OK;
   }
   if (d->stride > 1 || d->groups > 1) {  // discriminator layers
     const int g = d->groups > 1 ? d->groups : 1;
     VO_CHECK_ARG(!d->transposed && d->variant == 0, "conv1d: stride/groups exclude transposed and variants");
-    VO_CHECK_ARG(d->Ci % g == 0 && d->Co % g == 0, "conv1d: Ci %d / Co %d not divisible by groups %d", d->Ci,
-                 d->Co, g);
-    if (d->compute_dtype == VO_F32) {
-      VO_CHECK_ARG(xi == VO_F32 && yo == VO_F32, "conv1d: fp32 compute needs fp32 I/O");
-      return launch_disc<float, float, float>(d, st);
+    VO_CHECK_ARG(d->Ci % g == 0 && d->Co % g == 0, "conv1d: Ci %d / Co %d not divisible by groups %d", d->Ci, d->Co, g);
+    if (d->compute_dtype != VO_F32) {
+      VO_CHECK_ARG(d->compute_dtype == VO_BF16 && xi == VO_BF16, "conv1d: strided/grouped bf16 needs bf16 input");
+      p->types = yo == VO_BF16 ? BBB : BBF;
+      return VO_OK;
     }
-    VO_CHECK_ARG(d->compute_dtype == VO_BF16 && xi == VO_BF16, "conv1d: strided/grouped bf16 needs bf16 input");
-    if (yo == VO_BF16) return launch_disc<bf16_t, bf16_t, bf16_t>(d, st);
-    return launch_disc<bf16_t, bf16_t, float>(d, st);
   }
   if (d->compute_dtype == VO_F32) {
     VO_CHECK_ARG(xi == VO_F32 && yo == VO_F32, "conv1d: fp32 compute needs fp32 I/O");
-    if (d->lens) return launch_types<float, float, float, true>(d, st);
-    return launch_types<float, float, float>(d, st);
+    p->types = FFF;
+    return VO_OK;
   }
   VO_CHECK_ARG(d->compute_dtype == VO_BF16, "conv1d: bad compute dtype");
   if (d->lens) {  // the vocoder's forms: bf16 activations (MRF stage 0 in its own role), conv_pre reading an fp32 mel
     VO_CHECK_ARG(yo == VO_BF16 && d->variant <= 1, "conv1d: lens with bf16 compute needs a bf16 output, variant 0 / 1");
-    if (xi == VO_F32) return launch_types<float, bf16_t, bf16_t, true>(d, st);
-    if (d->variant == 0) return launch_types<bf16_t, bf16_t, bf16_t, true>(d, st);
-    const int cc = vo_tune_get("conv_cfg");
-    VO_CHECK_ARG(cc == 0, "conv1d: conv_cfg=%d selects a kernel without a ragged (lens) form", cc);
-    if (d->K >= 5) return launch_cfg_r<true, bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true, true>(d, st);
-    return launch_cfg_r<true, bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true>(d, st);
+    p->types = xi == VO_F32 ? FBB : BBB;
+  } else if ((xi != VO_BF16 && xi != VO_F32) || (yo != VO_BF16 && yo != VO_F32)) {
+    vo_set_error("conv1d: bad dtypes");
+    return VO_ERR_INVALID;
+  } else {
+    p->types = xi == VO_BF16 ? (yo == VO_BF16 ? BBB : BBF) : (yo == VO_BF16 ? FBB : FBF);
   }
-  if (xi == VO_BF16 && yo == VO_BF16) {
-    switch (d->variant) {  // HiFi-GAN MRF stages: own instantiations (same tiles as generic)
-      case 1: {  // C = 256: 256 x 256 tile, 8 waves of 64 co x 128 rows (each weight tap feeds
-                 // twice the rows of the 128 x 128 tile: 0.095/0.151/0.208 -> 0.077/0.125/0.172 ms
-                 // for k = 3/7/11 at B = 32, bit-identical).  conv_cfg 1 = the 128 x 128 tile.
-        // s_setprio(1) around each MFMA cluster: +1-3 % (0.1667 -> 0.1654 ms at k = 11); conv_cfg 2 = without
-        // Round 2: weights by LDS-DMA (GL): 0.084 / 0.134 / 0.171 -> 0.083 / 0.126 / 0.163 ms for
-        // k = 3 / 7 / 11 alone (tools/ab_conv_cfg.py, bit-identical), within noise in the bench step;
-        // conv_cfg 3 = register-staged weights, 4 = GL with 3-tap steps (spills)
-#ifdef VO_ABLATIONS  // measured-and-dropped tiles (A/B builds only: make abl)
-        if (vo_tune_get("conv_cfg") == 1) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 4, 2, 2, 2, 1>(d, st);
-        if (vo_tune_get("conv_cfg") == 2) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1>(d, st);
-        if (vo_tune_get("conv_cfg") == 3) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1>(d, st);
-        if (vo_tune_get("conv_cfg") == 4) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 3, 1, 1, 0, true>(d, st);
-        // one tap per step (k = 3's second 2-tap step re-fetches tap 2 as its padding tap)
-        if (vo_tune_get("conv_cfg") == 7) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 1, 1, 1, 0, true>(d, st);
-        if (vo_tune_get("conv_cfg") == 8) return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 1, 1, 1, 0, true, true>(d, st);
-#endif
-        // Round 2: role-split staging (RS: half the waves issue the weight DMA, half copy the window by
-        // LDS-DMA two chunks ahead; bare step barriers): k = 7 / 11 0.137 / 0.175 -> 0.130 / 0.168 ms,
-        // k = 3 0.084 -> 0.096 (two-step chunks: the weight waves' 8 DMA pieces per step, not the
-        // window, bind) -- k >= 5 only; conv_cfg 5 forces it, 6 disables it (tools/probes/s0_probe.py,
-        // bit-identical)
-        const int cc = vo_tune_get("conv_cfg");
-        // Round 3, measured and dropped (tools/mrf_bench.py --stages 0, conv pairs): 4-wave tiles, two
-        // workgroups per CU (256 co x 128 rows, 1 tap per step, with and without RS; 128 co x 256 rows)
-        // -- 27-45 % slower than the 8-wave 256 x 256 tile at k = 3 / 7 / 11
-        // (EJ, the epilogue's position tiles whose residual / accumulator rows are requested
-        // together: 4 measured within 1 % of 2, 8 spills and runs 10-20 % slower -- kept at 2)
-        if (cc == 5 || (cc != 6 && d->K >= 5))
-          return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true, true>(d, st);
-        return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 8, 4, 2, 2, 1, 1, 0, true>(d, st);
-      }
-      case 2: return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 4, 2, 2, 2, 2>(d, st);
-      case 3: return launch_cfg<bf16_t, bf16_t, bf16_t, 4, 4, 1, 4, 4, 3>(d, st);
-      case 4: return launch_cfg<bf16_t, bf16_t, bf16_t, 2, 4, 1, 4, 4, 4>(d, st);
-      default: return launch_types<bf16_t, bf16_t, bf16_t>(d, st);
-    }
-  }
-  if (xi == VO_F32 && yo == VO_BF16) return launch_types<float, bf16_t, bf16_t>(d, st);
-  if (xi == VO_BF16 && yo == VO_F32) return launch_types<bf16_t, bf16_t, float>(d, st);
-  if (xi == VO_F32 && yo == VO_F32) return launch_types<float, bf16_t, float>(d, st);
-  vo_set_error("conv1d: bad dtypes");
-  return VO_ERR_INVALID;
+  p->role = p->types == BBB ? d->variant : 0;  // HiFi-GAN MRF stages: own instantiations (same tiles as generic)
+  return VO_OK;
+}
+
+// check, select, plan: on VO_OK *p is what vo_conv1d launches
+static int conv1d_plan(const vo_conv1d_desc* d, ConvPlan* p) {
+  const int rc = conv1d_check(d, p);
+  if (rc != VO_OK || p->ups) return rc;
+  p->S = d->stride > 1 ? d->stride : 1;
+  p->tile = d->stride > 1 || d->groups > 1 ? select_disc(d) : p->role ? select_role(d, p->role)
+                                           : select_types(d, kTypeBytes[p->types][0], kTypeBytes[p->types][1]);
+  return p->tile ? plan_tile(d, p) : VO_ERR_INVALID;
+}
+
+}  // namespace vo
+
+using namespace vo;
+
+extern "C" int64_t vo_conv1d_workspace_size(const vo_conv1d_desc* d) {
+  int splits = 1, kcs = 0;
+  if (!d || !splitk_plan(d, &splits, &kcs)) return 0;
+  return (int64_t)splits * d->B * d->T_out * d->Co * (int64_t)sizeof(float);
+}
+
+static int copy_record(const int32_t* src, int32_t* rec, int n) {
+  const int m = rec ? std::max(0, std::min(n, (int)VO_CONV1D_LAUNCH_FIELDS)) : 0;
+  if (m > 0) memcpy(rec, src, m * sizeof(int32_t));
+  return m;
+}
+
+extern "C" int vo_conv1d_last_launch(int32_t* rec, int n) { return copy_record(g_last_launch, rec, n); }
+
+extern "C" int vo_conv1d_plan(const vo_conv1d_desc* d, int32_t* rec, int n) {
+  int32_t r[VO_CONV1D_LAUNCH_FIELDS] = {};
+  ConvPlan p;
+  const int rc = conv1d_plan(d, &p);
+  if (rc == VO_OK) plan_record(d, p, r);
+  copy_record(r, rec, n);
+  return rc;
+}
+
+extern "C" int vo_conv1d(const vo_conv1d_desc* d, void* stream) {
+  memset(g_last_launch, 0, sizeof(g_last_launch));
+  ConvPlan p;
+  const int rc = conv1d_plan(d, &p);
+  if (rc != VO_OK) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(const_cast<void*>(stream));
+  if (p.ups) return vo_ups_launch(d, st);
+  plan_record(d, p, g_last_launch);
+  return launch_plan(d, p, st);
 }

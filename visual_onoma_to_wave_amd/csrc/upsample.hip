@@ -444,47 +444,55 @@ static int launch_ups(const vo_conv1d_desc* d, hipStream_t st) {
   VO_RETURN_LAUNCH();
 }
 
-}  // namespace vo
+// The streaming kernel's shapes among the polyphase ConvTranspose1d descriptors vo_conv1d has validated.
+enum UpsShape { UPS_NONE = 0, UPS_128, UPS_WIDE, UPS_64 };
 
-// Called by vo_conv1d for a polyphase ConvTranspose1d (already validated there).  *handled = 0
-// when the descriptor is not one of the streaming kernel's shapes: the caller then runs the
-// generic tiled conv.  vo_tune("ups_cfg", 1) forces the generic path (A/B).
-int vo_ups_try(const vo_conv1d_desc* d, hipStream_t st, int* handled) {
-  using namespace vo;
-  *handled = 0;
+// Host-only predicate (descriptor fields and knobs, no HIP call): UPS_NONE = the caller runs the generic tiled
+// conv.  vo_tune("ups_cfg", 1) forces the generic path (A/B).
+static UpsShape ups_shape(const vo_conv1d_desc* d) {
+  if (vo_tune_get("ups_cfg") == 1) return UPS_NONE;
+  if (!d->transposed || d->compute_dtype != VO_BF16 || d->x_dtype != VO_BF16 || d->y_dtype != VO_BF16) return UPS_NONE;
+  if (d->res1 || d->res2 || d->post_act != VO_ACT_NONE || d->out_scale != 1.f) return UPS_NONE;
+  if (d->ldx != d->Ci || d->ldy != d->up_cout || d->T_out != d->T_in + 1 || d->T_in < 1) return UPS_NONE;
+  if (d->x_bstride % 8 || d->y_bstride % 8 || (d->stride > 1) || (d->groups > 1)) return UPS_NONE;
+  if (d->Ci == 128 && d->Co == 128 && d->up_cout % 32 == 0) return UPS_128;
+  // wide upsamplers: ups_cfg 4 forces the generic path for these alone
+  if (vo_tune_get("ups_cfg") != 4 && d->Ci == 256 && d->Co % 128 == 0 && d->up_cout % 32 == 0 && d->Co >= 256) return UPS_WIDE;
+  // ups0 (512 -> 256, k16 s8) as 64-column blocks on 4-wave workgroups (one wave per SIMD; its
+  // 16 x-fragment k-steps spill at 8 waves) took 230 us against 145 on the tiled conv
+  // (profiles/r01l/ups_probe_ups0.txt): ups0 stays on the tiled conv.
+  if (d->Ci == 64 && d->Co == 64 && d->up_cout % 16 == 0) return UPS_64;
+  return UPS_NONE;
+}
+
+bool vo_ups_takes(const vo_conv1d_desc* d) { return ups_shape(d) != UPS_NONE; }
+
+// Launches a descriptor vo_ups_takes accepted.
+int vo_ups_launch(const vo_conv1d_desc* d, hipStream_t st) {
   const bool rag = d->lens != nullptr;  // ragged: the shipped dispatch (vo_conv1d rejects ups_cfg != 0)
-  if (vo_tune_get("ups_cfg") == 1) return VO_OK;
-  if (!d->transposed || d->compute_dtype != VO_BF16 || d->x_dtype != VO_BF16 || d->y_dtype != VO_BF16) return VO_OK;
-  if (d->res1 || d->res2 || d->post_act != VO_ACT_NONE || d->out_scale != 1.f) return VO_OK;
-  if (d->ldx != d->Ci || d->ldy != d->up_cout || d->T_out != d->T_in + 1 || d->T_in < 1) return VO_OK;
-  if (d->x_bstride % 8 || d->y_bstride % 8 || (d->stride > 1) || (d->groups > 1)) return VO_OK;
   // unit length (tools/probes/ups_probe.py, B = 32 x 512 frames): CI = 128 NJ 1 / 2 / 4 =
   // 169 / 166 / 146 us (generic tiled conv 225); CI = 64 NJ 2 / 4 / 8 = 127 / 125 / 131 us
   // (generic 182).  ups_cfg 2 / 3 select the other two.
   const int cfg = vo_tune_get("ups_cfg");
-  if (d->Ci == 128 && d->Co == 128 && d->up_cout % 32 == 0) {
-    *handled = 1;
-    if (cfg == 2) return launch_ups<128, 128, 2>(d, st);
-    if (cfg == 3) return launch_ups<128, 128, 1>(d, st);
-    if (rag) return launch_ups<128, 128, 4, true>(d, st);
-    return launch_ups<128, 128, 4>(d, st);
+  switch (ups_shape(d)) {
+    case UPS_128:
+      if (cfg == 2) return launch_ups<128, 128, 2>(d, st);
+      if (cfg == 3) return launch_ups<128, 128, 1>(d, st);
+      if (rag) return launch_ups<128, 128, 4, true>(d, st);
+      return launch_ups<128, 128, 4>(d, st);
+    case UPS_WIDE:
+      if (cfg == 5) return launch_upsw<256, 64, 2>(d, st);
+      if (rag) return launch_upsw<256, 128, 1, 8, true>(d, st);
+      return launch_upsw<256, 128, 1>(d, st);
+    case UPS_64:
+      if (cfg == 2) return launch_ups<64, 64, 2>(d, st);
+      if (cfg == 3) return launch_ups<64, 64, 8>(d, st);
+      if (rag) return launch_ups<64, 64, 4, true>(d, st);
+      return launch_ups<64, 64, 4>(d, st);
+    default:
+      vo_set_error("upsample: not a streaming upsampler shape");
+      return VO_ERR_INVALID;
   }
-  // wide upsamplers: ups_cfg 4 forces the generic path for these alone
-  if (cfg != 4 && d->Ci == 256 && d->Co % 128 == 0 && d->up_cout % 32 == 0 && d->Co >= 256) {
-    *handled = 1;
-    if (cfg == 5) return launch_upsw<256, 64, 2>(d, st);
-    if (rag) return launch_upsw<256, 128, 1, 8, true>(d, st);
-    return launch_upsw<256, 128, 1>(d, st);
-  }
-  // ups0 (512 -> 256, k16 s8) as 64-column blocks on 4-wave workgroups (one wave per SIMD; its
-  // 16 x-fragment k-steps spill at 8 waves) took 230 us against 145 on the tiled conv
-  // (profiles/r01l/ups_probe_ups0.txt): ups0 stays on the tiled conv.
-  if (d->Ci == 64 && d->Co == 64 && d->up_cout % 16 == 0) {
-    *handled = 1;
-    if (cfg == 2) return launch_ups<64, 64, 2>(d, st);
-    if (cfg == 3) return launch_ups<64, 64, 8>(d, st);
-    if (rag) return launch_ups<64, 64, 4, true>(d, st);
-    return launch_ups<64, 64, 4>(d, st);
-  }
-  return VO_OK;
 }
+
+}  // namespace vo

@@ -78,26 +78,13 @@ def _check_lens(lens, lens_scale, B, ref, name):
 
 # ----------------------------------------------------------------------------- conv1d
 
-def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_dtype=None,
-           pre_act=ACT_NONE, pre_slope=0.0, post_act=ACT_NONE, post_slope=0.0, res1=None,
-           res2=None, out_scale=1.0, compute_dtype=torch.bfloat16, transposed=None, variant=0,
-           tag=None, stride=1, groups=1, ymask=None, ymask_slope=0.0, lens=None, lens_scale=1):
-    """Channels-last conv: x (B, T_in, Ci) -> y (B, T_out, Co).
-
-    ``w_packed``: [K][Co][Ci] in ``compute_dtype`` (see pack_conv_weight).
-    ``transposed``: None or dict(stride=s, pad=p, cout=C_out) for the polyphase
-    ConvTranspose1d; then Co = s*C_out, K = 2, pad = 1 and y is (B, s*T_in, C_out).
-    ``stride`` / ``groups``: strided and grouped convs (HiFi-GAN discriminators); grouped
-    weights are packed dense with zeros outside the diagonal blocks (pack_conv_weight groups=).
-    ``ymask`` (the output's shape and strides, bf16): each output stored as
-    round(round(v) * (ymask > 0 ? 1 : ymask_slope)) -- an input gradient put through the leaky-ReLU
-    backward of the layer whose output ymask is (bit for bit vo_lrelu_mask on the stored output).
-    ``lens`` (int32 (B,) on the device) / ``lens_scale``: ragged batch -- utterance b is the tensor of its first
-    clamp(lens[b] * lens_scale, 0, T_in) rows: rows past it read as zero (x, res1, res2) and are not written
-    (include/vonoma.h, "per-utterance lengths"; same-length convs and the polyphase form only).  The profiling
-    timer's FLOPs and bytes of a ragged call are still those of the padded shape: a true count would need the
-    lengths on the host.
-    """
+def _conv1d_desc(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_dtype=None,
+                 pre_act=ACT_NONE, pre_slope=0.0, post_act=ACT_NONE, post_slope=0.0, res1=None,
+                 res2=None, out_scale=1.0, compute_dtype=torch.bfloat16, transposed=None, variant=0,
+                 stride=1, groups=1, ymask=None, ymask_slope=0.0, lens=None, lens_scale=1):
+    """The vo_conv1d_desc of a ``conv1d`` call (its keyword arguments and defaults), shape checks and output
+    allocation included.  Returns (d, x, out, ws_bytes): ws_bytes > 0 = the split-reduction scratch the call wants
+    (d.workspace is left for the caller to set)."""
     if x.dim() == 2:
         x = x.unsqueeze(0)
     B, T_in, ldx = x.shape
@@ -161,25 +148,48 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
     if lens is not None:
         d.lens_scale = _check_lens(lens, lens_scale, B, x, "conv1d")
         d.lens = lens.data_ptr()
-    ws = None
     plain = (transposed is None and stride <= 1 and groups <= 1 and lens is None)
     deep_bf16 = (compute_dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and bias is None and res1 is None and
                  res2 is None and ymask is None and pre_act == ACT_NONE and post_act == ACT_NONE and out_scale == 1.0 and
                  Co <= 256 and Ci * K >= 2048 and B * T_rows >= 8192)
+    ws_bytes = 0
     if plain and ((storage_dtype(compute_dtype) == torch.float32 and T_rows <= 16) or deep_bf16):
         # split-reduction scratch: the short fp32 convs, the deep bf16 convs into <= 256 channels
-        # (stream-ordered: freed after enqueue)
-        nb = _lib.lib().vo_conv1d_workspace_size(ctypes.byref(d))
-        if nb > 0:
-            ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), nb
+        ws_bytes = int(_lib.lib().vo_conv1d_workspace_size(ctypes.byref(d)))
+    return d, x, out, ws_bytes
+
+
+def conv1d(x, w_packed, bias, *, tag=None, **kw):
+    """Channels-last conv: x (B, T_in, Ci) -> y (B, T_out, Co).  Keyword arguments (defaults in _conv1d_desc):
+    Co, K, dil=1, pad=0, T_out, out, out_dtype, pre_act, pre_slope, post_act, post_slope, res1, res2, out_scale=1.0,
+    compute_dtype=torch.bfloat16, transposed, variant=0, stride=1, groups=1, ymask, ymask_slope, lens, lens_scale=1;
+    ``tag`` names the call for the profiling timer.
+
+    ``w_packed``: [K][Co][Ci] in ``compute_dtype`` (see pack_conv_weight).
+    ``transposed``: None or dict(stride=s, pad=p, cout=C_out) for the polyphase
+    ConvTranspose1d; then Co = s*C_out, K = 2, pad = 1 and y is (B, s*T_in, C_out).
+    ``stride`` / ``groups``: strided and grouped convs (HiFi-GAN discriminators); grouped
+    weights are packed dense with zeros outside the diagonal blocks (pack_conv_weight groups=).
+    ``ymask`` (the output's shape and strides, bf16): each output stored as
+    round(round(v) * (ymask > 0 ? 1 : ymask_slope)) -- an input gradient put through the leaky-ReLU
+    backward of the layer whose output ymask is (bit for bit vo_lrelu_mask on the stored output).
+    ``lens`` (int32 (B,) on the device) / ``lens_scale``: ragged batch -- utterance b is the tensor of its first
+    clamp(lens[b] * lens_scale, 0, T_in) rows: rows past it read as zero (x, res1, res2) and are not written
+    (include/vonoma.h, "per-utterance lengths"; same-length convs and the polyphase form only).  The profiling
+    timer's FLOPs and bytes of a ragged call are still those of the padded shape: a true count would need the
+    lengths on the host.
+    """
+    d, x, out, ws_bytes = _conv1d_desc(x, w_packed, bias, **kw)
+    if ws_bytes > 0:  # stream-ordered: freed after enqueue
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws_bytes
     timer = profiling.active()
     ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
     _lib.check(_lib.lib().vo_conv1d(ctypes.byref(d), _stream(x)), "vo_conv1d")
     if ev is not None:
-        esz = x.element_size()
-        flops = 2.0 * B * T_rows * Co * Ci * K / groups
-        nbytes = (B * T_in * Ci * esz + out.numel() * out.element_size() +
+        res1, res2 = kw.get("res1"), kw.get("res2")
+        flops = 2.0 * d.B * d.T_out * d.Co * d.Ci * d.K / kw.get("groups", 1)
+        nbytes = (d.B * d.T_in * d.Ci * x.element_size() + out.numel() * out.element_size() +
                   (res1.numel() * res1.element_size() if res1 is not None else 0) +
                   (res2.numel() * res2.element_size() if res2 is not None else 0) +
                   w_packed.numel() * w_packed.element_size())
@@ -189,6 +199,18 @@ def conv1d(x, w_packed, bias, *, Co, K, dil=1, pad=0, T_out=None, out=None, out_
 
 LAUNCH_FIELDS = ("BCO", "BT", "S", "SEG", "nice", "splits", "sizeof_in", "sizeof_compute", "sizeof_out", "ROLE",
                  "compute_dtype", "NI", "WCO")
+
+
+def conv1d_plan(x, w_packed, bias, *, tag=None, **kw):
+    """The launch record ``conv1d`` with the same arguments would leave (a dict over LAUNCH_FIELDS), without
+    launching anything: the same descriptor, workspace decision included, through vo_conv1d_plan -- the dispatcher's
+    host side alone.  All zeros for a call the streaming upsampler takes; raises where ``conv1d`` would."""
+    d, x, _, ws_bytes = _conv1d_desc(x, w_packed, bias, **kw)
+    if ws_bytes > 0:  # never dereferenced: the plan only asks whether a workspace of that size is set
+        d.workspace, d.workspace_bytes = d.y, ws_bytes
+    rec = (ctypes.c_int32 * len(LAUNCH_FIELDS))()
+    _lib.check(_lib.lib().vo_conv1d_plan(ctypes.byref(d), rec, len(LAUNCH_FIELDS)), "vo_conv1d_plan")
+    return dict(zip(LAUNCH_FIELDS, (int(v) for v in rec)))
 
 
 def conv1d_last_launch():
