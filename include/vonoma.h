@@ -221,6 +221,10 @@ int vo_layernorm_bwd_drop(const void* x, int x_dtype, const void* res, int res_d
  * Scaled dot-product attention with key padding, H heads of d_k = D/H, over the fused
  * qkv activations (B, L, 3D) (columns [q | k | v], head h at h*d_k) -> out (B, L, D)
  * (head-concat columns h*d_k + d).  Keys t >= lens[b] are masked (-inf before softmax).
+ * lens contract, for the forward, the backward and their _lse forms alike: utterance b has
+ * clamp(lens[b], 0, L) keys (a length past L masks nothing inside [0, L)); lens = NULL means L
+ * keys everywhere; an utterance with no key has zero output rows and lse = +inf, and its
+ * gradients dQ / dK / dV are zero.
  * Replaces: MultiHeadAttention split/permute + ScaledDotProductAttention
  * (scripts/transformer/SubLayers.py:39-53, scripts/transformer/Modules.py:14-25).  The
  * probabilities are never materialised (the reference returns them but no caller uses

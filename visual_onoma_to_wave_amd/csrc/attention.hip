@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(256) attention_kernel(const TC* __restrict__ q
   const int q0 = (lid - bh * nq) * 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, g = lane >> 4, lk = g * 8;
-  const int len = lens ? lens[b] : L;
+  const int len = min(lens ? lens[b] : L, L);  // rows past L are staged as zeros: they must stay masked
   const int64_t row_stride = 3 * (int64_t)D;
   const TC* base = qkv + (int64_t)b * L * row_stride;
 
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) attention_kernel(const TC* __restrict__ q
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m_run[r] = -INFINITY; l_run[r] = 0.f; }
 
-  const int n_tiles = (min(len, L) + KT - 1) / KT;
+  const int n_tiles = (len + KT - 1) / KT;
   for (int kt = 0; kt < n_tiles; ++kt) {
     const int key0 = kt * KT;
     // stage K (row-major) and V (transposed): 64 keys x 128 dk = 1024 vectors of 8
