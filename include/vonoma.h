@@ -408,6 +408,13 @@ int vo_resblockk_lens(const void* x, const void* const* w1, const float* const* 
 /* output rows per tile of vo_resblockk's kernel for K (952 / 904 for K = 7 / 11; 0: no kernel) -- the edge shapes
  * of its tests */
 int vo_resblockk_tile_rows(int K);
+/* output rows per tile of the kernel that vo_resblock_pair (frag != 0: vo_resblock_pair_frag) / vo_resblock3 would
+ * launch now for a dense call of that shape, the current vo_tune knobs included; 0 for a shape the entry refuses.
+ * Host only: they run the entry's dispatch without a launch, make no HIP call and read no memory but dil[0..2].
+ * C = 32 pair: 512 - (K - 1); vo_resblock3: 200 / 488 at C = 128 / 64, 104 at C = 32 with dilations (1, 3, 5), else
+ * 232.  The edge shapes of the entries' tests.  Additive: VO_ABI_VERSION unchanged. */
+int vo_resblock_pair_tile_rows(int C, int K, int dil, int frag);
+int vo_resblock3_tile_rows(int C, const int* dil);
 
 /* (B, C, T) -> (B, T, ldy) with channels C..ldy-1 zero-filled; fp32 in, dtype out. */
 int vo_transpose_bct(const float* x, int B, int C, int T, void* y, int y_dtype, int ldy,

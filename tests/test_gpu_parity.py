@@ -408,11 +408,37 @@ def test_attention_vs_oracle(B, L, lens, dt, tol, cfg):
     assert rel_l2(out.float().cpu(), ref) < tol
 
 
+# Tile edges are asked of the library when a test runs (vo_resblock3_tile_rows / vo_resblock_pair_tile_rows), so they
+# follow a retiling: a length is an int, or m BT + add with BT the output rows per tile of the kernel that the
+# dispatch picks for the named shape under the named knob value.  Each such case keeps the id of today's length.
+def _r3(C, m=1, add=0, cfg=0, dils=(1, 3, 5)):
+    return ("rb3_cfg", cfg, lambda ops: ops.resblock3_tile_rows(C, dils), m, add)
+
+
+def _pr(C, k, d, m=1, add=0, cfg=0):
+    return ("pair_cfg", cfg, lambda ops: ops.resblock_pair_tile_rows(C, k, d), m, add)
+
+
+def _length(T):
+    if isinstance(T, int):
+        return T
+    from visual_onoma_to_wave_amd import _lib, ops
+    knob, cfg, query, m, add = T
+    _lib.lib().vo_tune(knob.encode(), cfg)
+    try:
+        bt = query(ops)
+    finally:
+        _lib.lib().vo_tune(knob.encode(), 0)
+    assert bt > 0
+    return m * bt + add
+
+
 def _resblock3_case(C, T, with_acc, cfg, dils):
     """vo_resblock3 under rb3_cfg `cfg` against the torch fp32 ResBlock, and against three vo_resblock_pair
     launches (same bf16 intermediates up to summation order)."""
     import torch.nn.functional as F
     from visual_onoma_to_wave_amd import ops
+    T = _length(T)
     g = torch.Generator().manual_seed(C * 7 + T)
     B, k = 2, 3
     x = torch.randn(B, T, C, generator=g).to(torch.bfloat16)
@@ -451,14 +477,27 @@ def _resblock3_case(C, T, with_acc, cfg, dils):
     assert rel_l2(out.float().cpu(), chain.float().cpu()) < 3e-3
 
 
-@pytest.mark.parametrize("C,T", [(32, 1000), (64, 777), (128, 300), (32, 5), (64, 1), (128, 13), (128, 232),
-                                 (128, 233), (32, 488 * 3 + 7), (64, 131072), (32, 65536), (128, 32768),
-                                 # register-resident frames: 104 (C = 32) / 72 (C = 64) output rows per tile
-                                 (32, 104), (32, 105), (32, 24), (64, 72), (64, 73), (64, 16), (64, 72 * 5 - 1),
-                                 # wave-owned planes (resblock_pb3.hip): 200 (C = 128) / 488 (C = 64) output rows per tile
-                                 (128, 200), (128, 201), (128, 200 * 4 + 3), (64, 488), (64, 489), (64, 488 * 3 + 5),
-                                 # the C = 32 LDS-frame kernel's own edge (256-row frames: 232 output rows per tile)
-                                 (32, 232), (32, 233)])
+@pytest.mark.parametrize("C,T", [(32, 1000), (64, 777), (128, 300), (32, 5), (64, 1), (128, 13),
+                                 # edges of earlier tilings (232-row frames at C = 128, 488-row ones at C = 32): interior
+                                 # lengths of today's kernels
+                                 (128, 232), (128, 233), (32, 488 * 3 + 7),
+                                 (64, 131072), (32, 65536), (128, 32768),
+                                 # register-resident frames at C = 32 (today 104 output rows per tile): BT, BT + 1
+                                 pytest.param(32, _r3(32), id="32-104"), pytest.param(32, _r3(32, 1, 1), id="32-105"),
+                                 (32, 24),
+                                 # the 72-row edges of the C = 64 register frames, a kernel of the A/B library only:
+                                 # interior lengths of the shipped plane kernel
+                                 (64, 72), (64, 73), (64, 16), (64, 72 * 5 - 1),
+                                 # wave-owned planes (resblock_pb3.hip; today 200 (C = 128) / 488 (C = 64) output rows
+                                 # per tile): BT, BT + 1, 4 BT + 3 / 3 BT + 5
+                                 pytest.param(128, _r3(128), id="128-200"), pytest.param(128, _r3(128, 1, 1), id="128-201"),
+                                 pytest.param(128, _r3(128, 4, 3), id="128-803"),
+                                 pytest.param(64, _r3(64), id="64-488"), pytest.param(64, _r3(64, 1, 1), id="64-489"),
+                                 pytest.param(64, _r3(64, 3, 5), id="64-1469"),
+                                 # the C = 32 LDS-frame kernel's own edge (rb3_cfg 80; today 256-row frames, 232 output
+                                 # rows per tile): BT, BT + 1
+                                 pytest.param(32, _r3(32, cfg=80), id="32-232"),
+                                 pytest.param(32, _r3(32, 1, 1, cfg=80), id="32-233")])
 @pytest.mark.parametrize("with_acc", [True, False])
 # cfg 0: the shipped dispatch (C = 32: register-resident frames; C = 64 / 128: wave-owned planes).  80 (any
 # rb3_cfg != 0): the LDS-frame kernels -- at C = 32 in either library; at C = 64 / 128 only in the A/B library
@@ -466,16 +505,19 @@ def _resblock3_case(C, T, with_acc, cfg, dils):
 @pytest.mark.parametrize("cfg", [0, 80])
 def test_fused_resblock3_vs_torch_fp32(C, T, with_acc, cfg):
     """vo_resblock3 (a whole k = 3 ResBlock, dilations 1/3/5, in one launch) against the torch fp32
-    ResBlock at tile edges (frame 232 / 488 valid rows), T = 1, and multi-tile persistent runs;
+    ResBlock at tile edges (asked of the library), T = 1, and multi-tile persistent runs;
     and against three vo_resblock_pair launches (same bf16 intermediates up to summation order)."""
     _resblock3_case(C, T, with_acc, cfg, (1, 3, 5))
 
 
 @pytest.mark.parametrize("with_acc", [True, False])
-@pytest.mark.parametrize("T", [1, 232, 233, 232 * 3 + 7])
+@pytest.mark.parametrize("T", [1, pytest.param(_r3(32, dils=(1, 2, 4)), id="232"),
+                               pytest.param(_r3(32, 1, 1, dils=(1, 2, 4)), id="233"),
+                               pytest.param(_r3(32, 3, 7, dils=(1, 2, 4)), id="703")])
 def test_fused_resblock3_c32_lds_frames_by_default(T, with_acc):
     """C = 32 off the (1, 3, 5) fast path: dilations (1, 2, 4) (halo 10 <= 12) run the LDS-frame kernel with no knob
-    set -- the only shipped code for them -- at its tile edges (232 output rows per 256-row frame)."""
+    set -- the only shipped code for them -- at its tile edges BT, BT + 1 and 3 BT + 7 (today 232 output rows per
+    256-row frame)."""
     _resblock3_case(32, T, with_acc, 0, (1, 2, 4))
 
 
@@ -490,6 +532,7 @@ def _pair_case(C, T, k, d, with_acc, cfg):
     """vo_resblock_pair under pair_cfg `cfg` against torch fp32."""
     import torch.nn.functional as F
     from visual_onoma_to_wave_amd import _lib, ops
+    T = _length(T)
     g = torch.Generator().manual_seed(C * T + k)
     B = 2
     x = torch.randn(B, T, C, generator=g).to(torch.bfloat16)
@@ -520,26 +563,32 @@ def _pair_case(C, T, k, d, with_acc, cfg):
 @pytest.mark.parametrize("cfg", _PAIR_CFGS)
 @pytest.mark.parametrize("with_acc", [True, False])
 @pytest.mark.parametrize("C,T,k,d", [(32, 1000, 11, 5), (64, 777, 7, 3), (32, 5, 3, 1), (64, 1, 11, 1),
-                                     (32, 246 * 3, 11, 5), (64, 4096, 3, 5), (64, 502, 11, 3),
+                                     # (3 x 246: three tiles of an earlier C = 32 tiling; an interior length today)
+                                     (32, 246 * 3, 11, 5), (64, 4096, 3, 5),
+                                     pytest.param(64, _pr(64, 11, 3), 11, 3, id="64-502-11-3"),
                                      # several tiles per persistent workgroup (pipelined window/weights)
                                      (32, 131072, 11, 5), (32, 65536, 3, 1), (64, 65536, 7, 3),
                                      (64, 65536, 3, 1), (64, 40000, 11, 5),
-                                     # C = 64 k = 7 / 11 plane kernel: one tile (502 / 506 valid rows), +1, two
-                                     (64, 503, 11, 5), (64, 13, 7, 1), (64, 1013, 7, 5), (64, 506, 7, 3),
+                                     # C = 64 k = 7 / 11 plane kernel: one tile (today 502 / 506 valid rows), + 1,
+                                     # two + 1
+                                     pytest.param(64, _pr(64, 11, 5, 1, 1), 11, 5, id="64-503-11-5"), (64, 13, 7, 1),
+                                     pytest.param(64, _pr(64, 7, 5, 2, 1), 7, 5, id="64-1013-7-5"),
+                                     pytest.param(64, _pr(64, 7, 3), 7, 3, id="64-506-7-3"),
                                      (128, 300, 3, 1), (128, 20000, 3, 5),
-                                     # C = 128 k = 7 / 11: T = 1, one tile, tile edges (246 / 250 valid
-                                     # rows), utterances crossing inside a workgroup's run, every dilation
-                                     (128, 1, 7, 3), (128, 1, 11, 5), (128, 13, 11, 1), (128, 246, 11, 5),
-                                     (128, 247, 11, 3), (128, 250, 7, 1), (128, 501, 7, 5), (128, 5000, 11, 3),
+                                     # C = 128 k = 7 / 11: T = 1, one tile, tile edges (today 246 / 250 valid
+                                     # rows: BT, BT + 1, BT, 2 BT + 1), utterances crossing inside a workgroup's
+                                     # run, every dilation
+                                     (128, 1, 7, 3), (128, 1, 11, 5), (128, 13, 11, 1),
+                                     pytest.param(128, _pr(128, 11, 5), 11, 5, id="128-246-11-5"),
+                                     pytest.param(128, _pr(128, 11, 3, 1, 1), 11, 3, id="128-247-11-3"),
+                                     pytest.param(128, _pr(128, 7, 1), 7, 1, id="128-250-7-1"),
+                                     pytest.param(128, _pr(128, 7, 5, 2, 1), 7, 5, id="128-501-7-5"),
+                                     (128, 5000, 11, 3),
                                      (128, 32768, 11, 5), (128, 32768, 7, 3), (128, 20011, 11, 1)])
 def test_fused_resblock_pair_vs_torch_fp32(C, T, k, d, with_acc, cfg):
     """vo_resblock_pair (c1 -> lrelu -> c2 + residual, MRF accumulate) at tile edges vs torch fp32,
     for the shipped dispatch and the LDS-tile kernels behind pair_cfg 93 / 111."""
     _pair_case(C, T, k, d, with_acc, cfg)
-
-
-# the generic LDS-tile pair: R1 rows per tile, BT = R1 - (k - 1) of them valid
-_GENERIC_R1 = {128: 256, 64: 512}
 
 
 @pytest.mark.parametrize("with_acc", [True, False])
@@ -549,14 +598,18 @@ _GENERIC_R1 = {128: 256, 64: 512}
 @pytest.mark.parametrize("C", [64, 128])
 def test_fused_resblock_pair_generic_k(C, k, edge, d, with_acc):
     """k = 5 / 9 at C = 64 / 128: shapes only the generic LDS-tile kernels serve (no knob set), at T = 1, one full
-    tile, one row more, and two tiles and three rows."""
-    bt = _GENERIC_R1[C] - (k - 1)
+    tile, one row more, and two tiles and three rows (the tile's rows asked of the library)."""
+    from visual_onoma_to_wave_amd import ops
+    bt = ops.resblock_pair_tile_rows(C, k, d)
+    assert bt > 0
     T = {"one": 1, "bt": bt, "bt+1": bt + 1, "2bt+3": 2 * bt + 3}[edge]
     _pair_case(C, T, k, d, with_acc, 0)
 
 
 @pytest.mark.parametrize("with_acc,scale", [(True, 1.0 / 3), (False, 1.0), (True, 0.3)])
-@pytest.mark.parametrize("T,k,d", [(32768, 11, 5), (20011, 7, 3), (777, 11, 1), (1, 7, 5), (250, 7, 1)])
+@pytest.mark.parametrize("T,k,d", [(32768, 11, 5), (20011, 7, 3), (777, 11, 1), (1, 7, 5),
+                                   # one tile of the C = 128 kernel (today 250 rows)
+                                   pytest.param(_pr(128, 7, 1), 7, 1, id="250-7-1")])
 @pytest.mark.parametrize("C", [128, 64])
 def test_pair_plane_frag_bit_identical(C, T, k, d, with_acc, scale):
     """vo_resblock_pair_frag (weights in the fragment order of vo_pack_frag, each load one contiguous
@@ -565,6 +618,7 @@ def test_pair_plane_frag_bit_identical(C, T, k, d, with_acc, scale):
     not a bf16 value)."""
     from visual_onoma_to_wave_amd import ops
     B = 3
+    T = _length(T)
     g = torch.Generator(device="cuda").manual_seed(T + 10 * k + d)
     x = torch.randn(B, T, C, device="cuda", generator=g).to(torch.bfloat16)
     acc = torch.randn(B, T, C, device="cuda", generator=g).to(torch.bfloat16)

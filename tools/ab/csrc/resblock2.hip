@@ -467,13 +467,14 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair2_kernel(Pair2Args a)
 }
 
 template <int C, int WC, int WT, int NJ, int K, bool GL, int TG, bool VD = true, int PIPE = 0>
-static int pair2_launch(Pair2Args a, int B, hipStream_t st) {
+static int pair2_launch(Pair2Args a, int B, MrfTo st) {
   constexpr int NW = WC * WT;
   constexpr int R1 = WT * 16 * NJ;
   constexpr int H2 = (K - 1) / 2;
   constexpr int WRMAX = R1 + 2 * PAIR2_DMAX * H2;
   constexpr int WR = WRMAX > R1 + 16 ? WRMAX : R1 + 16;
   constexpr int BT = R1 - 2 * H2;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   const size_t lds = ((size_t)WR * C + 2 * (size_t)TG * C * C) * sizeof(bf16_t) + 2 * C * sizeof(float) + 16;
@@ -493,7 +494,7 @@ using namespace vo;
 // C = 128 is reached only under pair_cfg 30 / 31.
 int vo_pair2_try(const MrfPairCall& c, int cfg, int* handled) {
   const int B = c.B, C = c.C, K = c.K;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (!((C == 64 || C == 128) && (K == 7 || K == 11) && c.dil >= 1 && c.dil <= PAIR2_DMAX)) return VO_OK;
   Pair2Args a;

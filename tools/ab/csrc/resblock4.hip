@@ -389,12 +389,13 @@ __global__ void __launch_bounds__(256, 2) mrf_pair3_kernel(Pair3Args a) {
 }
 
 template <int C, int NJ, int K, bool RESW, int TG>
-static int pair3_launch(Pair3Args a, int B, hipStream_t st) {
+static int pair3_launch(Pair3Args a, int B, MrfTo st) {
   constexpr int R1 = 4 * 16 * NJ;
   constexpr int H2 = (K - 1) / 2;
   constexpr int WRMAX = R1 + 2 * PAIR3_DMAX * H2;
   constexpr int WR = ((WRMAX > R1 + 16 ? WRMAX : R1 + 16) + 63) / 64 * 64;
   constexpr int BT = R1 - 2 * H2;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   const size_t wel = RESW ? 2 * (size_t)K * C * C : 2 * (size_t)TG * C * C;
@@ -414,7 +415,7 @@ using namespace vo;
 // (C = 32 / 64, K = 7 / 11, dilation <= 5) for the selected pair_cfg.
 int vo_pair3_try(const MrfPairCall& c, int cfg, int* handled) {
   const int B = c.B, C = c.C, K = c.K;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (!((C == 64 || C == 32) && (K == 7 || K == 11) && c.dil >= 1 && c.dil <= PAIR3_DMAX)) return VO_OK;
   Pair3Args a;

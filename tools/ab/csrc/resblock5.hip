@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(512, 1) mrf_wave_kernel(WaveArgs a) {
 }
 
 template <int MODE, int K, int D1, int NJ>
-static int wave_launch(WaveArgs a, int B, hipStream_t st) {
+static int wave_launch(WaveArgs a, int B, MrfTo st) {
   constexpr int C = 32, NW = 8;
   constexpr int NCV = MODE == 0 ? 6 : 2;
   constexpr int H2 = (K - 1) / 2;
@@ -267,6 +267,7 @@ static int wave_launch(WaveArgs a, int B, hipStream_t st) {
   constexpr int F = 16 * NJ;
   constexpr int RR = F + 2 * HP;
   constexpr int BT = F - 2 * (MODE == 0 ? 12 : H2);
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   const size_t lds = (size_t)NCV * K * C * C * sizeof(bf16_t) + NCV * C * sizeof(float) +
@@ -285,7 +286,7 @@ using namespace vo;
 // k = 3 ResBlock at C = 32, dilations (1, 3, 5) (vo_resblock3's shape); *handled = 0 otherwise
 int vo_rb3_wave_try(const MrfBlock3Call& c, int cfg, int* handled) {
   const int B = c.B;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (c.C != 32 || c.dil[0] != 1 || c.dil[1] != 3 || c.dil[2] != 5) return VO_OK;
   WaveArgs a;
@@ -304,7 +305,7 @@ int vo_rb3_wave_try(const MrfBlock3Call& c, int cfg, int* handled) {
 // k = 7 / 11 pair at C = 32, dilation 1 / 3 / 5
 int vo_pair_wave_try(const MrfPairCall& c, int cfg, int* handled) {
   const int B = c.B, K = c.K, dil = c.dil;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (c.C != 32 || !(K == 7 || K == 11) || !(dil == 1 || dil == 3 || dil == 5)) return VO_OK;
   WaveArgs a;

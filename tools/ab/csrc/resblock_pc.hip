@@ -463,10 +463,11 @@ __global__ void __launch_bounds__(512, 2) mrf_pair_pc_kernel(PcArgs a) {
 }
 
 template <int K, bool HAS_ACC, int MODE, int ABL, int VAR = 0>
-static int pc_launch(PcArgs a, int B, hipStream_t st) {
+static int pc_launch(PcArgs a, int B, MrfTo st) {
   constexpr int R1 = 256;
   constexpr int h2 = (K - 1) / 2;
   constexpr int BT = R1 - 2 * h2;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   constexpr size_t lds = 4 * 320 * 64 + 2 * 4 * 128 * 64 + 2 * 128 * 4;
@@ -488,7 +489,7 @@ using namespace vo;
 int vo_pair_pc_try(const MrfPairCall& c, int* handled) {
   const int B = c.B, K = c.K;
   const void* acc = c.acc;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (c.C != 128 || (K != 7 && K != 11) || c.dil < 1 || c.dil * (K - 1) > 64 || !(c.out_scale > 0.f) ||
       (int64_t)c.T * c.C * 2 >= (int64_t)1 << 31)

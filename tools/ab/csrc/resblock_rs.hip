@@ -354,10 +354,11 @@ __global__ void __launch_bounds__(NWV * 64, NWV / 4) mrf_pair_rs_kernel(RsArgs a
 }
 
 template <int K, bool HAS_ACC, int JW, int PF, int D, int NWV = 4, bool STAMP = false>
-static int rs_launch(RsArgs a, int B, hipStream_t st) {
+static int rs_launch(RsArgs a, int B, MrfTo st) {
   using Gm = RsGeom<JW, NWV>;
   constexpr int h2 = (K - 1) / 2;
   constexpr int BT = Gm::R1 - 2 * h2;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   auto kern = mrf_pair_rs_kernel<K, HAS_ACC, JW, PF, D, NWV, STAMP>;
@@ -377,7 +378,7 @@ using namespace vo;
 int vo_pair_rs_try(const MrfPairCall& c, int cfg, int* handled) {
   const int B = c.B, K = c.K;
   const void* acc = c.acc;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (c.C != 128 || (K != 7 && K != 11) || c.dil < 1 || c.dil * (K - 1) > 64 || !(c.out_scale > 0.f) ||
       (int64_t)B * c.T * c.C * 2 >= ((int64_t)1 << 31))  // 32-bit buffer offsets

@@ -123,6 +123,8 @@ _SIGNATURES = {
     "vo_resblockk_lens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
     "vo_resblockk_tile_rows": (c_int, [c_int]),
+    "vo_resblock_pair_tile_rows": (c_int, [c_int, c_int, c_int, c_int]),
+    "vo_resblock3_tile_rows": (c_int, [c_int, c_void_p]),
     "vo_conv1d": (c_int, [ctypes.POINTER(Conv1dDesc), c_void_p]),
     "vo_conv1d_workspace_size": (ctypes.c_int64, [ctypes.POINTER(Conv1dDesc)]),
     "vo_conv1d_last_launch": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int]),

@@ -137,13 +137,29 @@ inline int mrf_acc_mode(const void* acc, float out_scale) {
   return (invb == inv && std::isfinite(inv) && inv * out_scale == 1.0f) ? 2 : 1;
 }
 
+// Where a launch function sends its kernel: a stream -- or, for the host-only tile-rows queries
+// (vo_resblock_pair_tile_rows, vo_resblock3_tile_rows), nowhere: with `rows` set, the launch function the dispatch
+// reaches writes its output rows per tile there and returns before any HIP call (mrf_tile_rows_query).  The queries
+// run the entries' own dispatch this way, so what they report is the constant the launch computes its grid from.
+struct MrfTo {
+  hipStream_t st;
+  int* rows;
+  MrfTo(hipStream_t s = nullptr, int* r = nullptr) : st(s), rows(r) {}
+  operator hipStream_t() const { return st; }
+};
+// first statement of a launch function once it knows its tile: true = a query, answered
+inline bool mrf_tile_rows_query(const MrfTo& to, int rows) {
+  if (to.rows) *to.rows = rows;
+  return to.rows != nullptr;
+}
+
 // One vo_resblock_pair / vo_resblock3 call, as the entry points hand it to the kernels' vo_*_try functions
 struct MrfPairCall {
   const void* x; const void* w1; const float* b1; const void* w2; const float* b2;
   void* y; const void* acc;
   int B, T, C, K, dil;
   float slope, out_scale;
-  hipStream_t st;
+  MrfTo st;
   const int32_t* lens; int lens_scale;  // ragged batch (vo_*_lens entries); nullptr: dense
 };
 struct MrfBlock3Call {
@@ -152,7 +168,7 @@ struct MrfBlock3Call {
   void* y; const void* acc;
   int B, T, C;
   float slope, out_scale;
-  hipStream_t st;
+  MrfTo st;
   const int32_t* lens; int lens_scale;
 };
 struct MrfBlockKCall {  // one vo_resblockk / vo_resblockk_lens call: a whole k = 7 / 11 block
@@ -178,6 +194,8 @@ static void mrf_pair_args(A& a, const MrfPairCall& c) {
 
 // The argument checks of vo_resblock_pair and (frag) vo_resblock_pair_frag (resblock.hip); the error names the entry
 int vo_pair_check(const vo::MrfPairCall& c, bool frag);
+// vo_resblock_pair_frag's check and dispatch (resblock_rw.hip)
+int vo_pair_frag_entry(const vo::MrfPairCall& c);
 
 // The kernels behind vo_resblock_pair / vo_resblock3: each launches and sets *handled = 1 when it covers the shape
 // (and the knob value `cfg`), else leaves *handled = 0 for the next one.

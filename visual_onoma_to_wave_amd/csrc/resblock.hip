@@ -582,11 +582,12 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
 
 template <int C, int WC, int WT, int NJ, bool RES, int TG, int ABL = 0, int PRIO = 0, bool SB = false, bool GL = false,
           bool IP = false, bool HP = false, bool LATE = HP, bool VD = true, bool RAG = false>
-static int pair_launch(PairArgs a, int B, hipStream_t st) {
+static int pair_launch(PairArgs a, int B, MrfTo st) {
   constexpr int NW = WC * WT;
   constexpr int R1 = WT * 16 * NJ;
   const int h1 = a.dil * (a.K - 1) / 2, h2 = (a.K - 1) / 2;
   const int BT = R1 - 2 * h2;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   const size_t wtaps = RES ? 2 * (size_t)a.K : (HP ? 1 : 2 * (size_t)TG);  // HP: two half-tap buffers
@@ -626,8 +627,7 @@ int vo_pair_check(const MrfPairCall& c, bool frag) {
 // vo_resblock_pair (lens == nullptr) and vo_resblock_pair_lens
 static int resblock_pair_entry(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y,
                                const void* acc, int B, int T, int C, int K, int dil, float slope, float out_scale,
-                               void* stream, const int32_t* lens, int lens_scale) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+                               MrfTo st, const int32_t* lens, int lens_scale) {
   const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, st, lens, lens_scale};
   if (const int rc = vo_pair_check(c, false)) return rc;
   PairArgs a;
@@ -775,12 +775,32 @@ static int resblock_pair_entry(const void* x, const void* w1, const float* b1, c
 extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                                 void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
                                 float out_scale, void* stream) {
-  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, stream, nullptr, 0);
+  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale,
+                             reinterpret_cast<hipStream_t>(stream), nullptr, 0);
 }
 
 extern "C" int vo_resblock_pair_lens(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                                      void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
                                      float out_scale, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(lens && lens_scale >= 1, "resblock_pair_lens: lens is null or lens_scale %d < 1", lens_scale);
-  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, stream, lens, lens_scale);
+  return resblock_pair_entry(x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale,
+                             reinterpret_cast<hipStream_t>(stream), lens, lens_scale);
+}
+
+// Host-only: the dense dispatch above (vo_resblock_pair's, or with frag vo_resblock_pair_frag's) run as a tile-rows
+// query (MrfTo, mrf_common.h) -- the launch function it reaches reports its tile instead of launching.  The operand
+// pointers are placeholders that the dispatch compares and copies but never reads through.
+extern "C" int vo_resblock_pair_tile_rows(int C, int K, int dil, int frag) {
+  static const char in = 0;
+  static char out = 0;
+  const float* const fb = reinterpret_cast<const float*>(&in);
+  int rows = 0;
+  const MrfTo to(nullptr, &rows);
+  if (frag) {
+    const MrfPairCall c{&in, &in, fb, &in, fb, &out, nullptr, 1, 1, C, K, dil, 0.1f, 1.0f, to};
+    return vo_pair_frag_entry(c) == VO_OK ? rows : 0;
+  }
+  if (resblock_pair_entry(&in, &in, fb, &in, fb, &out, nullptr, 1, 1, C, K, dil, 0.1f, 1.0f, to, nullptr, 0) != VO_OK)
+    return 0;
+  return rows;
 }

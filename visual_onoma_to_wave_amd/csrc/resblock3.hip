@@ -536,10 +536,11 @@ __global__ void __launch_bounds__(WC * WT * 64, WC * WT == 4 ? 2 : 1) mrf_rb3_ke
 
 template <int C, int WC, int WT, int NJ, bool RESW, int SPLIT = 1, int NBUF = 2, bool VD = true, int TPG = 1,
           bool PIPE = false>
-static int rb3_launch(Rb3Args a, int B, hipStream_t st) {
+static int rb3_launch(Rb3Args a, int B, MrfTo st) {
   constexpr int NW = WC * WT;
   constexpr int F = WT * 16 * NJ;
   constexpr int BT = F - 2 * RB3_HALO;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   constexpr int RR = F + 2 * RB3_HPC;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
@@ -559,7 +560,7 @@ using namespace vo;
 // vo_resblock3 (lens == nullptr) and vo_resblock3_lens
 static int resblock3_entry(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                            const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
-                           float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
+                           float slope, float out_scale, MrfTo st, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && dil && y, "resblock3: null pointer");
   VO_CHECK_ARG(C == 32 || C == 64 || C == 128, "resblock3: C=%d unsupported (32, 64 or 128)", C);
   VO_CHECK_ARG(B > 0 && T > 0, "resblock3: empty");
@@ -580,7 +581,6 @@ static int resblock3_entry(const void* x, const void* const* w1, const float* co
   a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
   a.T = T; a.slope = slope; a.out_scale = out_scale;
   a.tiles_per_b = a.ntiles = 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const MrfBlock3Call c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st, lens, lens_scale};
   int handled = 0;
   // Shipped dispatch (measured on MI355X at B = 32 with the MRF accumulator, tools/ab_rb3.py, tools/mrf_bench.py):
@@ -661,12 +661,29 @@ static int resblock3_entry(const void* x, const void* const* w1, const float* co
 extern "C" int vo_resblock3(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                             const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
                             float slope, float out_scale, void* stream) {
-  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, stream, nullptr, 0);
+  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale,
+                         reinterpret_cast<hipStream_t>(stream), nullptr, 0);
 }
 
 extern "C" int vo_resblock3_lens(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                                  const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
                                  float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(lens && lens_scale >= 1, "resblock3_lens: lens is null or lens_scale %d < 1", lens_scale);
-  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, stream, lens, lens_scale);
+  return resblock3_entry(x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale,
+                         reinterpret_cast<hipStream_t>(stream), lens, lens_scale);
+}
+
+// Host-only: vo_resblock3's dense dispatch run as a tile-rows query (MrfTo, mrf_common.h) -- the launch function it
+// reaches reports its tile instead of launching.  The operand pointers are placeholders that the dispatch compares
+// and copies but never reads through; dil is read.
+extern "C" int vo_resblock3_tile_rows(int C, const int* dil) {
+  static const char in = 0;
+  static char out = 0;
+  const float* const fb = reinterpret_cast<const float*>(&in);
+  const void* const w[3] = {&in, &in, &in};
+  const float* const b[3] = {fb, fb, fb};
+  int rows = 0;
+  if (resblock3_entry(&in, w, b, w, b, dil, &out, nullptr, 1, 1, C, 0.1f, 1.0f, MrfTo(nullptr, &rows), nullptr, 0) != VO_OK)
+    return 0;
+  return rows;
 }

@@ -406,8 +406,9 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
 }
 
 template <int C, int ACC, bool RAG = false>
-static int pb3_launch(Pb3Args a, int B, hipStream_t st) {
+static int pb3_launch(Pb3Args a, int B, MrfTo st) {
   constexpr int BT = pb_f(C) - 2 * PB_HALO;
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   return mrf_launch(mrf_pb3_kernel<C, ACC, false, RAG>, a, a.ntiles, 256, pb_lds(C), false, st);

@@ -651,8 +651,9 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rr3w_kernel(RrArgs a) {
 }
 
 template <int C, int NB, int NWV, bool PF, bool RM = true>
-static int rr3w_launch(RrArgs a, int B, hipStream_t st) {
+static int rr3w_launch(RrArgs a, int B, MrfTo st) {
   constexpr int OR = 32 * NB - 2 * RR_HALO;
+  if (mrf_tile_rows_query(st, OR)) return VO_OK;
   constexpr size_t lds = (size_t)(6 * 3 * (C / 16) * (C / 32) + 6 * (C / 32)) * 1024;
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
@@ -662,8 +663,9 @@ static int rr3w_launch(RrArgs a, int B, hipStream_t st) {
 #endif  // VO_ABLATIONS
 
 template <int C, int NB, int NWV, bool PF, bool PA = false, bool PL = false, bool RAG = false>
-static int rr3_launch(RrArgs a, int B, hipStream_t st) {
+static int rr3_launch(RrArgs a, int B, MrfTo st) {
   constexpr int OR = 16 * NB - 2 * RR_HALO;
+  if (mrf_tile_rows_query(st, OR)) return VO_OK;
   constexpr size_t lds = (size_t)6 * 3 * (C / 32) * (C / 16) * 1024 + 6 * C * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
@@ -920,8 +922,9 @@ __global__ void __launch_bounds__(NWV * 64, 1) mrf_rrp_kernel(RrpArgs a) {
 }
 
 template <int C, int K, int D, int NB, int NWV, bool RT = false>
-static int rrp_launch(RrpArgs a, int B, hipStream_t st) {
+static int rrp_launch(RrpArgs a, int B, MrfTo st) {
   constexpr int OR = 16 * NB - 2 * ((K - 1) / 2) * (D + 1);
+  if (mrf_tile_rows_query(st, OR)) return VO_OK;
   constexpr size_t lds = (size_t)2 * (RT ? K - 1 : K) * (C / 32) * (C / 16) * 1024 + (RT ? 0 : 2 * C * sizeof(float));
   static_assert(lds <= 160 * 1024, "LDS");
   a.tiles_per_b = (a.T + OR - 1) / OR;
@@ -930,7 +933,7 @@ static int rrp_launch(RrpArgs a, int B, hipStream_t st) {
 }
 
 template <int C, int K, int NB, int NWV, bool RT = false>
-static int rrp_launch_d(RrpArgs a, int B, int dil, hipStream_t st) {
+static int rrp_launch_d(RrpArgs a, int B, int dil, MrfTo st) {
   if (dil == 1) return rrp_launch<C, K, 1, NB, NWV, RT>(a, B, st);
   if (dil == 3) return rrp_launch<C, K, 3, NB, NWV, RT>(a, B, st);
   return rrp_launch<C, K, 5, NB, NWV, RT>(a, B, st);
@@ -945,7 +948,7 @@ using namespace vo;
 // leaves the call to the LDS-frame kernel
 int vo_rb3_rr_try(const MrfBlock3Call& c, int cfg, int* handled) {
   const int B = c.B, C = c.C;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (!(C == 32 || C == 64) || c.dil[0] != 1 || c.dil[1] != 3 || c.dil[2] != 5) return VO_OK;
   if ((int64_t)c.T * C * 2 >= (int64_t)1 << 31) return VO_OK;  // buffer ranges are 32-bit
@@ -1000,7 +1003,7 @@ int vo_rb3_rr_try(const MrfBlock3Call& c, int cfg, int* handled) {
 // (DESIGN.md section 3, round 4): reached under pair_cfg 90-100 only
 int vo_pair_rr_try(const MrfPairCall& c, int cfg, int* handled) {
   const int B = c.B, C = c.C, K = c.K, dil = c.dil;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   if (!(C == 32 || C == 64) || !(K == 7 || K == 11) || !(dil == 1 || dil == 3 || dil == 5)) return VO_OK;
   if ((int64_t)c.T * C * 2 >= (int64_t)1 << 31) return VO_OK;

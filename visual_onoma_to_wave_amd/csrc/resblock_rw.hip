@@ -389,8 +389,9 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
 }
 
 template <int C, int K, int ACC, bool FR>
-static int prw_launch(PrwArgs a, int B, hipStream_t st) {
+static int prw_launch(PrwArgs a, int B, MrfTo st) {
   constexpr int BT = rw_r1(C) - 2 * ((K - 1) / 2);
+  if (mrf_tile_rows_query(st, BT)) return VO_OK;
   a.tiles_per_b = (a.T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;
   if (a.rg.lens) return mrf_launch(mrf_prw_kernel<C, K, ACC, FR, false, true>, a, a.ntiles, 256, rw_lds(C), false, st);
@@ -408,7 +409,7 @@ using namespace vo;
 // accumulator): C = 64 k = 11 355 us vs 426, k = 7 275 vs 286 (mean over d = 1 / 3 / 5).
 int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
   const int B = c.B, C = c.C, K = c.K;
-  hipStream_t st = c.st;
+  const MrfTo st = c.st;
   *handled = 0;
   // (C = 32 instantiates too, but measured 4-9 % slower than the LDS-tile kernel at B = 32: 210-258 us vs
   // 197-242 for k = 7 / 11, tools/mrf_bench.py --stages 3 -- one 32-channel plane per wave leaves 16
@@ -465,13 +466,19 @@ extern "C" int vo_pack_frag(const void* src, void* dst, int C, int K, void* stre
   VO_RETURN_LAUNCH();
 }
 
-extern "C" int vo_resblock_pair_frag(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
-                                     void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
-                                     float out_scale, void* stream) {
-  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, reinterpret_cast<hipStream_t>(stream)};
+// vo_resblock_pair_frag / vo_resblock_pair_frag_lens, and the frag form of vo_resblock_pair_tile_rows (resblock.hip)
+int vo_pair_frag_entry(const MrfPairCall& c) {
   if (const int rc = vo_pair_check(c, true)) return rc;
   int handled = 0;
   return vo_pair_rw_try(c, 0, 1, &handled);
+}
+
+extern "C" int vo_resblock_pair_frag(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
+                                     void* y, const void* acc, int B, int T, int C, int K, int dil, float slope,
+                                     float out_scale, void* stream) {
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale,
+                      MrfTo(reinterpret_cast<hipStream_t>(stream))};
+  return vo_pair_frag_entry(c);
 }
 
 extern "C" int vo_resblock_pair_frag_lens(const void* x, const void* w1, const float* b1, const void* w2,
@@ -479,11 +486,9 @@ extern "C" int vo_resblock_pair_frag_lens(const void* x, const void* w1, const f
                                           float slope, float out_scale, void* stream, const int32_t* lens,
                                           int lens_scale) {
   VO_CHECK_ARG(lens && lens_scale >= 1, "resblock_pair_frag_lens: lens is null or lens_scale %d < 1", lens_scale);
-  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale, reinterpret_cast<hipStream_t>(stream),
-                      lens, lens_scale};
-  if (const int rc = vo_pair_check(c, true)) return rc;
-  int handled = 0;
-  return vo_pair_rw_try(c, 0, 1, &handled);
+  const MrfPairCall c{x, w1, b1, w2, b2, y, acc, B, T, C, K, dil, slope, out_scale,
+                      MrfTo(reinterpret_cast<hipStream_t>(stream)), lens, lens_scale};
+  return vo_pair_frag_entry(c);
 }
 
 #ifdef VO_PRW_STAMPS

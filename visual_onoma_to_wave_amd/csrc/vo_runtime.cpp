@@ -97,7 +97,7 @@ static const char* const kSymbols[] = {
     "vo_resblock_pair_frag", "vo_pack_frag", "vo_attention_lse", "vo_attention_bwd_lse", "vo_dropout",
     "vo_conv1d_last_launch", "vo_conv1d_plan",
     "vo_resblock_pair_lens", "vo_resblock_pair_frag_lens", "vo_resblock3_lens", "vo_conv_post_lens",
-    "vo_resblockk", "vo_resblockk_lens", "vo_resblockk_tile_rows",
+    "vo_resblockk", "vo_resblockk_lens", "vo_resblockk_tile_rows", "vo_resblock_pair_tile_rows", "vo_resblock3_tile_rows",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

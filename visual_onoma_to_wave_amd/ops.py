@@ -695,6 +695,21 @@ def resblock_k_tile_rows(K):
     return int(_lib.lib().vo_resblockk_tile_rows(int(K)))
 
 
+def resblock_pair_tile_rows(C, K, dil=1, frag=False):
+    """Output rows per tile of the kernel ``resblock_pair`` (``frag``: with pack_frag weights) would launch now for
+    a dense call of that shape, vo_tune knobs included (0: a refused shape) -- its tests' edge shapes.  Host only."""
+    return int(_lib.lib().vo_resblock_pair_tile_rows(int(C), int(K), int(dil), 1 if frag else 0))
+
+
+def resblock3_tile_rows(C, dils=(1, 3, 5)):
+    """Output rows per tile of the kernel ``resblock3`` would launch now for a dense call with these three dilations,
+    vo_tune knobs included (0: a refused shape) -- its tests' edge shapes.  Host only."""
+    if len(dils) != 3:
+        raise ValueError("resblock3_tile_rows: three dilations")
+    dil = (ctypes.c_int * 3)(*[int(d) for d in dils])
+    return int(_lib.lib().vo_resblock3_tile_rows(int(C), dil))
+
+
 def resblock_k(x, w1s, b1s, w2s, b2s, K, dils, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None, lens=None,
                lens_scale=1):
     """A whole K = 7 / 11 ResBlock1 (three (c1_d, c2) pairs) in one launch (vo_resblockk):
