@@ -284,7 +284,7 @@ static int wave_launch(WaveArgs a, int B, MrfTo st) {
 using namespace vo;
 
 // k = 3 ResBlock at C = 32, dilations (1, 3, 5) (vo_resblock3's shape); *handled = 0 otherwise
-int vo_rb3_wave_try(const MrfBlock3Call& c, int cfg, int* handled) {
+int vo_rb3_wave_try(const MrfBlockCall& c, int cfg, int* handled) {
   const int B = c.B;
   const MrfTo st = c.st;
   *handled = 0;

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "vo_common.h"
 
@@ -112,6 +113,46 @@ struct MrfWalk {
   }
 };
 
+// A workgroup's tile run: its contiguous share [tile, tile_end) of the walk's total() tiles (all work: see MrfWalk),
+// for the kernels that stage the next tile's window while they compute the current one.
+//   MrfRun<RAG, BT> run(a.tiles_per_b, a.ntiles, T, a.rg);
+//   if (run.empty()) return;  // uniform per workgroup: the early exit is safe
+//   run.start();              // ... run.at(run.tile): stage the first window ...
+//   for (; run.more(); run.advance()) {
+//     const MrfTile ti = run.enter();  // this tile; run.at(run.succ()): its successor, whose window is prefetched
+//   }                                  // (the last tile's is itself: the prefetch loads unconditionally)
+// RAG: the walk's cursor only moves forward, so the run keeps one tile (nx) and at() answers with it whatever it is
+// asked: the first tile after start(), each tile's successor after enter().
+// The constructor's arguments are bound by reference and the dense tiles are computed from the kernel argument
+// tiles_per_b itself (tpb): with copies the same code came out in another order, and the plane kernels, at 496-510
+// of 512 registers, gained registers and instructions.
+template <bool RAG, int BT>
+struct MrfRun {
+  MrfWalk<RAG> walk;
+  int tile, tile_end;
+  MrfTile nx;
+  const int& tpb;
+  __device__ __forceinline__ MrfRun(const int& tiles_per_b, const int& ntiles, const int& T, const MrfLens& rg)
+      : walk(tiles_per_b, ntiles, T, BT, rg), tpb(tiles_per_b) {
+    const int ntl = RAG ? walk.total() : ntiles;
+    const int G = gridDim.x;
+    tile = (int)(((int64_t)blockIdx.x * ntl) / G);
+    tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
+  }
+  __device__ __forceinline__ bool empty() const { return tile >= tile_end; }
+  __device__ __forceinline__ void start() { if constexpr (RAG) nx = walk.at(tile); }
+  __device__ __forceinline__ bool more() const { return tile < tile_end; }
+  __device__ __forceinline__ void advance() { ++tile; }
+  __device__ __forceinline__ int succ() const { return tile + 1 < tile_end ? tile + 1 : tile; }
+  __device__ __forceinline__ MrfTile dense(int tl) const { const int b = tl / tpb; return MrfTile{b, (tl - b * tpb) * BT, walk.T}; }
+  __device__ __forceinline__ MrfTile at(int tl) { if constexpr (RAG) return nx; else return dense(tl); }
+  __device__ __forceinline__ MrfTile enter() {
+    const MrfTile ti = RAG ? nx : dense(tile);
+    if constexpr (RAG) nx = walk.at(succ());
+    return ti;
+  }
+};
+
 // ---------------------------------------------------------------- host side: launch and dispatch
 // Every MRF kernel is persistent: a workgroup walks its share of `work` items (tiles, or groups of NWV tiles in
 // the kernels whose waves take a tile each).  The grid is min(CUs * per_cu, work) with per_cu = 1, or, with
@@ -138,7 +179,7 @@ inline int mrf_acc_mode(const void* acc, float out_scale) {
 }
 
 // Where a launch function sends its kernel: a stream -- or, for the host-only tile-rows queries
-// (vo_resblock_pair_tile_rows, vo_resblock3_tile_rows), nowhere: with `rows` set, the launch function the dispatch
+// (vo_resblock_pair_tile_rows, vo_resblock3_tile_rows, vo_resblockk_tile_rows), nowhere: with `rows` set, the launch function the dispatch
 // reaches writes its output rows per tile there and returns before any HIP call (mrf_tile_rows_query).  The queries
 // run the entries' own dispatch this way, so what they report is the constant the launch computes its grid from.
 struct MrfTo {
@@ -153,7 +194,7 @@ inline bool mrf_tile_rows_query(const MrfTo& to, int rows) {
   return to.rows != nullptr;
 }
 
-// One vo_resblock_pair / vo_resblock3 call, as the entry points hand it to the kernels' vo_*_try functions
+// One vo_resblock_pair / vo_resblock3 / vo_resblockk call, as the entry points hand it to the kernels' vo_*_try functions
 struct MrfPairCall {
   const void* x; const void* w1; const float* b1; const void* w2; const float* b2;
   void* y; const void* acc;
@@ -162,22 +203,13 @@ struct MrfPairCall {
   MrfTo st;
   const int32_t* lens; int lens_scale;  // ragged batch (vo_*_lens entries); nullptr: dense
 };
-struct MrfBlock3Call {
-  const void* x; const void* const* w1; const float* const* b1; const void* const* w2; const float* const* b2;
-  const int* dil;
-  void* y; const void* acc;
-  int B, T, C;
-  float slope, out_scale;
-  MrfTo st;
-  const int32_t* lens; int lens_scale;
-};
-struct MrfBlockKCall {  // one vo_resblockk / vo_resblockk_lens call: a whole k = 7 / 11 block
+struct MrfBlockCall {  // a whole block of three (c1, c2) stages: vo_resblock3 (K = 3), vo_resblockk (K = 7 / 11)
   const void* x; const void* const* w1; const float* const* b1; const void* const* w2; const float* const* b2;
   const int* dil;
   void* y; const void* acc;
   int B, T, C, K;
   float slope, out_scale;
-  hipStream_t st;
+  MrfTo st;
   const int32_t* lens; int lens_scale;
 };
 
@@ -189,6 +221,28 @@ static void mrf_pair_args(A& a, const MrfPairCall& c) {
   a.T = c.T; a.dil = c.dil; a.slope = c.slope; a.out_scale = c.out_scale;
   a.tiles_per_b = a.ntiles = 0;
 }
+// the fields every plane block kernel's argument struct has (conv v = 2 s + ph: c1 / c2 of stage s), from the call
+template <class A>
+static void mrf_block_args(A& a, const MrfBlockCall& c) {
+  a.x = (const bf16_t*)c.x;
+  for (int s = 0; s < 3; ++s) {
+    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.b[2 * s] = c.b1[s];
+    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.b[2 * s + 1] = c.b2[s];
+  }
+  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
+  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
+  a.tiles_per_b = a.ntiles = 0;
+  a.rg = MrfLens{c.lens, c.lens_scale, c.B};
+}
+
+// f(std::integral_constant<int, ACC>) for the call's accumulator mode (mrf_acc_mode): the kernels take it as a
+// template argument
+template <class F>
+static int mrf_with_acc(int accm, F f) {
+  if (accm == 2) return f(std::integral_constant<int, 2>{});
+  if (accm == 1) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 0>{});
+}
 
 }  // namespace vo
 
@@ -196,13 +250,15 @@ static void mrf_pair_args(A& a, const MrfPairCall& c) {
 int vo_pair_check(const vo::MrfPairCall& c, bool frag);
 // vo_resblock_pair_frag's check and dispatch (resblock_rw.hip)
 int vo_pair_frag_entry(const vo::MrfPairCall& c);
+// The argument checks vo_resblock3 and vo_resblockk share (resblock3.hip); the error names the entry
+int vo_block_check(const vo::MrfBlockCall& c, const char* entry);
 
 // The kernels behind vo_resblock_pair / vo_resblock3: each launches and sets *handled = 1 when it covers the shape
 // (and the knob value `cfg`), else leaves *handled = 0 for the next one.
 int vo_pair_rw_try(const vo::MrfPairCall& c, int cfg, int frag, int* handled);  // resblock_rw.hip
-int vo_rb3_pb_try(const vo::MrfBlock3Call& c, int* handled);                     // resblock_pb3.hip
-int vo_rb3_rr_try(const vo::MrfBlock3Call& c, int cfg, int* handled);            // resblock_rr.hip
-int vo_rbk_pb_try(const vo::MrfBlockKCall& c, int* handled);                     // resblock_pbk.hip (vo_resblockk)
+int vo_rb3_pb_try(const vo::MrfBlockCall& c, int* handled);                      // resblock_pb3.hip
+int vo_rb3_rr_try(const vo::MrfBlockCall& c, int cfg, int* handled);             // resblock_rr.hip
+int vo_rbk_pb_try(const vo::MrfBlockCall& c, int* handled);                      // resblock_pbk.hip (vo_resblockk)
 #ifdef VO_ABLATIONS  // the A/B library's kernels (resblock_rr.hip and tools/ab/csrc)
 int vo_pair_rr_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rr.hip
 int vo_pair2_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resblock2.hip
@@ -210,5 +266,5 @@ int vo_pair3_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resbl
 int vo_pair_pc_try(const vo::MrfPairCall& c, int* handled);             // resblock_pc.hip
 int vo_pair_rs_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rs.hip
 int vo_pair_wave_try(const vo::MrfPairCall& c, int cfg, int* handled);  // resblock5.hip
-int vo_rb3_wave_try(const vo::MrfBlock3Call& c, int cfg, int* handled);  // resblock5.hip
+int vo_rb3_wave_try(const vo::MrfBlockCall& c, int cfg, int* handled);  // resblock5.hip
 #endif

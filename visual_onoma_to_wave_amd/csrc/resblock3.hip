@@ -557,21 +557,28 @@ static int rb3_launch(Rb3Args a, int B, MrfTo st) {
 
 using namespace vo;
 
+int vo_block_check(const MrfBlockCall& c, const char* entry) {
+  VO_CHECK_ARG(c.x && c.w1 && c.b1 && c.w2 && c.b2 && c.dil && c.y, "%s: null pointer", entry);
+  VO_CHECK_ARG(c.C == 32 || c.C == 64 || c.C == 128, "%s: C=%d unsupported (32, 64 or 128)", entry, c.C);
+  VO_CHECK_ARG(c.B > 0 && c.T > 0, "%s: empty", entry);
+  VO_CHECK_ARG(c.slope >= 0.f && c.slope <= 1.f, "%s: slope %g outside [0, 1]", entry, c.slope);
+  VO_CHECK_ARG(c.y != c.x, "%s: y must not alias x (neighbouring tiles re-read x)", entry);
+  VO_CHECK_ARG(c.acc == nullptr || c.acc == c.y || c.acc != c.x, "%s: acc must not alias x", entry);
+  for (int s = 0; s < 3; ++s)
+    VO_CHECK_ARG(c.w1[s] && c.b1[s] && c.w2[s] && c.b2[s], "%s: null weight of stage %d", entry, s);
+  return VO_OK;
+}
+
 // vo_resblock3 (lens == nullptr) and vo_resblock3_lens
 static int resblock3_entry(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                            const float* const* b2, const int* dil, void* y, const void* acc, int B, int T, int C,
                            float slope, float out_scale, MrfTo st, const int32_t* lens, int lens_scale) {
-  VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && dil && y, "resblock3: null pointer");
-  VO_CHECK_ARG(C == 32 || C == 64 || C == 128, "resblock3: C=%d unsupported (32, 64 or 128)", C);
-  VO_CHECK_ARG(B > 0 && T > 0, "resblock3: empty");
-  VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "resblock3: slope %g outside [0, 1]", slope);
-  VO_CHECK_ARG(y != x, "resblock3: y must not alias x (neighbouring tiles re-read x)");
-  VO_CHECK_ARG(acc == nullptr || acc == y || acc != x, "resblock3: acc must not alias x");
+  const MrfBlockCall c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, 3, slope, out_scale, st, lens, lens_scale};
+  if (const int rc = vo_block_check(c, "resblock3")) return rc;
   Rb3Args a;
   a.x = (const bf16_t*)x;
   int halo = 0;
   for (int s = 0; s < 3; ++s) {
-    VO_CHECK_ARG(w1[s] && b1[s] && w2[s] && b2[s], "resblock3: null weight of stage %d", s);
     VO_CHECK_ARG(dil[s] >= 1 && dil[s] <= RB3_HPC, "resblock3: dilation %d outside [1, %d]", dil[s], RB3_HPC);
     a.w1[s] = (const bf16_t*)w1[s]; a.b1[s] = b1[s]; a.w2[s] = (const bf16_t*)w2[s]; a.b2[s] = b2[s];
     a.dil[s] = dil[s];
@@ -581,7 +588,6 @@ static int resblock3_entry(const void* x, const void* const* w1, const float* co
   a.y = (bf16_t*)y; a.acc = (const bf16_t*)acc;
   a.T = T; a.slope = slope; a.out_scale = out_scale;
   a.tiles_per_b = a.ntiles = 0;
-  const MrfBlock3Call c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, slope, out_scale, st, lens, lens_scale};
   int handled = 0;
   // Shipped dispatch (measured on MI355X at B = 32 with the MRF accumulator, tools/ab_rb3.py, tools/mrf_bench.py):
   //   C = 64 / 128: wave-owned output planes (resblock_pb3.hip), for every shape accepted above;

@@ -19,15 +19,15 @@
 //     into the window for the next c1;
 //   * every conv runs on the whole F-row frame; the valid rows shrink by the halos (1+1+3+1+5+1 = 12 per
 //     side), so a tile yields F - 24 output rows (F = 256 at C = 128: 9 % extra MFMA work; F = 512 at C = 64);
-//   * LDS rows [plane][row][32 ch], 16-byte chunk q of row r at q ^ ((r >> 1) & 3) (rw_off): the B-fragment
-//     reads at any row shift, the T1 / window stores of the epilogues and the window staging (odd plane
-//     stride) are bank-conflict free.
+//   * LDS rows [plane][row][32 ch] in the swizzle of plane_off (mrf_plane.h): the B-fragment reads at any row
+//     shift, the T1 / window stores of the epilogues and the window staging (odd plane stride) are bank-conflict
+//     free.
 // Weights: [K][C_out][C_in] bf16 packs (vo_pack_weight); biases fp32.
 
 #include <algorithm>
 #include <cmath>
 
-#include "mrf_common.h"
+#include "mrf_plane.h"
 
 #ifndef VO_PB3_PK
 #define VO_PB3_PK 0  // epilogue leaky ReLU with one packed multiply per value pair (A/B)
@@ -64,8 +64,6 @@ constexpr int pb_nj(int C) { return C == 128 ? VO_PB3_NJ128 : VO_PB3_NJ64; }
 constexpr int pb_f(int C) { return 16 * pb_nj(C) * (4 / pb_np(C)); }  // frame rows per tile
 constexpr int pb_rp(int C) { return pb_f(C) + 2 * PB_HP + 1; }    // LDS rows per plane (odd)
 constexpr size_t pb_lds(int C) { return (size_t)2 * pb_np(C) * pb_rp(C) * 32 * sizeof(bf16_t) + 6 * C * sizeof(float); }
-
-__device__ __forceinline__ int pb_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
 // RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
 // T does in the dense form (buffer ranges, zeroed frame rows, stored rows); T stays the row stride between utterances
@@ -105,21 +103,12 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     }
   };
 
-  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
-  const int ntl = RAG ? walk.total() : a.ntiles;
-  const int G = gridDim.x;
-  int tile = (int)(((int64_t)blockIdx.x * ntl) / G);
-  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
-  if (tile >= tile_end) return;  // uniform per workgroup
-  MrfTile nx = RAG ? walk.at(tile) : MrfTile{0, 0, T};  // RAG: the tile whose window load_win fetches (the first, then each tile's successor)
+  MrfRun<RAG, BT> run(a.tiles_per_b, a.ntiles, T, a.rg);
+  if (run.empty()) return;  // uniform per workgroup: the early exit is safe
+  run.start();
 
   for (int i = tid; i < 6 * C; i += 256) sbias[i] = a.b[i / C][i % C];
-  // pad rows (read only by taps of frame rows whose outputs the halo discards): zeros, never NaN
-  for (int i = tid; i < 2 * NP * (2 * PB_HP + 1) * 4; i += 256) {
-    const int q = i & 3, r0 = (i >> 2) % (2 * PB_HP + 1), pb = (i >> 2) / (2 * PB_HP + 1);
-    const int r = r0 < PB_HP ? r0 : F + r0;
-    *reinterpret_cast<u32x4*>(win + pb * PL + pb_off(r, q)) = u32x4{0u, 0u, 0u, 0u};
-  }
+  plane_zero_pads<2 * NP, PB_HP, F, PL>(win, tid);
 
   // ---- A fragments (as resblock_rw.hip): lane l holds W[tap][co][ci], co = 32pw + 8(lr>>2) + 4t + (lr&3),
   // ci = 32s + 8lg .. +7; accumulator register i of co tile t is then channel 32pw + 8lg + 4t + i.
@@ -136,28 +125,25 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     const int lo = aoff + t * 4 * C * 2 + s * 64;
     A[uu % 3][s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw[v], lo, k * (C * C * 2), 0));
   };
-  auto utt = [&](const bf16_t* p, int b, int Tv) __attribute__((always_inline)) {  // rows [0, Tv) of one utterance of a (B, T, C) tensor: rows outside read 0
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
-  };
-  // op i of n spread over the steps [lo, lo + span) of a phase: does step jj carry it?
-  auto at = [](int jj, int lo, int span, int n, int i) __attribute__((always_inline)) { return jj == lo + i * span / n; };
+  auto utt = [&](const bf16_t* p, int b, int Tv) __attribute__((always_inline)) { return plane_utt<C>(p, b, T, Tv); };
+  auto at = [](int jj, int lo, int span, int n, int i) __attribute__((always_inline)) { return plane_at(jj, lo, span, n, i); };
 
   // ---- window staging: vector v = tid + 256 slot = (frame row xr + RPS slot, 16-byte column xc)
   const int xr = tid / VPR, xc = tid % VPR;
-  const int xl = (xc >> 2) * PL + pb_off(xr + PB_HP, xc & 3);  // + slot * RPS rows (swizzle unchanged)
+  const int xl = (xc >> 2) * PL + plane_off(xr + PB_HP, xc & 3);  // + slot * RPS rows (swizzle unchanged)
   u32x4 xw[NWV];
   auto load_win = [&](int tl, int sl) __attribute__((always_inline)) {
-    const int b = RAG ? nx.b : tl / a.tiles_per_b;
-    const int p0 = (RAG ? nx.t0 : (tl - b * a.tiles_per_b) * BT) - PB_HALO;
+    const MrfTile nt = run.at(tl);
+    const int b = nt.b, p0 = nt.t0 - PB_HALO;
     // positions before 0 wrap to huge offsets and past T exceed the range: both read 0 (zero padding)
-    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b, RAG ? nx.R : T), ((p0 + xr + RPS * sl) * C + xc * 8) * 2, 0, 0);
+    xw[sl] = __builtin_amdgcn_raw_buffer_load_b128(utt(a.x, b, nt.R), ((p0 + xr + RPS * sl) * C + xc * 8) * 2, 0, 0);
   };
   auto store_win = [&](int sl) __attribute__((always_inline)) { *reinterpret_cast<u32x4*>(win + xl + sl * RPS * 32) = lrelu8(xw[sl], slope); };
 
 #pragma unroll
   for (int i = 0; i < NAP; ++i) loadA_piece(0, i);
 #pragma unroll
-  for (int sl = 0; sl < NWV; ++sl) load_win(tile, sl);
+  for (int sl = 0; sl < NWV; ++sl) load_win(run.tile, sl);
 #pragma unroll
   for (int sl = 0; sl < NWV; ++sl) store_win(sl);
 
@@ -166,14 +152,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   u32x4 xres[NJ];  // the wave's residual rows (x from HBM for stage 0, then x1, x2 from its own epilogues)
   u32x4 ares[NJ];
   bf16x8 aid[2], ais[2];  // identity A fragments (co tile t); ais scaled by 1 / out_scale (ACC == 2)
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const bool one = (lr >> 2) == lg && e == 4 * t + (lr & 3);
-      aid[t][e] = (__bf16)(one ? 1.0f : 0.0f);
-      ais[t][e] = (__bf16)(one ? 1.0f / a.out_scale : 0.0f);
-    }
+  plane_identity(aid, ais, lr, lg, a.out_scale);
 
   // One conv of the block over the frame, in two phases:
   //   phase 0: tap 0, plane-major over the NJ row tiles (NST steps);
@@ -196,7 +175,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     auto ds = [&](int q) __attribute__((always_inline)) { return q < NST ? q / NJ : ((q - NST) % BS) / 4; };
     auto readB = [&](int q) __attribute__((always_inline)) {
       const int k = dk(q), j = dj(q), s = ds(q);
-      const bf16_t* base = src + (s >> 1) * 2 * PL + pb_off(PB_HP + (k - 1) * step + row0 + lro, lgo);
+      const bf16_t* base = src + (s >> 1) * 2 * PL + plane_off(PB_HP + (k - 1) * step + row0 + lro, lgo);
       Bq[q % NB] = *reinterpret_cast<const bf16x8*>(base + (s & 1) * PL + j * 512);
     };
     const f32x4* bz = reinterpret_cast<const f32x4*>(sbias + V * C + 32 * pw + 8 * lg);
@@ -245,26 +224,13 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
   };
 
   const int cofs = 32 * pw + 8 * lg;
-  for (; tile < tile_end; ++tile) {
-    const int b = RAG ? nx.b : tile / a.tiles_per_b;
-    const int t0 = RAG ? nx.t0 : (tile - b * a.tiles_per_b) * BT;
-    const int Tv = RAG ? nx.R : T;  // the utterance's valid rows
+  for (; run.more(); run.advance()) {
+    const MrfTile ti = run.enter();
+    const int b = ti.b, t0 = ti.t0, Tv = ti.R;  // utterance, first output row, the utterance's valid rows
+    const int ntile = run.succ();
     const int p0 = t0 - PB_HALO;  // position of frame row 0
-    const int ntile = tile + 1 < tile_end ? tile + 1 : tile;
-    if constexpr (RAG) nx = walk.at(ntile);
-    // Zero padding: the epilogues write every frame row unmasked (a mask per row tile cost 5 of its ~38 vector
-    // instructions, in the VALU-bound epilogue phase; a branch around it made hipcc copy eight accumulators out
-    // of the AGPRs at every join); in the tiles whose frame crosses an utterance end, the rows outside [0, T) of
-    // the wave's own plane are zeroed after the epilogue, before the barrier that publishes them
-    const bool edge = p0 < 0 || p0 + F > Tv;
-    const int zlo = p0 < 0 ? -p0 : 0, zhi = Tv - p0;  // frame rows [zlo, zhi) are inside the utterance
-    auto zero_rows = [&](bf16_t* buf) __attribute__((always_inline)) {
-      if (!edge) return;
-      for (int f = row0 + lane; f < row0 + 16 * NJ; f += 64)
-        if (f < zlo || f >= zhi)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x4*>(buf + pw * PL + pb_off(f + PB_HP, q)) = u32x4{0u, 0u, 0u, 0u};
-    };
+    const PlaneEdge edge(p0, F, Tv);  // the rows outside [0, Tv) of the wave's own plane are zeroed after each epilogue
+    auto zero_rows = [&](bf16_t* buf) __attribute__((always_inline)) { edge.zero_rows<PB_HP>(buf + pw * PL, row0, 16 * NJ, lane); };
     const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b, Tv);
     const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b, Tv);
 
@@ -282,7 +248,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
 #endif
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
-        *reinterpret_cast<u32x4*>(t1 + pw * PL + pb_off(f + PB_HP, lg)) = u32x4{pv[0], pv[1], pv[2], pv[3]};
+        *reinterpret_cast<u32x4*>(t1 + pw * PL + plane_off(f + PB_HP, lg)) = u32x4{pv[0], pv[1], pv[2], pv[3]};
       }
     };
     // P2 epilogue of stages 0 / 1: x_{s+1} = bf16(acc) kept in xres; lrelu(x_{s+1}) into the window (rows
@@ -301,7 +267,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
         xres[j] = u32x4{pv[0], pv[1], pv[2], pv[3]};
-        *reinterpret_cast<u32x4*>(win + pw * PL + pb_off(f + PB_HP, lg)) = u32x4{lv[0], lv[1], lv[2], lv[3]};
+        *reinterpret_cast<u32x4*>(win + pw * PL + plane_off(f + PB_HP, lg)) = u32x4{lv[0], lv[1], lv[2], lv[3]};
       }
     };
     // the residual (and acc_in / out_scale) through identity MFMAs at plane 0's step of row tile j:
@@ -420,7 +386,7 @@ using namespace vo;
 
 // Entry from vo_resblock3: *handled = 1 when this kernel covers the shape (C = 64 / 128, every dilation <= 8 and
 // their halo sum <= 12: at those C, everything vo_resblock3 accepts).
-int vo_rb3_pb_try(const MrfBlock3Call& c, int* handled) {
+int vo_rb3_pb_try(const MrfBlockCall& c, int* handled) {
   *handled = 0;
   if (!(c.C == 64 || c.C == 128)) return VO_OK;
   int halo = 0;
@@ -430,29 +396,15 @@ int vo_rb3_pb_try(const MrfBlock3Call& c, int* handled) {
   }
   if (halo > PB_HALO) return VO_OK;
   Pb3Args a;
-  a.x = (const bf16_t*)c.x;
-  for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.b[2 * s] = c.b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.b[2 * s + 1] = c.b2[s];
-    a.dil[s] = c.dil[s];
-  }
-  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
-  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
-  a.tiles_per_b = a.ntiles = 0;
+  mrf_block_args(a, c);
+  for (int s = 0; s < 3; ++s) a.dil[s] = c.dil[s];
   a.stamps = nullptr;
-  a.rg = MrfLens{c.lens, c.lens_scale, c.B};
   *handled = 1;
-  const int accm = mrf_acc_mode(c.acc, c.out_scale);
-#define VO_PB3_DISPATCH(CC, RG)                                                                                   \
-  return accm == 2 ? pb3_launch<CC, 2, RG>(a, c.B, c.st) : accm == 1 ? pb3_launch<CC, 1, RG>(a, c.B, c.st) \
-                                                                     : pb3_launch<CC, 0, RG>(a, c.B, c.st)
-  if (c.lens) {
-    if (c.C == 64) VO_PB3_DISPATCH(64, true);
-    VO_PB3_DISPATCH(128, true);
-  }
-  if (c.C == 64) VO_PB3_DISPATCH(64, false);
-  VO_PB3_DISPATCH(128, false);
-#undef VO_PB3_DISPATCH
+  return mrf_with_acc(mrf_acc_mode(c.acc, c.out_scale), [&](auto accm) {
+    constexpr int ACC = decltype(accm)::value;
+    if (c.lens) return c.C == 64 ? pb3_launch<64, ACC, true>(a, c.B, c.st) : pb3_launch<128, ACC, true>(a, c.B, c.st);
+    return c.C == 64 ? pb3_launch<64, ACC, false>(a, c.B, c.st) : pb3_launch<128, ACC, false>(a, c.B, c.st);
+  });
 }
 
 #ifdef VO_PB3_STAMPS
@@ -466,14 +418,10 @@ extern "C" int vo_pb3_stamps(const void* x, const void* const* w1, const float* 
   if (hipMalloc(&d, n * 8) != hipSuccess) return -1;
   (void)hipMemset(d, 0, n * 8);
   Pb3Args a;
-  a.x = (const bf16_t*)x;
-  for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)w1[s]; a.b[2 * s] = b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)w2[s]; a.b[2 * s + 1] = b2[s];
-    a.dil[s] = 2 * s + 1;
-  }
-  a.y = (bf16_t*)y; a.acc = (const bf16_t*)y;
-  a.T = T; a.slope = 0.1f; a.out_scale = 1.f / 3; a.stamps = d;
+  const int dil[3] = {1, 3, 5};
+  mrf_block_args(a, MrfBlockCall{x, w1, b1, w2, b2, dil, y, y, B, T, C, 3, 0.1f, 1.f / 3});
+  for (int s = 0; s < 3; ++s) a.dil[s] = dil[s];
+  a.stamps = d;
   const int BT = pb_f(C) - 2 * PB_HALO;
   a.tiles_per_b = (T + BT - 1) / BT;
   a.ntiles = a.tiles_per_b * B;

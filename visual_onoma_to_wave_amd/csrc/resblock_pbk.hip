@@ -21,15 +21,15 @@
 //   * a conv's first K - L taps run tap by tap over the 16 row tiles (phase A); its last L taps run interleaved in
 //     blocks of two row tiles (phase B), so that a block's accumulators are final after its 2 L steps and its
 //     epilogue issues under the next block's MFMAs (the epilogues, not the MFMAs, bound the k = 3 block);
-//   * LDS rows [row][32 ch], 16-byte chunk q of row r at q ^ ((r >> 1) & 3) (pb_off of resblock_pb3.hip): the
-//     B-fragment reads at any row shift and the T1 / window stores of the epilogues are bank-conflict free.
+//   * LDS rows [row][32 ch] in the swizzle of plane_off (mrf_plane.h): the B-fragment reads at any row shift and
+//     the T1 / window stores of the epilogues are bank-conflict free.
 // Weights: [K][C_out][C_in] bf16 packs (vo_pack_weight); biases fp32.
 
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
-#include "mrf_common.h"
+#include "mrf_plane.h"
 
 #ifndef VO_PBK_L
 #define VO_PBK_L 4  // taps of a conv that run interleaved with the epilogues (phase B)
@@ -54,8 +54,6 @@ constexpr int pbk_halo(int K) { return pbk_h2(K) * (1 + 1 + 3 + 1 + 5 + 1); }  /
 constexpr int pbk_bt(int K) { return PBK_F - 2 * pbk_halo(K); }               // output rows per tile
 constexpr int pbk_rp(int K) { return PBK_F + 2 * pbk_hp(K) + 1; }             // LDS rows per buffer
 constexpr size_t pbk_lds(int K) { return (size_t)2 * pbk_rp(K) * 32 * sizeof(bf16_t) + 6 * PBK_C * sizeof(float); }
-
-__device__ __forceinline__ int pbk_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
 // RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
 // T does in the dense form (buffer ranges, zeroed frame rows, stored rows); T stays the row stride between utterances
@@ -86,22 +84,12 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
   const int row0 = w * 16 * NJ;  // the wave's first frame row
   const int lr = lane & 15, lg = lane >> 4;
 
-  // contiguous tile run of this workgroup (uniform per workgroup: the early exit is safe)
-  MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
-  const int ntl = RAG ? walk.total() : a.ntiles;
-  const int G = gridDim.x;
-  int tile = (int)(((int64_t)blockIdx.x * ntl) / G);
-  const int tile_end = (int)(((int64_t)(blockIdx.x + 1) * ntl) / G);
-  if (tile >= tile_end) return;
-  MrfTile nx = RAG ? walk.at(tile) : MrfTile{0, 0, T};  // RAG: the tile whose window win_tile fetches (the first, then each tile's successor)
+  MrfRun<RAG, BT> run(a.tiles_per_b, a.ntiles, T, a.rg);
+  if (run.empty()) return;  // uniform per workgroup: the early exit is safe
+  run.start();
 
   for (int i = tid; i < 6 * C; i += 256) sbias[i] = a.b[i / C][i % C];
-  // pad rows (read only by taps of frame rows whose outputs the halo discards): zeros, never NaN
-  for (int i = tid; i < 2 * (2 * HP + 1) * 4; i += 256) {
-    const int q = i & 3, r0 = (i >> 2) % (2 * HP + 1), pb = (i >> 2) / (2 * HP + 1);
-    const int r = r0 < HP ? r0 : F + r0;
-    *reinterpret_cast<u32x4*>(win + pb * PL + pbk_off(r, q)) = u32x4{0u, 0u, 0u, 0u};
-  }
+  plane_zero_pads<2, HP, F, PL>(win, tid);
 
   // ---- A fragments (as resblock_rw.hip): lane l holds W[tap][co][ci], co = 8(lr>>2) + 4t + (lr&3), ci = 8lg .. +7;
   // accumulator register i of co tile t is then channel 8lg + 4t + i
@@ -114,25 +102,22 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
     const int uu = u % NU, v = uu / K, k = uu % K;
     A[uu % R][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw[v], aoff + t * 4 * C * 2, k * (C * C * 2), 0));
   };
-  auto utt = [&](const bf16_t* p, int b, int Tv) __attribute__((always_inline)) {  // rows [0, Tv) of one utterance of a (B, T, C) tensor: rows outside read 0
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
-  };
-  // op i of n spread over the steps [lo, lo + span) of a tap: does step jj carry it?
-  auto at = [](int jj, int lo, int span, int n, int i) __attribute__((always_inline)) { return jj == lo + i * span / n; };
+
+  auto utt = [&](const bf16_t* p, int b, int Tv) __attribute__((always_inline)) { return plane_utt<C>(p, b, T, Tv); };
 
   // ---- window staging: vector v = tid + 256 slot = (frame row xr + RPS slot, 16-byte column xc)
   const int xr = tid >> 2, xc = tid & 3;
-  const int xl = pbk_off(xr + HP, xc);  // + slot * RPS rows (swizzle unchanged)
+  const int xl = plane_off(xr + HP, xc);  // + slot * RPS rows (swizzle unchanged)
   u32x4 xw[NWV];
-  // the lane's byte offset of slot 0 in the window of tile tl (rs: its utterance), opaque per tile: hoisted out of the
+  // the lane's byte offset of slot 0 in the window of tile nt (rswin: its utterance), opaque per tile: hoisted out of the
   // tile loop, the sixteen slot offsets (and those of the residual, accumulator and y rows below) stayed live
   // throughout, spilled, and every reload waited for vmcnt(0)
   __amdgpu_buffer_rsrc_t rswin;
   int wbase;
   auto win_tile = [&](int tl) __attribute__((always_inline)) {
-    const int b = RAG ? nx.b : tl / a.tiles_per_b;
-    const int p0 = (RAG ? nx.t0 : (tl - b * a.tiles_per_b) * BT) - HALO;
-    rswin = utt(a.x, b, RAG ? nx.R : T);
+    const MrfTile nt = run.at(tl);
+    const int b = nt.b, p0 = nt.t0 - HALO;
+    rswin = utt(a.x, b, nt.R);
     wbase = ((p0 + xr) * C + xc * 8) * 2;
     asm volatile("" : "+v"(wbase));
   };
@@ -146,7 +131,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
   for (int u = 0; u < R - L; ++u)
 #pragma unroll
     for (int t = 0; t < 2; ++t) loadA_piece(u, t);
-  win_tile(tile);
+  win_tile(run.tile);
 #pragma unroll
   for (int sl = 0; sl < NWV; ++sl) load_win(sl);
 #pragma unroll
@@ -157,14 +142,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
   u32x4 xres[NJ];  // the wave's residual rows (x from HBM for stage 0, then x1, x2 from its own epilogues)
   u32x4 ares[NJ];
   bf16x8 aid[2], ais[2];  // identity A fragments (co tile t); ais scaled by 1 / out_scale (ACC == 2)
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const bool one = (lr >> 2) == lg && e == 4 * t + (lr & 3);
-      aid[t][e] = (__bf16)(one ? 1.0f : 0.0f);
-      ais[t][e] = (__bf16)(one ? 1.0f / a.out_scale : 0.0f);
-    }
+  plane_identity(aid, ais, lr, lg, a.out_scale);
 
   // One conv of the block over the frame.  Step q of the conv -> (tap, row tile): phase A (q < KA NJ) tap-major;
   // phase B in blocks of two row tiles, tap-major inside the block with the two row tiles alternating, so no MFMA
@@ -182,7 +160,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
     auto dj = [&](int q) __attribute__((always_inline)) { return q < KA * NJ ? q % NJ : 2 * ((q - KA * NJ) / BS) + (q - KA * NJ) % 2; };
     auto readB = [&](int q) __attribute__((always_inline)) {
       const int k = dk(q), j = dj(q);
-      Bq[q % NB] = *reinterpret_cast<const bf16x8*>(src + pbk_off(HP + (k - H2) * step + row0 + lro, lgo) + j * 512);
+      Bq[q % NB] = *reinterpret_cast<const bf16x8*>(src + plane_off(HP + (k - H2) * step + row0 + lro, lgo) + j * 512);
     };
     const f32x4* bz = reinterpret_cast<const f32x4*>(sbias + V * C + 8 * lg);
     const f32x4 bz0 = bz[0], bz1 = bz[1];
@@ -236,25 +214,13 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
   };
 
   const int cofs = 8 * lg;
-  for (; tile < tile_end; ++tile) {
-    const int b = RAG ? nx.b : tile / a.tiles_per_b;
-    const int t0 = RAG ? nx.t0 : (tile - b * a.tiles_per_b) * BT;
-    const int Tv = RAG ? nx.R : T;  // the utterance's valid rows
+  for (; run.more(); run.advance()) {
+    const MrfTile ti = run.enter();
+    const int b = ti.b, t0 = ti.t0, Tv = ti.R;  // utterance, first output row, the utterance's valid rows
+    const int ntile = run.succ();
     const int p0 = t0 - HALO;  // position of frame row 0
-    const int ntile = tile + 1 < tile_end ? tile + 1 : tile;
-    if constexpr (RAG) nx = walk.at(ntile);
-    // Zero padding: the epilogues write every frame row unmasked; in the tiles whose frame crosses an utterance
-    // end, the rows outside [0, Tv) of the wave's own row group are zeroed after the epilogue, before the barrier
-    // that publishes them (resblock_pb3.hip)
-    const bool edge = p0 < 0 || p0 + F > Tv;
-    const int zlo = p0 < 0 ? -p0 : 0, zhi = Tv - p0;  // frame rows [zlo, zhi) are inside the utterance
-    auto zero_rows = [&](bf16_t* buf) __attribute__((always_inline)) {
-      if (!edge) return;
-      for (int f = row0 + lane; f < row0 + 16 * NJ; f += 64)
-        if (f < zlo || f >= zhi)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x4*>(buf + pbk_off(f + HP, q)) = u32x4{0u, 0u, 0u, 0u};
-    };
+    const PlaneEdge edge(p0, F, Tv);  // the rows outside [0, Tv) of the wave's own row group are zeroed after each epilogue
+    auto zero_rows = [&](bf16_t* buf) __attribute__((always_inline)) { edge.zero_rows<HP>(buf, row0, 16 * NJ, lane); };
     const __amdgpu_buffer_rsrc_t rsx = utt(a.x, b, Tv);
     const __amdgpu_buffer_rsrc_t rsa = utt(ACC ? a.acc : a.x, b, Tv);
     // byte offsets of the lane's 8 channels of row tile 0: in x / acc (frame row row0 + lr) and in y's tile range
@@ -270,7 +236,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
       pv[p] = pk_bf16(lrelu_max(acc[t][j][e], slope), lrelu_max(acc[t][j][e + 1], slope));
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
-        *reinterpret_cast<u32x4*>(t1 + pbk_off(f + HP, lg)) = u32x4{pv[0], pv[1], pv[2], pv[3]};
+        *reinterpret_cast<u32x4*>(t1 + plane_off(f + HP, lg)) = u32x4{pv[0], pv[1], pv[2], pv[3]};
       }
     };
     // P2 epilogue of stages 0 / 1: x_{s+1} = bf16(acc) kept in xres; lrelu(x_{s+1}) into the window, taken from
@@ -284,7 +250,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
         xres[j] = u32x4{pv[0], pv[1], pv[2], pv[3]};
-        *reinterpret_cast<u32x4*>(win + pbk_off(f + HP, lg)) = u32x4{lv[0], lv[1], lv[2], lv[3]};
+        *reinterpret_cast<u32x4*>(win + plane_off(f + HP, lg)) = u32x4{lv[0], lv[1], lv[2], lv[3]};
       }
     };
     // the residual through identity MFMAs at tap 0: the lane's residual vector of row tile j IS a B fragment
@@ -304,7 +270,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
       if (k != WT) return;
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
-        if (at(jj, 2, NJ - 2, NJ, j))
+        if (plane_at(jj, 2, NJ - 2, NJ, j))
           xres[j] = __builtin_amdgcn_raw_buffer_load_b128(rsx, rbase + j * (16 * C * 2), 0, 0);
     };
     conv(std::integral_constant<int, 0>{}, s0_hook, p1_post, no_extra);
@@ -325,7 +291,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
       if (k != WT) return;
 #pragma unroll
       for (int sl = 0; sl < NWV; ++sl)
-        if (at(jj, 2, NJ - 2, NWV, sl)) load_win(sl);
+        if (plane_at(jj, 2, NJ - 2, NWV, sl)) load_win(sl);
     };
     win_tile(ntile);
     conv(std::integral_constant<int, 4>{}, s2a_hook, p1_post, no_extra);
@@ -343,7 +309,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
       const int g = k * NJ + jj;
 #pragma unroll
       for (int sl = 0; sl < NWV; ++sl)
-        if (at(g, NJ / 2, KA * NJ - NJ / 2, NWV, sl)) {
+        if (plane_at(g, NJ / 2, KA * NJ - NJ / 2, NWV, sl)) {
           store_win(sl);
           if constexpr (ACC != 0)  // into the registers the window slot just left
             ares[sl] = __builtin_amdgcn_raw_buffer_load_b128(rsa, rbase + sl * (16 * C * 2), 0, 0);
@@ -371,7 +337,8 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
 }
 
 template <int K, int ACC>
-static int pbk_launch(PbkArgs a, int B, hipStream_t st) {
+static int pbk_launch(PbkArgs a, int B, MrfTo st) {
+  if (mrf_tile_rows_query(st, pbk_bt(K))) return VO_OK;
   a.tiles_per_b = (a.T + pbk_bt(K) - 1) / pbk_bt(K);
   a.ntiles = a.tiles_per_b * B;
   if (a.rg.lens) return mrf_launch(mrf_pbk_kernel<K, ACC, true>, a, a.ntiles, 256, pbk_lds(K), false, st);
@@ -384,7 +351,7 @@ using namespace vo;
 
 // Entry from vo_resblockk / vo_resblockk_lens: *handled = 1 when this kernel covers the call -- C = 32, K = 7 / 11,
 // dilations (1, 3, 5), and an MRF accumulator only with 1 / out_scale a bf16 value (it enters through an identity MFMA)
-int vo_rbk_pb_try(const MrfBlockKCall& c, int* handled) {
+int vo_rbk_pb_try(const MrfBlockCall& c, int* handled) {
   *handled = 0;
   if (c.C != PBK_C || !(c.K == 7 || c.K == 11)) return VO_OK;
   if (c.dil[0] != 1 || c.dil[1] != 3 || c.dil[2] != 5) return VO_OK;
@@ -392,40 +359,21 @@ int vo_rbk_pb_try(const MrfBlockKCall& c, int* handled) {
   if (accm == 1) return VO_OK;
   if ((int64_t)c.T * PBK_C * 2 > 0x7fffffff) return VO_OK;  // an utterance is one buffer range
   PbkArgs a;
-  a.x = (const bf16_t*)c.x;
-  for (int s = 0; s < 3; ++s) {
-    a.w[2 * s] = (const bf16_t*)c.w1[s]; a.b[2 * s] = c.b1[s];
-    a.w[2 * s + 1] = (const bf16_t*)c.w2[s]; a.b[2 * s + 1] = c.b2[s];
-  }
-  a.y = (bf16_t*)c.y; a.acc = (const bf16_t*)c.acc;
-  a.T = c.T; a.slope = c.slope; a.out_scale = c.out_scale;
-  a.tiles_per_b = a.ntiles = 0;
-  a.rg = MrfLens{c.lens, c.lens_scale, c.B};
+  mrf_block_args(a, c);
   *handled = 1;
   if (c.K == 7) return accm == 2 ? pbk_launch<7, 2>(a, c.B, c.st) : pbk_launch<7, 0>(a, c.B, c.st);
   return accm == 2 ? pbk_launch<11, 2>(a, c.B, c.st) : pbk_launch<11, 0>(a, c.B, c.st);
 }
 
-// Output rows per tile of the kernel that vo_rbk_pb_try launches for K (0: none) -- the tests' edge shapes
-extern "C" int vo_resblockk_tile_rows(int K) { return K == 7 ? pbk_bt(7) : K == 11 ? pbk_bt(11) : 0; }
-
 // vo_resblockk (lens == nullptr) and vo_resblockk_lens
 static int resblockk_entry(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                            const float* const* b2, int K, const int* dil, void* y, const void* acc, int B, int T, int C,
-                           float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
-  VO_CHECK_ARG(x && w1 && b1 && w2 && b2 && dil && y, "resblockk: null pointer");
-  VO_CHECK_ARG(C == 32 || C == 64 || C == 128, "resblockk: C=%d unsupported (32, 64 or 128)", C);
+                           float slope, float out_scale, MrfTo st, const int32_t* lens, int lens_scale) {
+  const MrfBlockCall c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, K, slope, out_scale, st, lens, lens_scale};
+  if (const int rc = vo_block_check(c, "resblockk")) return rc;
   VO_CHECK_ARG(K % 2 == 1 && K >= 1 && K <= 15, "resblockk: K=%d unsupported (odd K <= 15)", K);
-  VO_CHECK_ARG(B > 0 && T > 0, "resblockk: empty");
-  VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "resblockk: slope %g outside [0, 1]", slope);
-  VO_CHECK_ARG(y != x, "resblockk: y must not alias x (neighbouring tiles re-read x)");
-  VO_CHECK_ARG(acc == nullptr || acc == y || acc != x, "resblockk: acc must not alias x");
-  for (int s = 0; s < 3; ++s) {
-    VO_CHECK_ARG(w1[s] && b1[s] && w2[s] && b2[s], "resblockk: null weight of stage %d", s);
+  for (int s = 0; s < 3; ++s)
     VO_CHECK_ARG(dil[s] >= 1 && dil[s] * (K - 1) <= 64, "resblockk: dilation %d unsupported ((K-1)*dil <= 64)", dil[s]);
-  }
-  const MrfBlockKCall c{x, w1, b1, w2, b2, dil, y, acc, B, T, C, K, slope, out_scale, reinterpret_cast<hipStream_t>(stream),
-                        lens, lens_scale};
   int handled = 0;
   const int rc = vo_rbk_pb_try(c, &handled);
   return handled ? rc : VO_NOT_HANDLED;
@@ -434,12 +382,30 @@ static int resblockk_entry(const void* x, const void* const* w1, const float* co
 extern "C" int vo_resblockk(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                             const float* const* b2, int K, const int* dil, void* y, const void* acc, int B, int T, int C,
                             float slope, float out_scale, void* stream) {
-  return resblockk_entry(x, w1, b1, w2, b2, K, dil, y, acc, B, T, C, slope, out_scale, stream, nullptr, 0);
+  return resblockk_entry(x, w1, b1, w2, b2, K, dil, y, acc, B, T, C, slope, out_scale,
+                         reinterpret_cast<hipStream_t>(stream), nullptr, 0);
 }
 
 extern "C" int vo_resblockk_lens(const void* x, const void* const* w1, const float* const* b1, const void* const* w2,
                                  const float* const* b2, int K, const int* dil, void* y, const void* acc, int B, int T,
                                  int C, float slope, float out_scale, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(lens && lens_scale >= 1, "resblockk_lens: lens is null or lens_scale %d < 1", lens_scale);
-  return resblockk_entry(x, w1, b1, w2, b2, K, dil, y, acc, B, T, C, slope, out_scale, stream, lens, lens_scale);
+  return resblockk_entry(x, w1, b1, w2, b2, K, dil, y, acc, B, T, C, slope, out_scale,
+                         reinterpret_cast<hipStream_t>(stream), lens, lens_scale);
+}
+
+// Host-only: output rows per tile of the kernel that vo_resblockk launches for K (0: none) -- its dispatch run as a
+// tile-rows query, as vo_resblock3_tile_rows (resblock3.hip): placeholder operands that are compared and copied, never
+// read through
+extern "C" int vo_resblockk_tile_rows(int K) {
+  static const char in = 0;
+  static char out = 0;
+  const float* const fb = reinterpret_cast<const float*>(&in);
+  const void* const w[3] = {&in, &in, &in};
+  const float* const b[3] = {fb, fb, fb};
+  const int dil[3] = {1, 3, 5};
+  int rows = 0;
+  if (resblockk_entry(&in, w, b, w, b, K, dil, &out, nullptr, 1, 1, 32, 0.1f, 1.0f, MrfTo(nullptr, &rows), nullptr, 0) != VO_OK)
+    return 0;
+  return rows;
 }

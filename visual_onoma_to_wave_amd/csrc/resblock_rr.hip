@@ -946,7 +946,7 @@ using namespace vo;
 
 // vo_resblock3's register-resident path (C = 32; C = 64 in the A/B library; dilations (1, 3, 5)); *handled = 0
 // leaves the call to the LDS-frame kernel
-int vo_rb3_rr_try(const MrfBlock3Call& c, int cfg, int* handled) {
+int vo_rb3_rr_try(const MrfBlockCall& c, int cfg, int* handled) {
   const int B = c.B, C = c.C;
   const MrfTo st = c.st;
   *handled = 0;

@@ -16,10 +16,9 @@
 //     (128 B/clk per CU, half the LDS array) and 1/16 of a global load of A;
 //   * the next tile's window is fetched during P2 (the window is dead once P1 ends; T1 has its own
 //     buffer) and written, lrelu'd, two taps after its loads were issued;
-//   * LDS layout [plane][row][32 ch] with 16-byte chunk q of row r at q ^ ((r >> 1) & 3): the B-fragment
-//     reads (16 rows x 4 chunks at ANY row offset -- the taps shift rows by k*dil), the T1 stores and
-//     the window stores (plane stride of 321 rows: odd) are all bank-conflict free (checked exhaustively
-//     over the lane groups of ds_read_b128 / ds_write_b128, MI355X_MICROARCH.md section LDS);
+//   * LDS layout [plane][row][32 ch] in the swizzle of plane_off (mrf_plane.h): the B-fragment reads at any
+//     row offset (the taps shift rows by k*dil), the T1 stores and the window stores (plane stride of 321
+//     rows: odd) are all bank-conflict free;
 //   * output channels permuted in the A rows so that a lane's two accumulators of one row tile are the
 //     8 consecutive channels 32w + 8(l>>4) .. +7 of row (l & 15): one 16-byte T1 store / y store per row
 //     tile, in the layout the next conv's B fragments read.
@@ -29,7 +28,7 @@
 #include <cmath>
 #include <type_traits>
 
-#include "mrf_common.h"
+#include "mrf_plane.h"
 
 namespace vo {
 
@@ -52,8 +51,6 @@ constexpr size_t rw_lds(int C) {
   return (size_t)rw_np(C) * (rw_wp(C) + rw_tp(C)) * 32 * sizeof(bf16_t) + 2 * C * sizeof(float);
 }
 constexpr int RW_NSTW = 16, RW_NSTT = 4, RW_NPT = 2 * 11 + 6;  // stamp geometry (diagnostic builds)
-
-__device__ __forceinline__ int rw_off(int r, int q) { return r * 32 + 8 * (q ^ ((r >> 1) & 3)); }
 
 // RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
 // T does in the dense form (buffer ranges, the T1 mask, stored rows); T stays the row stride between utterances
@@ -121,7 +118,9 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     }
   };
 
-  // contiguous tile run of this workgroup (uniform per workgroup: the early exit is safe)
+  // contiguous tile run of this workgroup (uniform per workgroup: the early exit is safe).  Written out, not MrfRun
+  // (mrf_common.h): with the struct the C = 128 k = 7 ACC = 2 kernel came out with 4 more registers and 12 more
+  // instructions
   MrfWalk<RAG> walk(a.tiles_per_b, a.ntiles, T, BT, a.rg);
   const int ntl = RAG ? walk.total() : a.ntiles;
   const int G = gridDim.x;
@@ -134,8 +133,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
 
   // ---- A fragments: lane l holds W[tap][co][ci] for co = 32pw + 8(lr>>2) + 4t + (lr&3) (co tile t:
   // accumulator register i of lane l is then channel 32pw + 8lg + 4t + i) and ci = 32s + 8lg .. +7
-  // loads through buffer resources: 32-bit lane offsets (a 64-bit address per load kept 2 VGPRs live
-  // each and spilled), rows outside an utterance read as 0 (the convs' zero padding) with no clamp
+  // loads through buffer resources (plane_utt, mrf_plane.h)
   const int aoff = ((32 * pw + 8 * (lr >> 2) + (lr & 3)) * C + 8 * lg) * (int)sizeof(bf16_t);
   const int afr = pw * NAP * 1024 + lane * 16;  // FR: [tap][pw][s][t][lane][8]
   const __amdgpu_buffer_rsrc_t rw1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w1, (short)0, K * C * C * 2, 0x00020000);
@@ -153,13 +151,11 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     A[uu & 1][s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(uu < K ? rw1 : rw2,
                                              lo, tap_off, 0));
   };
-  auto utt = [&](const bf16_t* p, int b, int Tv) {  // rows [0, Tv) of one utterance of a (B, T, C) tensor
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (int64_t)b * T * C), (short)0, Tv * C * 2, 0x00020000);
-  };
+  auto utt = [&](const bf16_t* p, int b, int Tv) { return plane_utt<C>(p, b, T, Tv); };
 
   // ---- window staging: vector v = tid + 256 * slot = (row xr + RPS slot, 16-byte column xc)
   const int xr = tid / VPR, xc = tid % VPR;
-  const int xl = (xc >> 2) * WP * 32 + rw_off(xr, xc & 3);  // + slot * RPS rows (swizzle unchanged)
+  const int xl = (xc >> 2) * WP * 32 + plane_off(xr, xc & 3);  // + slot * RPS rows (swizzle unchanged)
   u32x4 xw[NWV];
   // window rows c1 reads: R1 + (K - 1) dil of the R1 + 64 staged (the rest are never read: their loads
   // are sent out of the buffer's range, which returns 0 without touching memory -- at d = 1 they were
@@ -183,16 +179,8 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
 
   f32x4 acc[2][NJ];
   bf16x8 Bq[NB];
-  // identity A fragments (co tile t): lane (m = lr, lg) holds 1 at k = 4t + (m & 3) of its 8 when m / 4 == lg
-  bf16x8 aid[2], ais[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const bool one = (lr >> 2) == lg && e == 4 * t + (lr & 3);
-      aid[t][e] = (__bf16)(one ? 1.0f : 0.0f);
-      ais[t][e] = (__bf16)(one ? 1.0f / a.out_scale : 0.0f);  // ACC == 2: exact by the launcher's check
-    }
+  bf16x8 aid[2], ais[2];  // identity A fragments (co tile t); ais scaled by 1 / out_scale (ACC == 2)
+  plane_identity(aid, ais, lr, lg, a.out_scale);
 
   // One conv over the tile: K taps x 4 input planes x 16 row tiles, steps j-major inside a tap.  PH = 0:
   // c1 over the window (row step dil, taps u = k); PH = 1: c2 over T1 (row step 1, taps u = K + k).
@@ -221,7 +209,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     auto readB = [&](int q) {  // q: step index over the conv (tap q / NST, row tile, plane)
       const int k = q / NST, j = rt(k, q % NST), s = pl(k, q % NST);
       // planes 0-1 and 2-3 from two bases: the ds_read offset field holds 16 bits
-      const bf16_t* base = src + (s >> 1) * 2 * PL + rw_off(k * step + row0 + lro, lgo);
+      const bf16_t* base = src + (s >> 1) * 2 * PL + plane_off(k * step + row0 + lro, lgo);
       Bq[q % NB] = *reinterpret_cast<const bf16x8*>(base + (s & 1) * PL + j * 512);
     };
 #pragma unroll
@@ -310,7 +298,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
         const int pos = t0 - H2 + r;
         u32x4 v = u32x4{pv[0], pv[1], pv[2], pv[3]};
         if (!interior) v &= (pos >= 0 && pos < Tv) ? 0xffffffffu : 0u;
-        *reinterpret_cast<u32x4*>(t1 + pw * TP * 32 + rw_off(r, lg)) = v;
+        *reinterpret_cast<u32x4*>(t1 + pw * TP * 32 + plane_off(r, lg)) = v;
       }
     };
     conv(std::integral_constant<int, 0>{}, p1_hook, p1_post, p1_cinit, [&](int, int, int) {});
@@ -422,25 +410,15 @@ int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
   a.stamps = nullptr;
   a.rg = MrfLens{c.lens, c.lens_scale, B};
   *handled = 1;
-  const int accm = mrf_acc_mode(c.acc, c.out_scale);
-#define VO_PRW_DISPATCH(CC, KK, FF) \
-  return accm == 2 ? prw_launch<CC, KK, 2, FF>(a, B, st) : accm == 1 ? prw_launch<CC, KK, 1, FF>(a, B, st) \
-                                                        : prw_launch<CC, KK, 0, FF>(a, B, st)
-  if (C == 64) {
-    if (frag) {
-      if (K == 7) VO_PRW_DISPATCH(64, 7, true);
-      VO_PRW_DISPATCH(64, 11, true);
+  return mrf_with_acc(mrf_acc_mode(c.acc, c.out_scale), [&](auto accm) {
+    constexpr int ACC = decltype(accm)::value;
+    if (C == 64) {
+      if (frag) return K == 7 ? prw_launch<64, 7, ACC, true>(a, B, st) : prw_launch<64, 11, ACC, true>(a, B, st);
+      return K == 7 ? prw_launch<64, 7, ACC, false>(a, B, st) : prw_launch<64, 11, ACC, false>(a, B, st);
     }
-    if (K == 7) VO_PRW_DISPATCH(64, 7, false);
-    VO_PRW_DISPATCH(64, 11, false);
-  }
-  if (frag) {
-    if (K == 7) VO_PRW_DISPATCH(128, 7, true);
-    VO_PRW_DISPATCH(128, 11, true);
-  }
-  if (K == 7) VO_PRW_DISPATCH(128, 7, false);
-  VO_PRW_DISPATCH(128, 11, false);
-#undef VO_PRW_DISPATCH
+    if (frag) return K == 7 ? prw_launch<128, 7, ACC, true>(a, B, st) : prw_launch<128, 11, ACC, true>(a, B, st);
+    return K == 7 ? prw_launch<128, 7, ACC, false>(a, B, st) : prw_launch<128, 11, ACC, false>(a, B, st);
+  });
 }
 
 // [K][C][C] bf16 conv pack -> the fragment order the pair kernel streams (NP = C / 32 planes):

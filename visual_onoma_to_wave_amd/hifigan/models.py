@@ -119,22 +119,22 @@ class ResBlock(HipModule):
         k, C = self.kernel_size, self.channels
         cur = x
         rag = {} if lens is None else dict(lens=lens, lens_scale=lens_scale)
+
+        def whole(op, *ksize):  # the whole ResBlock (three pairs) in one launch; x1 / x2 stay on chip
+            (w1s, b1s), (w2s, b2s) = zip(*[p[0] for p in packs]), zip(*[p[1] for p in packs])
+            return op(cur, w1s, b1s, w2s, b2s, *ksize, self.dilation, LRELU_SLOPE, out=out,
+                      out_scale=out_scale, acc=accumulate, tag=tag, **rag)
+
         if (RB3_ENABLED and k == 3 and len(self.dilation) == 3 and C in self.fused_pair_channels
                 and x.dtype == self.compute_dtype == torch.bfloat16
                 and sum(d + 1 for d in self.dilation) <= 12 and max(self.dilation) <= 8):
-            # k = 3: the whole ResBlock (three pairs) in one launch; x1 / x2 stay on chip
-            (w1s, b1s), (w2s, b2s) = zip(*[p[0] for p in packs]), zip(*[p[1] for p in packs])
-            return ops.resblock3(cur, w1s, b1s, w2s, b2s, self.dilation, LRELU_SLOPE, out=out,
-                                 out_scale=out_scale, acc=accumulate, tag=tag, **rag)
+            return whole(ops.resblock3)  # k = 3
         if (RBK_ENABLED and C == 32 and k in (7, 11) and self.dilation == (1, 3, 5)
                 and x.dtype == self.compute_dtype == torch.bfloat16):
-            # C = 32, k = 7 / 11: the whole ResBlock in one launch; x1 / x2 stay on chip.  Dense and ragged calls
-            # alike: a ragged batch equals its utterances run alone bit for bit only when both take the same kernel.
-            # None: the kernel does not cover the call (an MRF accumulator with 1 / out_scale not a bf16 value)
-            # and nothing ran
-            (w1s, b1s), (w2s, b2s) = zip(*[p[0] for p in packs]), zip(*[p[1] for p in packs])
-            y = ops.resblock_k(cur, w1s, b1s, w2s, b2s, k, self.dilation, LRELU_SLOPE, out=out,
-                               out_scale=out_scale, acc=accumulate, tag=tag, **rag)
+            # C = 32, k = 7 / 11.  Dense and ragged calls alike: a ragged batch equals its utterances run alone bit
+            # for bit only when both take the same kernel.  None: the kernel does not cover the call (an MRF
+            # accumulator with 1 / out_scale not a bf16 value) and nothing ran
+            y = whole(ops.resblock_k, k)
             if y is not None:
                 return y
         if C in self.fused_pair_channels and x.dtype == self.compute_dtype == torch.bfloat16:

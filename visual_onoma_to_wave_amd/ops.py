@@ -656,6 +656,46 @@ def resblock_pair(x, w1, b1, w2, b2, K, dil, slope=0.1, out=None, out_scale=1.0,
     return out
 
 
+VO_NOT_HANDLED = -2  # include/vonoma.h
+
+
+def _resblock_block(who, K, x, w1s, b1s, w2s, b2s, dils, slope, out, out_scale, acc, tag, lens, lens_scale):
+    """The body of ``resblock3`` (K = 3: vo_resblock3) and ``resblock_k`` (vo_resblockk, which takes K and may answer
+    VO_NOT_HANDLED -> None); ``who`` names the caller in the errors."""
+    whole = who == "resblock_k"
+    _contig(x, "x")
+    B, T, C = x.shape
+    if x.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in list(w1s) + list(w2s)):
+        raise TypeError(f"{who}: bf16 activations and packed bf16 weights")
+    if not (len(w1s) == len(b1s) == len(w2s) == len(b2s) == len(dils) == 3):
+        raise ValueError(f"{who}: three stages")
+    if whole and any(tuple(w.shape) != (K, C, C) for w in list(w1s) + list(w2s)):
+        raise ValueError(f"{who}: weights must be [K][C][C] packs")
+    out = out if out is not None else torch.empty_like(x)
+    if acc is not None and (acc.shape != x.shape or acc.dtype != x.dtype):
+        raise ValueError(f"{who}: acc must match x")
+    arr = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])  # noqa: E731
+    dil = (ctypes.c_int * 3)(*[int(d) for d in dils])
+    timer = profiling.active()
+    ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
+    name = ("vo_resblockk" if whole else "vo_resblock3") + ("" if lens is None else "_lens")
+    rag = () if lens is None else (_ptr(lens), _check_lens(lens, lens_scale, B, x, who))
+    kk = (int(K),) if whole else ()
+    rc = getattr(_lib.lib(), name)(_ptr(x), arr(w1s), arr(b1s), arr(w2s), arr(b2s), *kk, dil, _ptr(out), _ptr(acc),
+                                   B, T, C, float(slope), float(out_scale), _stream(x), *rag)
+    if whole and rc == VO_NOT_HANDLED:  # nothing ran; the start event (if any) is dropped unpaired
+        return None
+    _lib.check(rc, name)
+    if ev is not None:
+        flops = 3 * 2.0 * 2.0 * B * T * C * C * K
+        nbytes = 2.0 * x.numel() * 2 + (x.numel() * 2 if acc is not None else 0) + 6 * w1s[0].numel() * 2
+        if whole:  # booked as the three pair launches it stands for (profiling.py: launch units)
+            timer.stop(tag, ev, flops, nbytes, kernel=f"mrf_pbk_kernel<K={K}, ...>", launches=3)
+        else:
+            timer.stop(tag, ev, flops, nbytes, kernel=f"mrf_rb3_kernel<C={C}, ...>")
+    return out
+
+
 def resblock3(x, w1s, b1s, w2s, b2s, dils, slope=0.1, out=None, out_scale=1.0, acc=None, tag=None, lens=None,
               lens_scale=1):
     """A whole K = 3 ResBlock1 (three (c1_d, c2) pairs) in one launch (vo_resblock3):
@@ -663,31 +703,8 @@ def resblock3(x, w1s, b1s, w2s, b2s, dils, slope=0.1, out=None, out_scale=1.0, a
     [3][C][C] bf16 weights each, b1s / b2s three fp32 biases, dils the three dilations.
     ``lens`` / ``lens_scale`` (ragged batch, as ``conv1d``): rows past R_b read as zero -- x, acc and the on-chip
     T1, x_1, x_2 -- and rows >= R_b of ``out`` are not written.  The timer's FLOPs stay those of the padded shape."""
-    _contig(x, "x")
-    B, T, C = x.shape
-    if x.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in list(w1s) + list(w2s)):
-        raise TypeError("resblock3: bf16 activations and packed bf16 weights")
-    if not (len(w1s) == len(b1s) == len(w2s) == len(b2s) == len(dils) == 3):
-        raise ValueError("resblock3: three stages")
-    out = out if out is not None else torch.empty_like(x)
-    if acc is not None and (acc.shape != x.shape or acc.dtype != x.dtype):
-        raise ValueError("resblock3: acc must match x")
-    arr = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])  # noqa: E731
-    dil = (ctypes.c_int * 3)(*[int(d) for d in dils])
-    timer = profiling.active()
-    ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
-    name = "vo_resblock3" if lens is None else "vo_resblock3_lens"
-    rag = () if lens is None else (_ptr(lens), _check_lens(lens, lens_scale, B, x, "resblock3"))
-    _lib.check(getattr(_lib.lib(), name)(_ptr(x), arr(w1s), arr(b1s), arr(w2s), arr(b2s), dil, _ptr(out), _ptr(acc),
-                                         B, T, C, float(slope), float(out_scale), _stream(x), *rag), name)
-    if ev is not None:
-        flops = 3 * 2.0 * 2.0 * B * T * C * C * 3
-        nbytes = 2.0 * x.numel() * 2 + (x.numel() * 2 if acc is not None else 0) + 6 * w1s[0].numel() * 2
-        timer.stop(tag, ev, flops, nbytes, kernel=f"mrf_rb3_kernel<C={C}, ...>")
-    return out
-
-
-VO_NOT_HANDLED = -2  # include/vonoma.h
+    return _resblock_block("resblock3", 3, x, w1s, b1s, w2s, b2s, dils, slope, out, out_scale, acc, tag, lens,
+                           lens_scale)
 
 
 def resblock_k_tile_rows(K):
@@ -722,34 +739,8 @@ def resblock_k(x, w1s, b1s, w2s, b2s, K, dils, slope=0.1, out=None, out_scale=1.
     T1, x_1, x_2 -- and rows >= R_b of ``out`` are not written.  The timer's FLOPs stay those of the padded shape;
     under ``tag`` the launch counts as three launch units (the pairs it replaces), with the block's whole FLOPs
     and algorithmic bytes."""
-    _contig(x, "x")
-    B, T, C = x.shape
-    if x.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 for w in list(w1s) + list(w2s)):
-        raise TypeError("resblock_k: bf16 activations and packed bf16 weights")
-    if not (len(w1s) == len(b1s) == len(w2s) == len(b2s) == len(dils) == 3):
-        raise ValueError("resblock_k: three stages")
-    if any(tuple(w.shape) != (K, C, C) for w in list(w1s) + list(w2s)):
-        raise ValueError("resblock_k: weights must be [K][C][C] packs")
-    out = out if out is not None else torch.empty_like(x)
-    if acc is not None and (acc.shape != x.shape or acc.dtype != x.dtype):
-        raise ValueError("resblock_k: acc must match x")
-    arr = lambda ts: (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])  # noqa: E731
-    dil = (ctypes.c_int * 3)(*[int(d) for d in dils])
-    timer = profiling.active()
-    ev = timer.start() if (tag is not None and timer is not None and timer.watching(tag)) else None
-    name = "vo_resblockk" if lens is None else "vo_resblockk_lens"
-    rag = () if lens is None else (_ptr(lens), _check_lens(lens, lens_scale, B, x, "resblock_k"))
-    rc = getattr(_lib.lib(), name)(_ptr(x), arr(w1s), arr(b1s), arr(w2s), arr(b2s), int(K), dil, _ptr(out), _ptr(acc),
-                                   B, T, C, float(slope), float(out_scale), _stream(x), *rag)
-    if rc == VO_NOT_HANDLED:  # nothing ran; the start event (if any) is dropped unpaired
-        return None
-    _lib.check(rc, name)
-    if ev is not None:
-        flops = 3 * 2.0 * 2.0 * B * T * C * C * K
-        nbytes = 2.0 * x.numel() * 2 + (x.numel() * 2 if acc is not None else 0) + 6 * w1s[0].numel() * 2
-        # booked as the three pair launches it stands for (profiling.py: launch units)
-        timer.stop(tag, ev, flops, nbytes, kernel=f"mrf_pbk_kernel<K={K}, ...>", launches=3)
-    return out
+    return _resblock_block("resblock_k", K, x, w1s, b1s, w2s, b2s, dils, slope, out, out_scale, acc, tag, lens,
+                           lens_scale)
 
 
 # ----------------------------------------------------------------------------- mel / STFT
