@@ -224,6 +224,9 @@ int vo_layernorm_bwd_drop(const void* x, int x_dtype, const void* res, int res_d
  * Scaled dot-product attention with key padding, H heads of d_k = D/H, over the fused
  * qkv activations (B, L, 3D) (columns [q | k | v], head h at h*d_k) -> out (B, L, D)
  * (head-concat columns h*d_k + d).  Keys t >= lens[b] are masked (-inf before softmax).
+ * Head sizes: d_k in {32, 64, 128} for any H >= 1, in VO_F32 and VO_BF16, on all four entry
+ * points below (hidden 256 with 8 / 4 / 2 heads, hidden 512 with 16 / 8 / 4); any other dk is
+ * VO_ERR_INVALID with a message naming the three sizes.
  * lens contract, for the forward, the backward and their _lse forms alike: utterance b has
  * clamp(lens[b], 0, L) keys (a length past L masks nothing inside [0, L)); lens = NULL means L
  * keys everywhere; an utterance with no key has zero output rows and lse = +inf, and its

@@ -22,19 +22,24 @@
 
 namespace vo {
 
-constexpr int AB_DK = 128;
+// Every kernel is a template on the head size DK in {32, 64, 128} (D = H * DK): DK / 32 k-steps of 32 for the
+// products that sum over channels, DK / 16 accumulator tiles of 16 channels for dQ / dK / dV, DK / 8 eight-element
+// vectors per staged row.
 constexpr int AB_KT = 64;  // keys per tile (dq kernel) / keys per workgroup (dkdv kernel)
 
-// stage ROWS rows of 128 channels (channel offset `col` in rows of pitch `ld` starting at `row0`)
-// row-major into dst (pitch AB_DK + 8) and, if dst_t, transposed into dst_t[c][row] (pitch TP)
-template <typename TC, int ROWS, int TP>
+// stage ROWS rows of DK channels (channel offset `col` in rows of pitch `ld` starting at `row0`)
+// row-major into dst (pitch DK + 8) and, if dst_t, transposed into dst_t[c][row] (pitch TP).
+// ROWS * DK / 8 vectors over 256 threads: 32 rows of 32 channels are 128 vectors, so the last (only) trip is
+// guarded by the vector index wherever the count is no multiple of 256
+template <typename TC, int DK, int ROWS, int TP>
 __device__ __forceinline__ void ab_stage(const TC* __restrict__ src, int64_t ld, int row0, int nrows, int tid,
                                          TC* __restrict__ dst, TC* __restrict__ dst_t) {
-  constexpr int P = AB_DK + 8;
+  constexpr int P = DK + 8, VR = DK / 8, NV = ROWS * VR;
 #pragma unroll
-  for (int s = 0; s < ROWS * 16 / 256; ++s) {
+  for (int s = 0; s < (NV + 255) / 256; ++s) {
     const int v = tid + 256 * s;
-    const int r = v >> 4, c8 = (v & 15) * 8;
+    if (NV % 256 != 0 && v >= NV) break;
+    const int r = v / VR, c8 = (v % VR) * 8;
     float x[8];
     if (row0 + r < nrows)
       load8(src + (int64_t)(row0 + r) * ld + c8, x);
@@ -48,22 +53,23 @@ __device__ __forceinline__ void ab_stage(const TC* __restrict__ src, int64_t ld,
   }
 }
 
-template <typename TC>
+template <typename TC, int DK>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__ qkv, const TC* __restrict__ o,
                                                           const TC* __restrict__ dout,
                                                           const int32_t* __restrict__ lens, int L, int H,
                                                           float scale, TC* __restrict__ dqkv,
                                                           float* __restrict__ lse_ws, float* __restrict__ dd_ws,
                                                           int xcd) {
-  constexpr int KP = AB_DK + 8;
+  constexpr int KS = DK / 32, DT = DK / 16;
+  constexpr int KP = DK + 8;  // as attention_kernel's K tile: 2-way at worst for the fragment reads at every DK
   constexpr int TP = AB_KT + 8;
   __shared__ __attribute__((aligned(16))) TC k_lds[AB_KT * KP];
   __shared__ __attribute__((aligned(16))) TC v_lds[AB_KT * KP];
-  __shared__ __attribute__((aligned(16))) TC kt_lds[AB_DK * TP];
+  __shared__ __attribute__((aligned(16))) TC kt_lds[DK * TP];
   __shared__ __attribute__((aligned(16))) TC p_lds[4][16 * TP];
   __shared__ float dd_lds[4][16];
 
-  const int D = H * AB_DK;
+  const int D = H * DK;
   // the query tiles of one (b, h) read the same K / V: consecutive logical ids, one XCD's L2
   const int nq = gridDim.x, wid = blockIdx.x + nq * blockIdx.y;
   const int lid = xcd ? xcd_grouped_id(wid, nq * gridDim.y) : wid;
@@ -75,18 +81,18 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
   const int len = lens ? min(lens[b], L) : L;
   const int64_t rs = 3 * (int64_t)D;
   const TC* base = qkv + (int64_t)b * L * rs;
-  const TC* kbase = base + D + h * AB_DK;
-  const TC* vbase = base + 2 * D + h * AB_DK;
+  const TC* kbase = base + D + h * DK;
+  const TC* vbase = base + 2 * D + h * DK;
 
   // Q and dO fragments (A operands: row q, k = channel), D = rowsum(dO o O)
-  Frag<TC> qf[4], df[4];
+  Frag<TC> qf[KS], df[KS];
   float dpart = 0.f;
   {
     const int q = q0 + 16 * wave + lr;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
       if (q < L) {
-        const int c = h * AB_DK + 32 * ks + lk;
+        const int c = h * DK + 32 * ks + lk;
         qf[ks].load(base + (int64_t)q * rs + c);
         df[ks].load(dout + ((int64_t)b * L + q) * D + c);
         float ov[8], dv[8];
@@ -115,14 +121,14 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
   for (int kt = 0; kt < n_tiles; ++kt) {
     const int key0 = kt * AB_KT;
     __syncthreads();
-    ab_stage<TC, AB_KT, TP>(kbase, rs, key0, L, tid, k_lds, (TC*)nullptr);
+    ab_stage<TC, DK, AB_KT, TP>(kbase, rs, key0, L, tid, k_lds, (TC*)nullptr);
     __syncthreads();
     f32x4 s[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       s[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < KS; ++ks) {
         Frag<TC> kf;
         kf.load(k_lds + (16 * nt + lr) * KP + 32 * ks + lk);
         s[nt] = mfma(qf[ks], kf, s[nt]);
@@ -163,15 +169,15 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
   }
 
   // pass 2: P, dP, dS; dQ += dS K
-  f32x4 acc[8];
+  f32x4 acc[DT];
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   TC* pw = p_lds[wave];
   for (int kt = 0; kt < n_tiles; ++kt) {
     const int key0 = kt * AB_KT;
     __syncthreads();
-    ab_stage<TC, AB_KT, TP>(kbase, rs, key0, L, tid, k_lds, kt_lds);
-    ab_stage<TC, AB_KT, TP>(vbase, rs, key0, L, tid, v_lds, (TC*)nullptr);
+    ab_stage<TC, DK, AB_KT, TP>(kbase, rs, key0, L, tid, k_lds, kt_lds);
+    ab_stage<TC, DK, AB_KT, TP>(vbase, rs, key0, L, tid, v_lds, (TC*)nullptr);
     __syncthreads();
     f32x4 s[4], dp[4];
 #pragma unroll
@@ -179,7 +185,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
       s[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
       dp[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < KS; ++ks) {
         Frag<TC> kf, vf;
         kf.load(k_lds + (16 * nt + lr) * KP + 32 * ks + lk);
         vf.load(v_lds + (16 * nt + lr) * KP + 32 * ks + lk);
@@ -200,7 +206,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) sf[ks].load(pw + lr * TP + 32 * ks + lk);
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
+    for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         Frag<TC> kf;
@@ -212,30 +218,31 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const TC* __restrict__
   for (int r = 0; r < 4; ++r) {
     const int q = q0 + 16 * wave + 4 * g + r;
     if (q >= L) continue;
-    TC* row = dqkv + ((int64_t)b * L + q) * rs + h * AB_DK;
+    TC* row = dqkv + ((int64_t)b * L + q) * rs + h * DK;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) row[16 * dt + lr] = from_f32<TC>(acc[dt][r] * scale);
+    for (int dt = 0; dt < DT; ++dt) row[16 * dt + lr] = from_f32<TC>(acc[dt][r] * scale);
   }
 }
 
-template <typename TC, int QT>
+template <typename TC, int QT, int DK>
 __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict__ qkv, const TC* __restrict__ dout,
                                                             const int32_t* __restrict__ lens, int L, int H,
                                                             float scale, TC* __restrict__ dqkv,
                                                             const float* __restrict__ lse_ws,
                                                             const float* __restrict__ dd_ws, int xcd) {
-  constexpr int NT = QT / 16, KS = QT / 32;
-  constexpr int QP = AB_DK + 8;
+  constexpr int NT = QT / 16, KS = QT / 32;  // query tiles of 16 / query k-steps of 32
+  constexpr int CS = DK / 32, DT = DK / 16;  // channel k-steps of 32 / dK, dV tiles of 16 channels
+  constexpr int QP = DK + 8;
   constexpr int TP = QT + 8;
   __shared__ __attribute__((aligned(16))) TC q_lds[QT * QP];
   __shared__ __attribute__((aligned(16))) TC do_lds[QT * QP];
-  __shared__ __attribute__((aligned(16))) TC qt_lds[AB_DK * TP];
-  __shared__ __attribute__((aligned(16))) TC dot_lds[AB_DK * TP];
+  __shared__ __attribute__((aligned(16))) TC qt_lds[DK * TP];
+  __shared__ __attribute__((aligned(16))) TC dot_lds[DK * TP];
   __shared__ __attribute__((aligned(16))) TC pt_lds[4][16 * TP];
   __shared__ __attribute__((aligned(16))) TC st_lds[4][16 * TP];
   __shared__ float lse_s[QT], dd_s[QT];
 
-  const int D = H * AB_DK;
+  const int D = H * DK;
   // the key tiles of one (b, h) read the same Q / dO: consecutive logical ids, one XCD's L2
   const int nk = gridDim.x, wid = blockIdx.x + nk * blockIdx.y;
   const int lid = xcd ? xcd_grouped_id(wid, nk * gridDim.y) : wid;
@@ -248,21 +255,21 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
   const int64_t rs = 3 * (int64_t)D;
   const TC* base = qkv + (int64_t)b * L * rs;
 
-  f32x4 dk[8], dv[8];
+  f32x4 dk[DT], dv[DT];
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) {
+  for (int dt = 0; dt < DT; ++dt) {
     dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (k0 < len) {  // workgroup-uniform: a tile of padded keys only gets zero gradients
-    Frag<TC> kf[4], vf[4];
+    Frag<TC> kf[CS], vf[CS];
     {
       const int key = k0 + 16 * wave + lr;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < CS; ++ks) {
         if (key < L) {
-          kf[ks].load(base + (int64_t)key * rs + D + h * AB_DK + 32 * ks + lk);
-          vf[ks].load(base + (int64_t)key * rs + 2 * D + h * AB_DK + 32 * ks + lk);
+          kf[ks].load(base + (int64_t)key * rs + D + h * DK + 32 * ks + lk);
+          vf[ks].load(base + (int64_t)key * rs + 2 * D + h * DK + 32 * ks + lk);
         } else {
           kf[ks].zero();
           vf[ks].zero();
@@ -271,13 +278,13 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
     }
     TC* pw = pt_lds[wave];
     TC* sw = st_lds[wave];
-    const TC* dob = dout + (int64_t)b * L * D + h * AB_DK;
+    const TC* dob = dout + (int64_t)b * L * D + h * DK;
     const int n_qt = (L + QT - 1) / QT;
     for (int qt = 0; qt < n_qt; ++qt) {
       const int qb = qt * QT;
       __syncthreads();
-      ab_stage<TC, QT, TP>(base + h * AB_DK, rs, qb, L, tid, q_lds, qt_lds);
-      ab_stage<TC, QT, TP>(dob, D, qb, L, tid, do_lds, dot_lds);
+      ab_stage<TC, DK, QT, TP>(base + h * DK, rs, qb, L, tid, q_lds, qt_lds);
+      ab_stage<TC, DK, QT, TP>(dob, D, qb, L, tid, do_lds, dot_lds);
       if (tid < QT) {
         const int q = qb + tid;
         lse_s[tid] = q < L ? lse_ws[(int64_t)bh * L + q] : INFINITY;
@@ -291,7 +298,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
         st[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         dpt[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < CS; ++ks) {
           Frag<TC> qf, df;
           qf.load(q_lds + (16 * nt + lr) * QP + 32 * ks + lk);
           df.load(do_lds + (16 * nt + lr) * QP + 32 * ks + lk);
@@ -320,7 +327,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
         sf[ks].load(sw + lr * TP + 32 * ks + lk);
       }
 #pragma unroll
-      for (int dt = 0; dt < 8; ++dt)
+      for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           Frag<TC> a, c;
@@ -335,9 +342,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
   for (int r = 0; r < 4; ++r) {
     const int key = k0 + 16 * wave + 4 * g + r;
     if (key >= L) continue;
-    TC* row = dqkv + ((int64_t)b * L + key) * rs + h * AB_DK;
+    TC* row = dqkv + ((int64_t)b * L + key) * rs + h * DK;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
+    for (int dt = 0; dt < DT; ++dt) {
       row[D + 16 * dt + lr] = from_f32<TC>(dk[dt][r] * scale);
       row[2 * D + 16 * dt + lr] = from_f32<TC>(dv[dt][r]);
     }
@@ -357,7 +364,12 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const TC* __restrict
 // (k index 8 g + j <-> 32 ks + 4 g + j, j < 4; 32 ks + 16 + 4 g + j - 4, j >= 4), and the transposed
 // reads use the same order -- exactly attention2_kernel's O^T += V^T P^T.  K / V (Q / dO) tiles are
 // double-buffered in LDS, the next tile fetched into registers during the current one (one barrier).
-constexpr int AB2_P = AB_DK + 16;  // LDS row pitch (elements): 72 dwords = 8 mod 64 banks
+// LDS row pitch (elements) of the row-major tiles: (DK + 16) / 2 = 72 / 40 / 24 dwords, each 8 mod 16 --
+// attention2_kernel's pitch, with its bank arithmetic: the transposed reads (32-lane halves, 8 rows x 8 dwords, rows
+// 8 x {9, 5, 3} dwords apart) and the row fragment reads (ds_read_b128, 16-lane groups, rows 18 / 10 / 6 slots apart)
+// are conflict-free at every DK.  Rows stay 16-byte aligned (288 / 160 / 96 bytes), the transposed reads 8-byte aligned.
+template <int DK>
+constexpr int AB2_P = DK + 16;
 
 typedef unsigned int ab_u4 __attribute__((ext_vector_type(4)));
 typedef short ab_v4s __attribute__((ext_vector_type(4)));
@@ -366,10 +378,11 @@ typedef __attribute__((address_space(3))) ab_v4s ab_lds_v4s;
 
 // A fragment of X^T (rows d = 16 dt + lane row, k = the 32 rows 32 ks .. of the row-major LDS tile X, in
 // the accumulator order above)
+template <int P>
 __device__ __forceinline__ Frag<bf16_t> ab_tr_frag(const bf16_t* X, int ks, int dt, int g, int tq, int tp) {
-  const bf16_t* vb = X + (32 * ks + 4 * g + tq) * AB2_P + 16 * dt + 4 * tp;
+  const bf16_t* vb = X + (32 * ks + 4 * g + tq) * P + 16 * dt + 4 * tp;
   const ab_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)vb);
-  const ab_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)(vb + 16 * AB2_P));
+  const ab_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)(vb + 16 * P));
   Frag<bf16_t> f;
   f.v = __builtin_bit_cast(bf16x8, (ab_v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   return f;
@@ -383,15 +396,16 @@ __device__ __forceinline__ Frag<bf16_t> ab_acc_frag(const f32x4& a, const f32x4&
   return f;
 }
 
-template <int NONE = 0>
+template <int DK>
 __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                            const bf16_t* __restrict__ dout,
                                                            const int32_t* __restrict__ lens, int L, int H, float scale,
                                                            const float* __restrict__ lse, bf16_t* __restrict__ dqkv,
                                                            float* __restrict__ dd_ws, int xcd) {
-  constexpr int P = AB2_P, KT = AB_KT;
+  constexpr int P = AB2_P<DK>, KT = AB_KT;
+  constexpr int KS = DK / 32, DT = DK / 16, VR = DK / 8, NS = KT * VR / 256;  // NS: 16-byte vectors per thread and tile
   __shared__ __attribute__((aligned(16))) bf16_t kv_lds[2][2][KT * P];  // [buf][K | V][key][dk]
-  const int D = H * AB_DK;
+  const int D = H * DK;
   const int nq = gridDim.x, wid = blockIdx.x + nq * blockIdx.y;
   const int lid = xcd ? xcd_grouped_id(wid, nq * gridDim.y) : wid;
   const int bh = lid / nq;
@@ -401,17 +415,17 @@ __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restr
   const int lr = lane & 15, g = lane >> 4;
   const int len = min(lens ? lens[b] : L, L);
   const int64_t rs = 3 * (int64_t)D;
-  const bf16_t* base = qkv + (int64_t)b * L * rs + h * AB_DK;
+  const bf16_t* base = qkv + (int64_t)b * L * rs + h * DK;
 
   // Q^T / dO^T fragments (B operands): lane (g, lr) holds X[q = q0 + 16 wave + lr][32 ks + 8 g + j]
   const int qrow = q0 + 16 * wave + lr;
   const bool qok = qrow < L;
-  Frag<bf16_t> qf[4], df[4];
+  Frag<bf16_t> qf[KS], df[KS];
   float dpart = 0.f;
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
+  for (int ks = 0; ks < KS; ++ks) {
     if (qok) {
-      const int64_t off = ((int64_t)b * L + qrow) * D + h * AB_DK + 32 * ks + 8 * g;
+      const int64_t off = ((int64_t)b * L + qrow) * D + h * DK + 32 * ks + 8 * g;
       qf[ks].load(base + (int64_t)qrow * rs + 32 * ks + 8 * g);
       df[ks].load(dout + off);
       float ov[8], dv[8];
@@ -430,11 +444,11 @@ __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restr
   const float lq = qok ? lse[(int64_t)bh * L + qrow] : INFINITY;
   if (qok && g == 0) dd_ws[(int64_t)bh * L + qrow] = ddr;
 
-  ab_u4 kreg[4], vreg[4];
+  ab_u4 kreg[NS], vreg[NS];
   auto fetch = [&](int key0) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int v = tid + 256 * s, kr = v >> 4, c8 = (v & 15) * 8;
+    for (int s = 0; s < NS; ++s) {
+      const int v = tid + 256 * s, kr = v / VR, c8 = (v % VR) * 8;
       const int key = min(key0 + kr, L - 1);  // rows past L are masked by len <= L
       const bf16_t* rp = base + (int64_t)key * rs + c8;
       kreg[s] = *reinterpret_cast<const ab_u4*>(rp + D);
@@ -443,16 +457,16 @@ __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restr
   };
   auto stash = [&](int buf) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int v = tid + 256 * s, kr = v >> 4, c8 = (v & 15) * 8;
+    for (int s = 0; s < NS; ++s) {
+      const int v = tid + 256 * s, kr = v / VR, c8 = (v % VR) * 8;
       *reinterpret_cast<ab_u4*>(&kv_lds[buf][0][kr * P + c8]) = kreg[s];
       *reinterpret_cast<ab_u4*>(&kv_lds[buf][1][kr * P + c8]) = vreg[s];
     }
   };
 
-  f32x4 dq[8];  // dQ^T: lane (g, lr) holds dQ[q = lr][d = 16 dt + 4 g + r]
+  f32x4 dq[DT];  // dQ^T: lane (g, lr) holds dQ[q = lr][d = 16 dt + 4 g + r]
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int n_tiles = (len + KT - 1) / KT;
   if (n_tiles > 0) {
     fetch(0);
@@ -471,7 +485,7 @@ __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restr
       st[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
       dpt[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+      for (int ks = 0; ks < KS; ++ks) {
         Frag<bf16_t> kf, vf;
         kf.load(K + (16 * nt + lr) * P + 32 * ks + 8 * g);
         vf.load(V + (16 * nt + lr) * P + 32 * ks + 8 * g);
@@ -492,30 +506,31 @@ __global__ void __launch_bounds__(256) attn2_bwd_dq_kernel(const bf16_t* __restr
     for (int ks = 0; ks < 2; ++ks) {
       const Frag<bf16_t> sf = ab_acc_frag(st[2 * ks], st[2 * ks + 1]);
 #pragma unroll
-      for (int dt = 0; dt < 8; ++dt) dq[dt] = mfma(ab_tr_frag(K, ks, dt, g, tq, tp), sf, dq[dt]);
+      for (int dt = 0; dt < DT; ++dt) dq[dt] = mfma(ab_tr_frag<P>(K, ks, dt, g, tq, tp), sf, dq[dt]);
     }
     if (kt + 1 < n_tiles) stash(buf ^ 1);  // the other buffer was last read before the previous barrier
     __syncthreads();
   }
   if (!qok) return;
-  bf16_t* row = dqkv + ((int64_t)b * L + qrow) * rs + h * AB_DK;
+  bf16_t* row = dqkv + ((int64_t)b * L + qrow) * rs + h * DK;
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt)
+  for (int dt = 0; dt < DT; ++dt)
     *reinterpret_cast<uint2*>(row + 16 * dt + 4 * g) =
         make_uint2(pk_bf16(dq[dt][0] * scale, dq[dt][1] * scale), pk_bf16(dq[dt][2] * scale, dq[dt][3] * scale));
 }
 
-template <int V = 0>  // V = 2: the per-element lse / D reads under the padded-key branch (A/B, att_cfg 2)
+template <int V, int DK>  // V = 2: the per-element lse / D reads under the padded-key branch (A/B, att_cfg 2)
 __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv,
                                                              const bf16_t* __restrict__ dout,
                                                              const int32_t* __restrict__ lens, int L, int H,
                                                              float scale, const float* __restrict__ lse,
                                                              const float* __restrict__ dd_ws, bf16_t* __restrict__ dqkv,
                                                              int xcd) {
-  constexpr int P = AB2_P, QT = 64;
+  constexpr int P = AB2_P<DK>, QT = 64;
+  constexpr int KS = DK / 32, DT = DK / 16, VR = DK / 8, NS = QT * VR / 256;  // NS: 16-byte vectors per thread and tile
   __shared__ __attribute__((aligned(16))) bf16_t qd_lds[2][2][QT * P];  // [buf][Q | dO][query][dk]
   __shared__ __attribute__((aligned(16))) float ld_s[2][2][QT];        // [buf][lse | D][query]
-  const int D = H * AB_DK;
+  const int D = H * DK;
   const int nk = gridDim.x, wid = blockIdx.x + nk * blockIdx.y;
   const int lid = xcd ? xcd_grouped_id(wid, nk * gridDim.y) : wid;
   const int bh = lid / nk;
@@ -525,20 +540,20 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
   const int lr = lane & 15, g = lane >> 4;
   const int len = min(lens ? lens[b] : L, L);
   const int64_t rs = 3 * (int64_t)D;
-  const bf16_t* base = qkv + (int64_t)b * L * rs + h * AB_DK;
-  const bf16_t* dob = dout + (int64_t)b * L * D + h * AB_DK;
+  const bf16_t* base = qkv + (int64_t)b * L * rs + h * DK;
+  const bf16_t* dob = dout + (int64_t)b * L * D + h * DK;
   const int krow = k0 + 16 * wave + lr;
 
-  f32x4 dk[8], dv[8];  // dK^T / dV^T: lane (g, lr) holds [key = lr][d = 16 dt + 4 g + r]
+  f32x4 dk[DT], dv[DT];  // dK^T / dV^T: lane (g, lr) holds [key = lr][d = 16 dt + 4 g + r]
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) {
+  for (int dt = 0; dt < DT; ++dt) {
     dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (k0 < len) {  // workgroup-uniform: a tile of padded keys only gets zero gradients
-    Frag<bf16_t> kf[4], vf[4];  // K / V of key krow (B operands): [32 ks + 8 g + j]
+    Frag<bf16_t> kf[KS], vf[KS];  // K / V of key krow (B operands): [32 ks + 8 g + j]
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
       if (krow < L) {
         kf[ks].load(base + (int64_t)krow * rs + D + 32 * ks + 8 * g);
         vf[ks].load(base + (int64_t)krow * rs + 2 * D + 32 * ks + 8 * g);
@@ -548,12 +563,12 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
       }
     }
     const bool kok = krow < len;
-    ab_u4 qreg[4], dreg[4];
+    ab_u4 qreg[NS], dreg[NS];
     float lreg = 0.f, dsreg = 0.f;
     auto fetch = [&](int qb) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int v = tid + 256 * s, qr = v >> 4, c8 = (v & 15) * 8;
+      for (int s = 0; s < NS; ++s) {
+        const int v = tid + 256 * s, qr = v / VR, c8 = (v % VR) * 8;
         const int q = min(qb + qr, L - 1);  // rows past L: P = 0 through lse = +inf below
         qreg[s] = *reinterpret_cast<const ab_u4*>(base + (int64_t)q * rs + c8);
         dreg[s] = *reinterpret_cast<const ab_u4*>(dob + (int64_t)q * D + c8);
@@ -566,8 +581,8 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
     };
     auto stash = [&](int buf) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int v = tid + 256 * s, qr = v >> 4, c8 = (v & 15) * 8;
+      for (int s = 0; s < NS; ++s) {
+        const int v = tid + 256 * s, qr = v / VR, c8 = (v % VR) * 8;
         *reinterpret_cast<ab_u4*>(&qd_lds[buf][0][qr * P + c8]) = qreg[s];
         *reinterpret_cast<ab_u4*>(&qd_lds[buf][1][qr * P + c8]) = dreg[s];
       }
@@ -592,7 +607,7 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
         sc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {
           Frag<bf16_t> qf, df;
           qf.load(Q + (16 * nt + lr) * P + 32 * ks + 8 * g);
           df.load(dO + (16 * nt + lr) * P + 32 * ks + 8 * g);
@@ -633,9 +648,9 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
         const Frag<bf16_t> pf = ab_acc_frag(sc[2 * ks], sc[2 * ks + 1]);
         const Frag<bf16_t> sf = ab_acc_frag(dp[2 * ks], dp[2 * ks + 1]);
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
-          dv[dt] = mfma(ab_tr_frag(dO, ks, dt, g, tq, tp), pf, dv[dt]);
-          dk[dt] = mfma(ab_tr_frag(Q, ks, dt, g, tq, tp), sf, dk[dt]);
+        for (int dt = 0; dt < DT; ++dt) {
+          dv[dt] = mfma(ab_tr_frag<P>(dO, ks, dt, g, tq, tp), pf, dv[dt]);
+          dk[dt] = mfma(ab_tr_frag<P>(Q, ks, dt, g, tq, tp), sf, dk[dt]);
         }
       }
       if (qt + 1 < n_qt) stash(buf ^ 1);
@@ -643,9 +658,9 @@ __global__ void __launch_bounds__(256) attn2_bwd_dkdv_kernel(const bf16_t* __res
     }
   }
   if (krow >= L) return;
-  bf16_t* row = dqkv + ((int64_t)b * L + krow) * rs + h * AB_DK;
+  bf16_t* row = dqkv + ((int64_t)b * L + krow) * rs + h * DK;
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) {
+  for (int dt = 0; dt < DT; ++dt) {
     *reinterpret_cast<uint2*>(row + D + 16 * dt + 4 * g) =
         make_uint2(pk_bf16(dk[dt][0] * scale, dk[dt][1] * scale), pk_bf16(dk[dt][2] * scale, dk[dt][3] * scale));
     *reinterpret_cast<uint2*>(row + 2 * D + 16 * dt + 4 * g) =
@@ -661,32 +676,65 @@ extern "C" int64_t vo_attention_bwd_workspace_size(int B, int L, int H) {
   return 2 * (int64_t)B * H * L * (int64_t)sizeof(float);
 }
 
-extern "C" int vo_attention_bwd(const void* qkv, const void* out, const void* dout, int dtype, const int32_t* lens,
-                                int B, int L, int H, int dk, float scale, void* dqkv, void* workspace,
-                                void* stream) {
-  VO_CHECK_ARG(qkv && out && dout && dqkv && workspace, "attention_bwd: null pointer");
-  VO_CHECK_ARG(dk == AB_DK, "attention_bwd: d_k=%d unsupported (128)", dk);
-  VO_CHECK_ARG(B > 0 && L > 0 && H > 0, "attention_bwd: empty");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// d_k -> the instantiations: the one map, shared by both entry points
+#define AB_FOR_DK(dk, CALL)        \
+  switch (dk) {                    \
+    case 32: return CALL(32);      \
+    case 64: return CALL(64);      \
+    default: return CALL(128);     \
+  }
+#define AB_DK_OK(dk) ((dk) == 32 || (dk) == 64 || (dk) == 128)
+
+// the version-1 pair: rebuilds the row log-sum-exp itself (fp32; bf16 without lse or under att_cfg 1)
+template <int DK>
+static int attention_bwd_v1(const void* qkv, const void* out, const void* dout, int dtype, const int32_t* lens, int B,
+                            int L, int H, float scale, void* dqkv, void* workspace, hipStream_t st) {
   float* lse = (float*)workspace;
   float* dd = lse + (int64_t)B * H * L;
   dim3 grid((unsigned)((L + 63) / 64), (unsigned)(B * H));
   const int xcd = vo_tune_get("att_xcd") != 1;  // att_xcd 1: plain (tile, head) order (A/B)
   if (dtype == VO_BF16) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)out,
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<bf16_t, DK>), grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)out,
                        (const bf16_t*)dout, lens, L, H, scale, (bf16_t*)dqkv, lse, dd, xcd);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<bf16_t, 64>), grid, dim3(256), 0, st, (const bf16_t*)qkv,
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<bf16_t, 64, DK>), grid, dim3(256), 0, st, (const bf16_t*)qkv,
                        (const bf16_t*)dout, lens, L, H, scale, (bf16_t*)dqkv, (const float*)lse, (const float*)dd, xcd);
   } else if (dtype == VO_F32) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, grid, dim3(256), 0, st, (const float*)qkv, (const float*)out,
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<float, DK>), grid, dim3(256), 0, st, (const float*)qkv, (const float*)out,
                        (const float*)dout, lens, L, H, scale, (float*)dqkv, lse, dd, xcd);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<float, 32>), grid, dim3(256), 0, st, (const float*)qkv,
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<float, 32, DK>), grid, dim3(256), 0, st, (const float*)qkv,
                        (const float*)dout, lens, L, H, scale, (float*)dqkv, (const float*)lse, (const float*)dd, xcd);
   } else {
     vo_set_error("attention_bwd: bad dtype");
     return VO_ERR_INVALID;
   }
   VO_RETURN_LAUNCH();
+}
+
+// the version-2 pair (bf16): the forward's lse, D = rowsum(dO o O) in the workspace
+template <int DK>
+static int attention_bwd_v2(const void* qkv, const void* out, const void* dout, const int32_t* lens, int B, int L,
+                            int H, float scale, const float* lse, void* dqkv, void* workspace, hipStream_t st) {
+  float* dd = (float*)workspace;
+  dim3 grid((unsigned)((L + 63) / 64), (unsigned)(B * H));
+  const int xcd = vo_tune_get("att_xcd") != 1;
+  hipLaunchKernelGGL(attn2_bwd_dq_kernel<DK>, grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)out,
+                     (const bf16_t*)dout, lens, L, H, scale, lse, (bf16_t*)dqkv, dd, xcd);
+  auto dkdv = vo_tune_get("att_cfg") == 2 ? attn2_bwd_dkdv_kernel<2, DK> : attn2_bwd_dkdv_kernel<0, DK>;
+  hipLaunchKernelGGL(dkdv, grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lens,
+                     L, H, scale, lse, (const float*)dd, (bf16_t*)dqkv, xcd);
+  VO_RETURN_LAUNCH();
+}
+
+extern "C" int vo_attention_bwd(const void* qkv, const void* out, const void* dout, int dtype, const int32_t* lens,
+                                int B, int L, int H, int dk, float scale, void* dqkv, void* workspace,
+                                void* stream) {
+  VO_CHECK_ARG(qkv && out && dout && dqkv && workspace, "attention_bwd: null pointer");
+  VO_CHECK_ARG(AB_DK_OK(dk), "attention_bwd: d_k=%d unsupported (32, 64 or 128)", dk);
+  VO_CHECK_ARG(B > 0 && L > 0 && H > 0, "attention_bwd: empty");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define AB_CALL(N) attention_bwd_v1<N>(qkv, out, dout, dtype, lens, B, L, H, scale, dqkv, workspace, st)
+  AB_FOR_DK(dk, AB_CALL)
+#undef AB_CALL
 }
 
 // Backward with the forward's row log-sum-exp (vo_attention_lse): bf16 -> the version-2 kernels (no key
@@ -696,18 +744,12 @@ extern "C" int vo_attention_bwd_lse(const void* qkv, const void* out, const void
                                     int B, int L, int H, int dk, float scale, const float* lse, void* dqkv,
                                     void* workspace, void* stream) {
   VO_CHECK_ARG(qkv && out && dout && dqkv && workspace && lse, "attention_bwd_lse: null pointer");
-  VO_CHECK_ARG(dk == AB_DK, "attention_bwd_lse: d_k=%d unsupported (128)", dk);
+  VO_CHECK_ARG(AB_DK_OK(dk), "attention_bwd_lse: d_k=%d unsupported (32, 64 or 128)", dk);
   VO_CHECK_ARG(B > 0 && L > 0 && H > 0, "attention_bwd_lse: empty");
   if (dtype != VO_BF16 || vo_tune_get("att_cfg") == 1)  // att_cfg 1: the version-1 kernels (A/B)
     return vo_attention_bwd(qkv, out, dout, dtype, lens, B, L, H, dk, scale, dqkv, workspace, stream);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* dd = (float*)workspace;
-  dim3 grid((unsigned)((L + 63) / 64), (unsigned)(B * H));
-  const int xcd = vo_tune_get("att_xcd") != 1;
-  hipLaunchKernelGGL(attn2_bwd_dq_kernel<0>, grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)out,
-                     (const bf16_t*)dout, lens, L, H, scale, lse, (bf16_t*)dqkv, dd, xcd);
-  auto dkdv = vo_tune_get("att_cfg") == 2 ? attn2_bwd_dkdv_kernel<2> : attn2_bwd_dkdv_kernel<0>;
-  hipLaunchKernelGGL(dkdv, grid, dim3(256), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lens,
-                     L, H, scale, lse, (const float*)dd, (bf16_t*)dqkv, xcd);
-  VO_RETURN_LAUNCH();
+#define AB_CALL(N) attention_bwd_v2<N>(qkv, out, dout, lens, B, L, H, scale, lse, dqkv, workspace, st)
+  AB_FOR_DK(dk, AB_CALL)
+#undef AB_CALL
 }
