@@ -325,6 +325,24 @@ int vo_embed_bwd(const void* dy, int dy_dtype, const int32_t* idx, int64_t rows,
 int vo_vfe_stencil(const float* images, int B, int H, int W, int slice_w, int n_slices,
                    const float* conv, const float* bn, int n_layers, void* out, int out_dtype,
                    void* stream);
+/* The general glyph stencil (additive; vo_vfe_stencil stays the ICASSP path): context windows of `stride`
+ * cells (preprocess.yaml visual_text.stride) and kh x kw taps (model.yaml conv_kernel_size), kh, kw odd <= 9.
+ * host only: LDS bytes vo_vfe_stencil_ex needs for an H x win_w window (win_w = slice_w * stride);
+ * makes no HIP call (as vo_resblock3_tile_rows); -1 for a size below 1 */
+int64_t vo_vfe_stencil_lds_bytes(int H, int win_w, int kh, int kw);
+/* for every window (b, i), columns [i*slice_w, i*slice_w + slice_w*stride) of images (B, 1, H, W):
+ * n_layers x [Conv2d kh x kw, zero pad ((kh-1)/2, (kw-1)/2), 1 -> 1 ch -> y*scale + shift -> ReLU],
+ * flattened h*win_w + w into out (B*n_slices, H*win_w).  Each window is convolved on its own: every
+ * layer zero-pads at the window's edges, never reading a neighbouring window.
+ * conv: [n_layers][kh*kw + 1] (row-major taps, then bias); bn: [n_layers][2] = scale, shift
+ * (1, 0 when the module has no BatchNorm).  fp32: acc = bias, one fma per tap in row-major order,
+ * fma(acc, scale, shift), ReLU -- at 3 x 3, stride 1 bit-identical to vo_vfe_stencil.
+ * H <= 32; (n_slices - 1)*slice_w + slice_w*stride <= W; a window whose vo_vfe_stencil_lds_bytes
+ * exceed 160 KiB is refused with VO_ERR_INVALID and nothing is launched.
+ * Replaces: scripts/model/visual_feature_extractor.py:60-80 for any stride / kernel size. */
+int vo_vfe_stencil_ex(const float* images, int B, int H, int W, int slice_w, int stride, int n_slices,
+                      int kh, int kw, const float* conv, const float* bn, int n_layers,
+                      void* out, int out_dtype, void* stream);
 /* x[b, t, :] += pe[t, :] (pe nullable) + cls[idx, :] (cls nullable) with idx = cls_idx[b]
  * (idx_per_token = 0) or cls_idx[b*T + t] (idx_per_token = 1).
  * Replaces: position_enc add (Models.py:107-116, 184-186), audiotype_emb add (vtts.py:84-85)
@@ -622,7 +640,9 @@ int vo_lrelu_mask_sum(const void* g, int ldg, int g_dtype, const void* ref, int 
  * Replaces nn.BatchNorm1d/2d in training mode -- PostNet (scripts/transformer/Layers.py:129-137)
  * and the glyph encoder's single-channel BatchNorm2d (C = 1; scripts/model/
  * visual_feature_extractor.py:40-47).  vo_bn_bwd: dgamma = sum dy xhat, dbeta = sum dy,
- * dx = gamma rstd (dy - dbeta / M - xhat dgamma / M) (dx in x's dtype).  Deterministic. */
+ * dx = gamma rstd (dy - dbeta / M - xhat dgamma / M) (dx in x's dtype).  Deterministic.  At C = 1
+ * with M a multiple of the 16-byte vector the backward's sums and dx are formed in double (the workspace,
+ * 8-byte aligned, holds them as doubles) and rounded once. */
 int64_t vo_bn_workspace_size(int M, int C);
 int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const float* gamma, const float* beta, float eps,
                     float momentum, float* run_mean, float* run_var, int64_t* nbt, float* mean_rstd,
@@ -646,6 +666,14 @@ int64_t vo_vfe_conv_workspace_size(int N, int H, int W);
 int vo_vfe_conv_fwd(const float* x, int N, int H, int W, const float* w, float* y, void* stream);
 int vo_vfe_conv_bwd(const float* x, const float* dy, int N, int H, int W, const float* w, float* dx, float* dw,
                     float* workspace, void* stream);
+/* The same for Conv2d(1, 1, (kh, kw), padding ((kh-1)/2, (kw-1)/2)), kh, kw odd <= 9 (additive; the 3 x 3
+ * entries above stay the ICASSP path): w[kh*kw + 1] = row-major kernel, then the bias; dw[kh*kw + 1] alike.
+ * Per-block partials in the workspace, summed in a fixed order (bit-reproducible).  The size query
+ * returns -1 for arguments the entries refuse. */
+int64_t vo_vfe_conv_workspace_size_ex(int N, int H, int W, int kh, int kw);
+int vo_vfe_conv_fwd_ex(const float* x, int N, int H, int W, int kh, int kw, const float* w, float* y, void* stream);
+int vo_vfe_conv_bwd_ex(const float* x, const float* dy, int N, int H, int W, int kh, int kw, const float* w,
+                       float* dx, float* dw, float* workspace, void* stream);
 
 /* Backward of vo_stft_mel_ex (clip off; the HiFi-GAN V1 training mel-loss front end):
  * gmel (B, n_mels, F) = dL/dlogmel -> dwav (B, N) fp32 (written, not accumulated).  Per frame the

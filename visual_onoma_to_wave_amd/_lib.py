@@ -170,6 +170,9 @@ _SIGNATURES = {
     "vo_embed_bwd": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_int64, c_int, c_int, c_void_p, c_void_p]),
     "vo_vfe_stencil": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_int, c_void_p, c_int, c_void_p]),
+    "vo_vfe_stencil_lds_bytes": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
+    "vo_vfe_stencil_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "vo_add_pos_class": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_void_p]),
     "vo_mask_from_lengths": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -235,6 +238,10 @@ _SIGNATURES = {
     "vo_vfe_conv_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vo_vfe_conv_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
+    "vo_vfe_conv_workspace_size_ex": (ctypes.c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "vo_vfe_conv_fwd_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vo_vfe_conv_bwd_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
     "vo_stft_mel_bwd_workspace_size": (ctypes.c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "vo_stft_mel_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                 c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

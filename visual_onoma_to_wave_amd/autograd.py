@@ -13,7 +13,8 @@ The forward of every op is the same HIP kernel the inference path runs.  Backwar
 * LengthRegulator backward: HIP -- ``vo_length_regulate_bwd`` (segmented frame sums per token,
   deterministic);
 * training-mode BatchNorm (PostNet, glyph encoder) forward / backward and the glyph encoder's
-  3 x 3 conv forward / backward: HIP -- ``vo_bn_*`` and ``vo_vfe_conv_*`` (train_glue.hip).
+  kh x kw conv forward / backward: HIP -- ``vo_bn_*`` and ``vo_vfe_conv_*`` (3 x 3) / ``vo_vfe_conv_*_ex``
+  (train_glue.hip).
 
 All functions take and return channels-last (B, T, C) activations.
 """
@@ -516,10 +517,37 @@ class VfeConvFn(torch.autograd.Function):
         return dx, dw[:9].view(ctx.wshape), dw[9:]
 
 
+class VfeConvExFn(torch.autograd.Function):
+    """The glyph encoder's Conv2d(1, 1, (kh, kw), padding ((kh-1)/2, (kw-1)/2)) for odd kh, kw <= 9
+    (``vo_vfe_conv_fwd_ex`` / ``vo_vfe_conv_bwd_ex``)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        w = torch.cat([weight.detach().reshape(-1).float(), bias.detach().reshape(-1).float()])
+        xc = x.contiguous()
+        ctx.save_for_backward(xc, w)
+        ctx.wshape = weight.shape
+        return ops.vfe_conv_fwd_ex(xc, w, weight.shape[2], weight.shape[3])
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        kh, kw = ctx.wshape[2], ctx.wshape[3]
+        dx, dw = ops.vfe_conv_bwd_ex(x, gy.contiguous(), w, kh, kw)
+        return dx, dw[:kh * kw].view(ctx.wshape), dw[kh * kw:]
+
+
 def vfe_conv(x, conv):
-    if conv.weight.shape != (1, 1, 3, 3) or conv.bias is None or conv.padding != (1, 1) or conv.stride != (1, 1):
-        raise NotImplementedError("vfe_conv: the HIP path covers Conv2d(1, 1, 3, padding=1) with bias")
-    return VfeConvFn.apply(x, conv.weight, conv.bias)
+    shape = tuple(conv.weight.shape)
+    kh, kw = shape[2:] if len(shape) == 4 else (0, 0)
+    if (shape[:2] != (1, 1) or kh % 2 == 0 or kw % 2 == 0 or max(kh, kw) > ops.VFE_MAX_KERNEL or conv.bias is None or
+            tuple(conv.padding) != ((kh - 1) // 2, (kw - 1) // 2) or tuple(conv.stride) != (1, 1) or
+            tuple(conv.dilation) != (1, 1)):
+        raise NotImplementedError("vfe_conv: the HIP path covers Conv2d(1, 1, (kh, kw), padding=((kh-1)/2, (kw-1)/2)) "
+                                  f"with bias, stride 1 and odd kh, kw <= {ops.VFE_MAX_KERNEL}")
+    if (kh, kw) == (3, 3):
+        return VfeConvFn.apply(x, conv.weight, conv.bias)
+    return VfeConvExFn.apply(x, conv.weight, conv.bias)
 
 
 def length_regulate(x, dur, max_len, out_dtype=None):

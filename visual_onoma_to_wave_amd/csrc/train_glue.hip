@@ -362,7 +362,19 @@ __global__ void __launch_bounds__(256) bn_apply_v_kernel(const TX* __restrict__ 
   }
 }
 
-// backward partials per row block: part[block][c] = (sum dy, sum dy xhat)
+// one vector of dy beside a vector of x: the same width, or (x fp32, 4 per vector; dy bf16) an 8-byte load
+template <typename TX, typename TG>
+__device__ __forceinline__ void bn_load_dy(const TG* p, float (&gv)[BnVec<TX>::V]) {
+  if constexpr (sizeof(TG) == sizeof(TX)) {
+    BnVec<TG>::load(p, gv);
+  } else {
+    const uint2 u = *reinterpret_cast<const uint2*>(p);
+    gv[0] = __uint_as_float(u.x << 16); gv[1] = __uint_as_float(u.x & 0xffff0000u);
+    gv[2] = __uint_as_float(u.y << 16); gv[3] = __uint_as_float(u.y & 0xffff0000u);
+  }
+}
+
+// backward partials per row block: part[block][c] = (sum dy, sum dy xhat); FLAT: as doubles
 template <typename TX, typename TG, bool FLAT>
 __global__ void __launch_bounds__(256) bn_bwd_stats_v_kernel(const TX* __restrict__ x, const TG* __restrict__ dy,
                                                              int rows, int C, int RB,
@@ -374,10 +386,40 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_v_kernel(const TX* __restric
   const int CV = FLAT ? 1 : C / V, RL = 256 / CV;
   const int tid = threadIdx.x, vc = tid % CV, rl = tid / CV;
   const int r0 = blockIdx.x * RB, r1 = min(r0 + RB, rows);
+  if constexpr (FLAT) {
+    // C = 1 (the glyph encoder's maps): xhat, the products and both sums in double, the partials doubles too.
+    // Where another batch-statistics BatchNorm follows, d gamma is the small remainder of cancelling terms
+    // (sum |dy xhat| = 1700 |d gamma| at 2400 elements): fp32 terms and sums leave it 1e-5 off.
+    __shared__ double da[256], db[256];
+    const double mu = mean_rstd[0], rs = mean_rstd[1];
+    double a = 0., b = 0.;
+    for (int r = r0 + tid; r < r1; r += 256) {
+      const int64_t o = (int64_t)r * V;
+      float xv[V], gv[V];
+      BnVec<TX>::load(x + o, xv);
+      bn_load_dy<TX, TG>(dy + o, gv);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        a += (double)gv[e];
+        b = fma((double)gv[e], ((double)xv[e] - mu) * rs, b);
+      }
+    }
+    da[tid] = a; db[tid] = b;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {  // pairwise tree over the 256 lanes (fixed order)
+      if (tid < h) { da[tid] += da[tid + h]; db[tid] += db[tid + h]; }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      double* p = reinterpret_cast<double*>(part) + (int64_t)blockIdx.x * 2;
+      p[0] = da[0]; p[1] = db[0];
+    }
+    return;
+  }
   float mu[V], rs[V], a[V], b[V];
 #pragma unroll
   for (int e = 0; e < V; ++e) {
-    const int c = FLAT ? 0 : vc * V + e;
+    const int c = vc * V + e;
     mu[e] = mean_rstd[c]; rs[e] = mean_rstd[C + c];
     a[e] = b[e] = 0.f;
   }
@@ -386,35 +428,13 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_v_kernel(const TX* __restric
       const int64_t o = ((int64_t)r * CV + vc) * V;
       float xv[V], gv[V];
       BnVec<TX>::load(x + o, xv);
-      if constexpr (sizeof(TG) == sizeof(TX)) {
-        BnVec<TG>::load(dy + o, gv);
-      } else {  // x fp32 (4 per vector), dy bf16: 8-byte loads
-        const uint2 u = *reinterpret_cast<const uint2*>(dy + o);
-        gv[0] = __uint_as_float(u.x << 16); gv[1] = __uint_as_float(u.x & 0xffff0000u);
-        gv[2] = __uint_as_float(u.y << 16); gv[3] = __uint_as_float(u.y & 0xffff0000u);
-      }
+      bn_load_dy<TX, TG>(dy + o, gv);
 #pragma unroll
       for (int e = 0; e < V; ++e) {
         a[e] += gv[e];
         b[e] = fmaf(gv[e], (xv[e] - mu[e]) * rs[e], b[e]);
       }
     }
-  if (FLAT) {
-    float ta = 0.f, tb = 0.f;
-#pragma unroll
-    for (int e = 0; e < V; ++e) { ta += a[e]; tb += b[e]; }
-    sa[tid] = ta; sb[tid] = tb;
-    __syncthreads();
-    for (int h = 128; h >= 1; h >>= 1) {
-      if (tid < h) { sa[tid] += sa[tid + h]; sb[tid] += sb[tid + h]; }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      float* p = part + (int64_t)blockIdx.x * 2;
-      p[0] = sa[0]; p[1] = sb[0];
-    }
-    return;
-  }
 #pragma unroll
   for (int e = 0; e < V; ++e) { sa[tid * V + e] = a[e]; sb[tid * V + e] = b[e]; }
   __syncthreads();
@@ -458,17 +478,54 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_v_kernel(const float* __r
   dgamma[c] = b;
 }
 
+// FLAT: the nb <= BN_NB double partials summed by a fixed tree; tot = (sum dy, sum dy xhat) stays in double
+// for the apply kernel (one ulp of fp32 on d gamma of the second glyph BatchNorm is 3e-6 on the first's)
+__global__ void __launch_bounds__(BN_NB) bn_bwd_finalize_flat_kernel(const double* __restrict__ part, int nb,
+                                                                     float* __restrict__ dgamma,
+                                                                     float* __restrict__ dbeta, double* __restrict__ tot) {
+  __shared__ double sa[BN_NB], sb[BN_NB];
+  const int tid = threadIdx.x;
+  sa[tid] = tid < nb ? part[2 * tid] : 0.;
+  sb[tid] = tid < nb ? part[2 * tid + 1] : 0.;
+  __syncthreads();
+  for (int h = BN_NB / 2; h >= 1; h >>= 1) {
+    if (tid < h) { sa[tid] += sa[tid + h]; sb[tid] += sb[tid + h]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    tot[0] = sa[0]; tot[1] = sb[0];
+    dbeta[0] = (float)sa[0];
+    dgamma[0] = (float)sb[0];
+  }
+}
+
+// tot: FLAT only (bn_bwd_finalize_flat_kernel's sums)
 template <typename TX, typename TG, bool FLAT>
 __global__ void __launch_bounds__(256) bn_bwd_apply_v_kernel(const TX* __restrict__ x, const TG* __restrict__ dy,
                                                              int nvec, int C, float inv_m,
                                                              const float* __restrict__ mean_rstd,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ dgamma,
-                                                             const float* __restrict__ dbeta, TX* __restrict__ dx) {
+                                                             const float* __restrict__ dbeta,
+                                                             const double* __restrict__ tot, TX* __restrict__ dx) {
   constexpr int V = BnVec<TX>::V;
-  const int CV = FLAT ? 1 : C / V;
   const int i0 = blockIdx.x * 256 + threadIdx.x;
-  const int c0 = FLAT ? 0 : (i0 % CV) * V;
+  if constexpr (FLAT) {  // every element in double from the double sums, rounded once
+    const double im = 1. / ((double)nvec * V);
+    const double mu = mean_rstd[0], rs = mean_rstd[1], gr = (gamma ? (double)gamma[0] : 1.) * rs;
+    const double db = tot[0] * im, dg = tot[1] * im;
+    for (int i = i0; i < nvec; i += gridDim.x * 256) {
+      float xv[V], gv[V];
+      BnVec<TX>::load(x + (int64_t)i * V, xv);
+      bn_load_dy<TX, TG>(dy + (int64_t)i * V, gv);
+#pragma unroll
+      for (int e = 0; e < V; ++e) xv[e] = (float)(gr * ((double)gv[e] - db - ((double)xv[e] - mu) * rs * dg));
+      BnVec<TX>::store(dx + (int64_t)i * V, xv);
+    }
+    return;
+  }
+  const int CV = C / V;
+  const int c0 = (i0 % CV) * V;
   __shared__ float sp[5][BN_CMAX];  // per-channel parameters staged once per block (see bn_apply_v_kernel)
   for (int c = threadIdx.x; c < C; c += 256) {
     sp[0][c] = mean_rstd[c]; sp[1][c] = mean_rstd[C + c];
@@ -479,7 +536,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_v_kernel(const TX* __restric
   float mu[V], rs[V], gr[V], db[V], dg[V];  // gr = gamma rstd, db / dg = dbeta / M, dgamma / M
 #pragma unroll
   for (int e = 0; e < V; ++e) {
-    const int c = FLAT ? 0 : c0 + e;
+    const int c = c0 + e;
     mu[e] = sp[0][c]; rs[e] = sp[1][c]; gr[e] = sp[2][c]; db[e] = sp[3][c]; dg[e] = sp[4][c];
   }
   const int stride = gridDim.x * 256;
@@ -490,13 +547,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_v_kernel(const TX* __restric
       if (i + u * stride >= nvec) continue;
       const int64_t o = (int64_t)(i + u * stride) * V;
       BnVec<TX>::load(x + o, xv[u]);
-      if constexpr (sizeof(TG) == sizeof(TX)) {
-        BnVec<TG>::load(dy + o, gv[u]);
-      } else {
-        const uint2 q = *reinterpret_cast<const uint2*>(dy + o);
-        gv[u][0] = __uint_as_float(q.x << 16); gv[u][1] = __uint_as_float(q.x & 0xffff0000u);
-        gv[u][2] = __uint_as_float(q.y << 16); gv[u][3] = __uint_as_float(q.y & 0xffff0000u);
-      }
+      bn_load_dy<TX, TG>(dy + o, gv[u]);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -619,6 +670,87 @@ __global__ void vfe_conv_wgrad_finalize_kernel(const float* __restrict__ part, i
   const int k = blockIdx.x;
   float s = 0.f;
   for (int b = threadIdx.x; b < nb; b += 64) s += part[(int64_t)b * 10 + k];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) dw[k] = s;
+}
+
+// ------------------------------------------------------------------------------- kh x kw single-channel conv
+// The general Conv2d(1, 1, (kh, kw), padding ((kh-1)/2, (kw-1)/2)): w[kh kw + 1] = row-major taps, then the bias.
+
+constexpr int VC_MAXK = 9;
+constexpr int VC_MAXT = VC_MAXK * VC_MAXK + 1;  // partial sums per block: the taps and the bias
+
+__global__ void __launch_bounds__(VC_TILE) vfe_conv_fwd_ex_kernel(const float* __restrict__ x, int N, int H, int W,
+                                                                  int kh, int kw, const float* __restrict__ w,
+                                                                  float* __restrict__ y) {
+  const int64_t total = (int64_t)N * H * W;
+  const int64_t i = (int64_t)blockIdx.x * VC_TILE + threadIdx.x;
+  if (i >= total) return;
+  const int wq = (int)(i % W), hq = (int)((i / W) % H);
+  const int64_t base = i - (int64_t)hq * W - wq;
+  const int ph = (kh - 1) / 2, pw = (kw - 1) / 2;
+  // summed in double and rounded once: up to 81 taps, and the training path's BatchNorm gradients are cancelling
+  // sums that magnify every rounding of the maps (bn_bwd_stats_v_kernel)
+  double s = w[kh * kw];  // bias
+  for (int a = 0; a < kh; ++a) {
+    const int h = hq + a - ph;
+    if (h < 0 || h >= H) continue;
+    for (int b = 0; b < kw; ++b) {
+      const int ww = wq + b - pw;
+      if (ww >= 0 && ww < W) s = fma((double)w[a * kw + b], (double)x[base + (int64_t)h * W + ww], s);
+    }
+  }
+  y[i] = (float)s;
+}
+
+// dx[h, w] = sum_ab w[a][b] dy[h - (a - ph), w - (b - pw)]; per block and tap the partial
+// dW[a][b] = sum dy[h, w] x[h + a - ph, w + b - pw], one tap at a time: the wave reduction inside the tap loop,
+// so no per-tap register array
+__global__ void __launch_bounds__(VC_TILE) vfe_conv_bwd_ex_kernel(const float* __restrict__ x,
+                                                                  const float* __restrict__ dy, int N, int H, int W,
+                                                                  int kh, int kw, const float* __restrict__ w,
+                                                                  float* __restrict__ dx, float* __restrict__ part) {
+  __shared__ float red[VC_MAXT][VC_TILE / 64];
+  const int64_t total = (int64_t)N * H * W;
+  const int64_t i = (int64_t)blockIdx.x * VC_TILE + threadIdx.x;
+  const bool live = i < total;
+  const int64_t ic = live ? i : total - 1;
+  const int wq = (int)(ic % W), hq = (int)((ic / W) % H);
+  const int64_t base = ic - (int64_t)hq * W - wq;
+  const int ph = (kh - 1) / 2, pw = (kw - 1) / 2, nt = kh * kw;
+  const float g = live ? dy[ic] : 0.f;
+  const int wave = threadIdx.x >> 6;
+  const bool lead = (threadIdx.x & 63) == 0;
+  double s = 0.;  // dx in double, rounded once (as the forward)
+  for (int a = 0; a < kh; ++a)
+    for (int b = 0; b < kw; ++b) {
+      const int hx = hq + a - ph, wx = wq + b - pw;  // the x this pixel's dy multiplies for tap (a, b)
+      const int hy = hq - a + ph, wy = wq - b + pw;  // the dy that reached this pixel's x through tap (a, b)
+      float p = 0.f;
+      if (live && hx >= 0 && hx < H && wx >= 0 && wx < W) p = g * x[base + (int64_t)hx * W + wx];
+      if (live && hy >= 0 && hy < H && wy >= 0 && wy < W) s = fma((double)w[a * kw + b], (double)dy[base + (int64_t)hy * W + wy], s);
+      p = wave_sum(p);
+      if (lead) red[a * kw + b][wave] = p;
+    }
+  {
+    const float p = wave_sum(g);
+    if (lead) red[nt][wave] = p;
+  }
+  if (live) dx[i] = (float)s;
+  __syncthreads();
+  if ((int)threadIdx.x <= nt) {
+    float v = 0.f;
+    for (int q = 0; q < VC_TILE / 64; ++q) v += red[threadIdx.x][q];
+    part[(int64_t)blockIdx.x * (nt + 1) + threadIdx.x] = v;
+  }
+}
+
+__global__ void vfe_conv_wgrad_finalize_ex_kernel(const float* __restrict__ part, int nb, int nk,
+                                                  float* __restrict__ dw) {
+  // as vfe_conv_wgrad_finalize_kernel, nk partials per block
+  const int k = blockIdx.x;
+  float s = 0.f;
+  for (int b = threadIdx.x; b < nb; b += 64) s += part[(int64_t)b * nk + k];
   s = wave_sum(s);
   if (threadIdx.x == 0) dw[k] = s;
 }
@@ -891,8 +1023,8 @@ extern "C" int64_t vo_bn_workspace_size(int M, int C) {
   const int RB = C == 1 ? 8192 : 512;
   const int64_t nb = (M + RB - 1) / RB;
   (void)CT;
-  // (the vectorised kernels use at most BN_NB partials per channel)
-  return std::max<int64_t>(nb, BN_NB) * C * 3 * (int64_t)sizeof(float);
+  // (the vectorised kernels use at most BN_NB partials per channel; C = 1: the backward's are doubles)
+  return std::max<int64_t>(nb, BN_NB) * C * 3 * (int64_t)(C == 1 ? sizeof(double) : sizeof(float));
 }
 
 static void bn_geometry(int M, int C, int* CT, int* RB, int* nb) {
@@ -971,14 +1103,21 @@ extern "C" int vo_bn_bwd(const void* x, int x_dtype, const void* dy, int dy_dtyp
     const int nvec = (int)((int64_t)M * C / V);
     const unsigned ablk = bn_apply_blocks(nvec, flat ? 1 : C / V);
     const float inv_m = 1.f / (float)M;
+    // FLAT: the workspace as doubles -- BN_NB partial pairs, then the pair of totals
+    VO_CHECK_ARG(!flat || reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "bn_bwd: workspace must be 8-byte aligned");
+    double* tot = flat ? reinterpret_cast<double*>(workspace) + 2 * BN_NB : nullptr;
 #define VO_BNB_V(TX, TG, FL)                                                                                        \
   do {                                                                                                              \
     hipLaunchKernelGGL((bn_bwd_stats_v_kernel<TX, TG, FL>), dim3((unsigned)nbv), dim3(256), 0, st, (const TX*)x,     \
                        (const TG*)dy, rows, C, RBv, mean_rstd, workspace);                                          \
-    hipLaunchKernelGGL(bn_bwd_finalize_v_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, workspace, nbv,   \
-                       C, dgamma, dbeta);                                                                           \
+    if (FL)                                                                                                         \
+      hipLaunchKernelGGL(bn_bwd_finalize_flat_kernel, dim3(1), dim3(BN_NB), 0, st, (const double*)workspace, nbv,   \
+                         dgamma, dbeta, tot);                                                                       \
+    else                                                                                                            \
+      hipLaunchKernelGGL(bn_bwd_finalize_v_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, st, workspace,    \
+                         nbv, C, dgamma, dbeta);                                                                    \
     hipLaunchKernelGGL((bn_bwd_apply_v_kernel<TX, TG, FL>), dim3(ablk), dim3(256), 0, st, (const TX*)x,             \
-                       (const TG*)dy, nvec, C, inv_m, mean_rstd, gamma, dgamma, dbeta, (TX*)dx);                    \
+                       (const TG*)dy, nvec, C, inv_m, mean_rstd, gamma, dgamma, dbeta, (const double*)tot, (TX*)dx); \
   } while (0)
     if (x_dtype == VO_F32 && dy_dtype == VO_F32) {
       if (flat) VO_BNB_V(float, float, true); else VO_BNB_V(float, float, false);
@@ -1045,6 +1184,43 @@ extern "C" int vo_vfe_conv_bwd(const float* x, const float* dy, int N, int H, in
   const int nb = (int)((total + VC_TILE - 1) / VC_TILE);
   hipLaunchKernelGGL(vfe_conv_bwd_kernel, dim3((unsigned)nb), dim3(VC_TILE), 0, st, x, dy, N, H, W, w, dx, workspace);
   hipLaunchKernelGGL(vfe_conv_wgrad_finalize_kernel, dim3(10), dim3(64), 0, st, workspace, nb, dw);
+  VO_RETURN_LAUNCH();
+}
+
+// ---- the general glyph-encoder conv: kh x kw odd taps up to 9, w[kh kw + 1] = row-major kernel + bias
+static bool vfe_conv_ex_args(int N, int H, int W, int kh, int kw) {
+  return N > 0 && H > 0 && W > 0 && kh >= 1 && kw >= 1 && kh % 2 == 1 && kw % 2 == 1 && kh <= VC_MAXK && kw <= VC_MAXK &&
+         ((int64_t)N * H * W + VC_TILE - 1) / VC_TILE <= INT32_MAX;
+}
+
+extern "C" int64_t vo_vfe_conv_workspace_size_ex(int N, int H, int W, int kh, int kw) {
+  if (!vfe_conv_ex_args(N, H, W, kh, kw)) return -1;
+  const int64_t nb = ((int64_t)N * H * W + VC_TILE - 1) / VC_TILE;
+  return nb * (kh * kw + 1) * (int64_t)sizeof(float);
+}
+
+extern "C" int vo_vfe_conv_fwd_ex(const float* x, int N, int H, int W, int kh, int kw, const float* w, float* y,
+                                  void* stream) {
+  VO_CHECK_ARG(x && w && y, "vfe_conv_fwd_ex: null pointer");
+  VO_CHECK_ARG(vfe_conv_ex_args(N, H, W, kh, kw), "vfe_conv_fwd_ex: N=%d H=%d W=%d, kernel %dx%d (odd sizes up to %d)", N,
+               H, W, kh, kw, VC_MAXK);
+  const int64_t total = (int64_t)N * H * W;
+  hipLaunchKernelGGL(vfe_conv_fwd_ex_kernel, dim3((unsigned)((total + VC_TILE - 1) / VC_TILE)), dim3(VC_TILE), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, N, H, W, kh, kw, w, y);
+  VO_RETURN_LAUNCH();
+}
+
+extern "C" int vo_vfe_conv_bwd_ex(const float* x, const float* dy, int N, int H, int W, int kh, int kw, const float* w,
+                                  float* dx, float* dw, float* workspace, void* stream) {
+  VO_CHECK_ARG(x && dy && w && dx && dw && workspace, "vfe_conv_bwd_ex: null pointer");
+  VO_CHECK_ARG(vfe_conv_ex_args(N, H, W, kh, kw), "vfe_conv_bwd_ex: N=%d H=%d W=%d, kernel %dx%d (odd sizes up to %d)", N,
+               H, W, kh, kw, VC_MAXK);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t total = (int64_t)N * H * W;
+  const int nb = (int)((total + VC_TILE - 1) / VC_TILE), nk = kh * kw + 1;
+  hipLaunchKernelGGL(vfe_conv_bwd_ex_kernel, dim3((unsigned)nb), dim3(VC_TILE), 0, st, x, dy, N, H, W, kh, kw, w, dx,
+                     workspace);
+  hipLaunchKernelGGL(vfe_conv_wgrad_finalize_ex_kernel, dim3((unsigned)nk), dim3(64), 0, st, workspace, nb, nk, dw);
   VO_RETURN_LAUNCH();
 }
 

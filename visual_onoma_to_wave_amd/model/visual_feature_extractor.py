@@ -4,6 +4,12 @@ The strip (B, 1, 24, 102*T) is cut into T character slices by the kernel grid it
 (no Python slicing loop, no stacked copies); each slice runs 3 x [Conv2d 3x3 (1 -> 1
 channel) -> BatchNorm2d(eval) -> ReLU] in LDS (``vo_vfe_stencil``), then the bridge
 Linear(2448 -> 256) + ReLU runs as a K=1 MFMA conv over all B*T slices at once.
+
+That is the ICASSP configuration.  Every other gray-scale configuration of the reference's
+configs -- ``visual_text.stride`` s >= 1 (slice i is the context window of cells i .. i+s-1
+of the margin-padded strip), odd ``conv_kernel_size`` up to 9 x 9, any ``layer_num``,
+``embed_normalize`` / ``bridge_relu`` on or off -- runs through ``vo_vfe_stencil_ex`` (one
+workgroup per window, the whole window in LDS) and the same bridge.
 """
 
 import torch
@@ -40,21 +46,53 @@ class VisualFeatureExtractor(HipModule):
         for p in self.parameters():
             nn.init.uniform_(p, -0.08, 0.08)
 
+    @property
+    def _linear(self):
+        return self.bridge[0] if self.bridge_relu else self.bridge
+
+    def _icassp(self):
+        """Stride 1, 3 x 3, BatchNorm, bridge ReLU: the configuration ``vo_vfe_stencil`` was written for."""
+        return self.stride == 1 and self.kernel_size == (3, 3) and self.embed_normalize and self.bridge_relu
+
     def _supported(self):
-        if not (self.dim3 == 1 and self.stride == 1 and self.kernel_size == (3, 3) and
-                self.embed_normalize and self.bridge_relu):
-            raise NotImplementedError("the HIP VFE covers the ICASSP configuration (gray-scale, stride 1, "
-                                      "3x3 kernels, BatchNorm, bridge ReLU)")
+        kh, kw = self.kernel_size
+        H, win_w = self.slice_height, self.slice_width * self.stride
+        if self.dim3 != 1:
+            raise NotImplementedError("the HIP VFE covers gray-scale glyphs only (scale_in_training: RGB-scale is not "
+                                      "supported)")
+        if self.stride < 1 or self.num_convolutions < 1:
+            raise NotImplementedError(f"the HIP VFE needs stride >= 1 and layer_num >= 1, got {self.stride} and "
+                                      f"{self.num_convolutions}")
+        if min(kh, kw) < 1 or max(kh, kw) > ops.VFE_MAX_KERNEL:
+            raise NotImplementedError(f"the HIP VFE covers odd conv kernel sizes from 1 to {ops.VFE_MAX_KERNEL} in each "
+                                      f"dimension, got {self.kernel_size}")
+        if tuple(self.embedder[0].padding) != ((kh - 1) // 2, (kw - 1) // 2):
+            raise NotImplementedError(f"the HIP VFE pads ((kh-1)/2, (kw-1)/2), the module has "
+                                      f"{tuple(self.embedder[0].padding)}")
+        if H > ops.VFE_MAX_H:
+            raise NotImplementedError(f"the HIP VFE covers slice heights up to {ops.VFE_MAX_H}, got {H}")
+        if (H * win_w) % 8:
+            raise NotImplementedError(f"the HIP VFE bridge runs as a conv over slice_height * slice_width * stride = "
+                                      f"{H * win_w} input channels, which must be a multiple of 8")
+        if self._icassp() and self.slice_width <= 128:
+            return
+        lds = ops.vfe_stencil_lds_bytes(H, win_w, kh, kw)
+        if lds > ops.VFE_LDS_MAX:
+            raise NotImplementedError(f"the HIP VFE keeps a whole {H} x {win_w} context window (slice_width * stride "
+                                      f"columns) in LDS: {lds} B with a {kh} x {kw} kernel, over the "
+                                      f"{ops.VFE_LDS_MAX} B bound")
 
     def _build(self, device, dtype):
         convs, bns = [], []
         for m in self.embedder:
             if isinstance(m, nn.Conv2d):
                 convs.append(torch.cat([m.weight.detach().float().reshape(-1), m.bias.detach().float()]))
+                if not self.embed_normalize:
+                    bns.append(torch.tensor([1.0, 0.0], device=m.weight.device))
             elif isinstance(m, nn.BatchNorm2d):
                 s, sh = fold_bn(m)
                 bns.append(torch.cat([s, sh]))
-        lin = self.bridge[0]
+        lin = self._linear
         d = dict(conv=torch.stack(convs).to(device).contiguous(),
                  bn=torch.stack(bns).to(device).contiguous(),
                  w=ops.pack_conv_weight(lin.weight.to(device)[:, :, None], dtype),
@@ -73,30 +111,39 @@ class VisualFeatureExtractor(HipModule):
     def run(self, images, out_dtype=None):
         self._supported()
         p = self._packed(images.device, self._build)
-        flat, n = ops.vfe_stencil(images, p["conv"], p["bn"], self.slice_width, self.compute_dtype)
+        if self._icassp() and self.slice_width <= 128:
+            flat, n = ops.vfe_stencil(images, p["conv"], p["bn"], self.slice_width, self.compute_dtype)
+        else:
+            flat, n = ops.vfe_stencil_ex(images, p["conv"], p["bn"], self.slice_width, self.stride, self.kernel_size,
+                                         self.compute_dtype)
         B = images.shape[0]
         E = self.embed_dim
         if p.get("split", 1) > 1 and flat.shape[0] <= 4096:
             S = p["split"]
             part = ops.conv1d(flat.unsqueeze(0), p["wsplit"], None, Co=S * E, K=1, groups=S,
                               out_dtype=torch.float32, compute_dtype=self.compute_dtype)
-            y = torch.relu(part.view(-1, S, E).sum(1) + p["b"]).to(out_dtype or self.compute_dtype)
-            return y.view(B, n, E)
+            y = part.view(-1, S, E).sum(1) + p["b"]
+            if self.bridge_relu:
+                y = torch.relu(y)
+            return y.to(out_dtype or self.compute_dtype).view(B, n, E)
         y = ops.conv1d(flat.unsqueeze(0), p["w"], p["b"], Co=E, K=1,
-                       post_act=ops.ACT_RELU, out_dtype=out_dtype or self.compute_dtype,
-                       compute_dtype=self.compute_dtype)
+                       post_act=ops.ACT_RELU if self.bridge_relu else ops.ACT_NONE,
+                       out_dtype=out_dtype or self.compute_dtype, compute_dtype=self.compute_dtype)
         return y.view(B, n, E)
 
     def train_run(self, images, out_dtype):
         """Training forward (BatchNorm2d uses batch statistics, so the eval-folded stencil kernel
-        does not apply): the slices gathered into (B n, 1, 24, 102) maps, then conv (vo_vfe_conv),
-        BatchNorm with batch statistics (vo_bn_train_fwd), ReLU, and the bridge on HIP."""
+        does not apply): the overlapping context windows gathered into (B n, 1, H, slice_w * stride)
+        maps, then per layer conv (vo_vfe_conv / vo_vfe_conv_ex), BatchNorm with batch statistics
+        (vo_bn_train_fwd) where configured, ReLU, and the bridge on HIP."""
         from .. import autograd as AG
-        B, C, H, W = images.shape
-        n = int((W - (self.stride // 2) * self.slice_width * 2) / self.slice_width)
-        sl = images[..., : n * self.slice_width].reshape(B, C, H, n, self.slice_width)
-        x = sl.permute(0, 3, 1, 2, 4).reshape(B * n, C, H, self.slice_width)
         self._supported()
+        B, C, H, W = images.shape
+        win_w = self.slice_width * self.stride
+        n = int((W - (self.stride // 2) * self.slice_width * 2) / self.slice_width)
+        # window i = columns [i slice_w, i slice_w + win_w): (B, C, H, n, win_w) -> (B n, C, H, win_w)
+        win = images.unfold(3, win_w, self.slice_width)[:, :, :, :n]
+        x = win.permute(0, 3, 1, 2, 4).reshape(B * n, C, H, win_w)
         for m in self.embedder:
             if isinstance(m, nn.BatchNorm2d):
                 x = AG.batch_norm_train(x, m, (0, 2, 3))
@@ -104,8 +151,9 @@ class VisualFeatureExtractor(HipModule):
                 x = torch.relu(x)
             else:
                 x = AG.vfe_conv(x, m)
-        y = AG.linear(x.reshape(1, B * n, -1).to(out_dtype), self.bridge[0].weight, self.bridge[0].bias,
-                      relu=True, compute_dtype=out_dtype)
+        lin = self._linear
+        y = AG.linear(x.reshape(1, B * n, -1).to(out_dtype), lin.weight, lin.bias,
+                      relu=self.bridge_relu, compute_dtype=out_dtype)
         return y.view(B, n, self.embed_dim)
 
     def forward(self, images):

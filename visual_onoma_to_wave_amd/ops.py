@@ -553,6 +553,46 @@ def vfe_stencil(images, conv_params, bn_params, slice_w, out_dtype):
     return out, n
 
 
+VFE_LDS_MAX = 160 * 1024  # the window bound of vo_vfe_stencil_ex
+VFE_MAX_KERNEL = 9
+VFE_MAX_H = 32
+
+
+def vfe_stencil_lds_bytes(H, win_w, kh, kw):
+    """LDS bytes ``vfe_stencil_ex`` needs for an H x win_w window (host only: no GPU call)."""
+    return int(_lib.lib().vo_vfe_stencil_lds_bytes(int(H), int(win_w), int(kh), int(kw)))
+
+
+def vfe_stencil_ex(images, conv_params, bn_params, slice_w, stride, kernel_size, out_dtype, out=None):
+    """images (B, 1, H, W) fp32 -> (B*n, H*slice_w*stride): the context windows of ``stride`` cells at a
+    step of one cell, each through conv_params.shape[0] layers of kh x kw conv, scale / shift, ReLU.
+    conv_params [layers][kh*kw + 1], bn_params [layers][2].  n as the reference counts it
+    (scripts/model/visual_feature_extractor.py:67).  ``out``: a contiguous (B*n, H*slice_w*stride) tensor of
+    ``out_dtype`` to write instead of a new one."""
+    images = _contig(images.float(), "images")
+    B, C, H, W = images.shape
+    if C != 1:
+        raise ValueError("vfe_stencil_ex: gray-scale (1 channel) images only")
+    kh, kw = kernel_size
+    n = max(int((W - (stride // 2) * slice_w * 2) / slice_w), 0)
+    _contig(conv_params, "conv_params")
+    _contig(bn_params, "bn_params")
+    if conv_params.dim() != 2 or conv_params.shape[1] != kh * kw + 1 or bn_params.shape != (conv_params.shape[0], 2) \
+            or conv_params.dtype != torch.float32 or bn_params.dtype != torch.float32:
+        raise ValueError(f"vfe_stencil_ex: conv_params {tuple(conv_params.shape)} / bn_params {tuple(bn_params.shape)} "
+                         f"must be fp32 (layers, {kh * kw + 1}) and (layers, 2)")
+    if out is None:
+        out = torch.empty((B * n, H * slice_w * stride), dtype=out_dtype, device=images.device)
+    elif tuple(out.shape) != (B * n, H * slice_w * stride) or out.dtype != out_dtype or not out.is_contiguous() \
+            or out.device != images.device:
+        raise ValueError(f"vfe_stencil_ex: out must be a contiguous {(B * n, H * slice_w * stride)} {out_dtype} tensor "
+                         f"on {images.device}")
+    _lib.check(_lib.lib().vo_vfe_stencil_ex(_ptr(images), B, H, W, slice_w, stride, n, kh, kw, _ptr(conv_params),
+                                            _ptr(bn_params), conv_params.shape[0], _ptr(out), vo_dtype(out),
+                                            _stream(images)), "vo_vfe_stencil_ex")
+    return out, n
+
+
 def add_pos_class(x, pe=None, cls=None, cls_idx=None, per_token=False):
     """x (B, T, D) += pe[t] + cls[cls_idx[b]] (or cls[cls_idx[b, t]] when per_token), in place."""
     B, T, D = x.shape
@@ -931,6 +971,41 @@ def vfe_conv_bwd(x, gy, w10):
     ws = torch.empty(int(L.vo_vfe_conv_workspace_size(N, H, W)) // 4, dtype=torch.float32, device=x.device)
     _lib.check(L.vo_vfe_conv_bwd(_ptr(x), _ptr(gy), N, H, W, _ptr(w10), _ptr(dx), _ptr(dw), _ptr(ws), _stream(x)),
                "vo_vfe_conv_bwd")
+    return dx, dw
+
+
+def _vfe_taps(w, kh, kw, what):
+    _contig(w, "w")
+    if w.dtype != torch.float32 or w.numel() != kh * kw + 1:
+        raise ValueError(f"{what}: w must be {kh * kw + 1} fp32 values ({kh} x {kw} taps + bias), got {tuple(w.shape)}")
+
+
+def vfe_conv_fwd_ex(x, w, kh, kw):
+    """Conv2d(1, 1, (kh, kw), padding ((kh-1)/2, (kw-1)/2)): x (N, 1, H, W) fp32, w = kh*kw taps (row-major) + bias."""
+    N, H, W = _vfe_shape(x)
+    _vfe_taps(w, kh, kw, "vfe_conv_fwd_ex")
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().vo_vfe_conv_fwd_ex(_ptr(x), N, H, W, kh, kw, _ptr(w), _ptr(y), _stream(x)),
+               "vo_vfe_conv_fwd_ex")
+    return y
+
+
+def vfe_conv_bwd_ex(x, gy, w, kh, kw):
+    """Backward of ``vfe_conv_fwd_ex``: (dx, dw[kh*kw + 1])."""
+    N, H, W = _vfe_shape(x)
+    _vfe_taps(w, kh, kw, "vfe_conv_bwd_ex")
+    _contig(gy, "gy")
+    if gy.shape != x.shape or gy.dtype != torch.float32:
+        raise ValueError("vfe_conv_bwd_ex: gy must match x")
+    L = _lib.lib()
+    nbytes = int(L.vo_vfe_conv_workspace_size_ex(N, H, W, kh, kw))
+    if nbytes < 0:
+        raise ValueError(f"vfe_conv_bwd_ex: {N} x {H} x {W} maps with a {kh} x {kw} kernel unsupported (odd sizes up to 9)")
+    dx = torch.empty_like(x)
+    dw = torch.empty(kh * kw + 1, dtype=torch.float32, device=x.device)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    _lib.check(L.vo_vfe_conv_bwd_ex(_ptr(x), _ptr(gy), N, H, W, kh, kw, _ptr(w), _ptr(dx), _ptr(dw), _ptr(ws),
+                                    _stream(x)), "vo_vfe_conv_bwd_ex")
     return dx, dw
 
 
