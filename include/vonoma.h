@@ -303,6 +303,21 @@ typedef struct vo_head_desc {
   int32_t* idx_out;               /* optional bucket indices                  */
 } vo_head_desc;
 int vo_variance_head(const vo_head_desc* d, void* stream);
+/* vo_variance_head with a per-token multiplier read on the device: the multiplier of token
+ * (b, t) is control[b*stride_b + t*stride_t] (fp32, strides in floats, 0 = broadcast along that
+ * dimension).  It replaces d->d_control for VO_HEAD_DURATION and d->e_control for VO_HEAD_ENERGY
+ * (d's own field is ignored); with an energy target it is unused, as in the reference.  Every
+ * token's multiplier is loaded, pad tokens included.  n_control = the number of floats
+ * addressable from control: VO_ERR_INVALID, and nothing is launched, for a NULL control, a
+ * negative stride, (B-1)*stride_b + (T-1)*stride_t >= n_control (a view that would read past
+ * its storage) and whatever vo_variance_head refuses.  Control values are not validated: the
+ * duration's fmaxf maps a NaN product to 0 where torch.clamp keeps the NaN.  The pointer is
+ * read when the kernel runs, so a captured graph follows values changed in place.
+ * Replaces: the (B, T) e_control / d_control of vTTS.forward (scripts/model/vtts.py:68-69),
+ * broadcast in prediction * control (modules.py:53-64) and round(exp(log_d) - 1) * d_control
+ * (modules.py:110-113). */
+int vo_variance_head_ctl(const vo_head_desc* d, const float* control, int64_t n_control,
+                         int64_t stride_b, int64_t stride_t, void* stream);
 
 /* Training-side energy embedding (config C4, teacher-forced): idx = bucketize(target, bins)
  * (right=False; a NaN target -> n_bins, as torch.bucketize), out = x + table[idx] (out of place),

@@ -162,6 +162,7 @@ _SIGNATURES = {
                                        c_void_p]),
     "vo_lr_lengths": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vo_variance_head": (c_int, [ctypes.POINTER(HeadDesc), c_void_p]),
+    "vo_variance_head_ctl": (c_int, [ctypes.POINTER(HeadDesc), c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "vo_bucket_embed": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_int64,
                                 c_int, c_void_p, c_void_p, c_void_p]),
     "vo_adam_multi": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

@@ -464,7 +464,51 @@ def length_regulate_bwd(go, dur, T_src, out_dtype=torch.float32):
 
 # ----------------------------------------------------------------------------- variance heads
 
+def _is_number(c):
+    return isinstance(c, (int, float, np.integer, np.floating))
+
+
+def control_view(control, B, T, device=None):
+    """A per-token control as vo_variance_head_ctl takes it: ``(c, n_control, stride_b, stride_t)`` with ``c`` an
+    fp32 tensor whose first element is the multiplier of token (0, 0), the strides (in elements, 0 = broadcast) of
+    ``c.expand(B, T)`` and ``n_control`` the number of floats from that element to the end of what the view reaches.
+
+    ``control`` is whatever ``torch.broadcast_to(control, (B, T))`` accepts: 0-d, (1,), (T,), (1, T), (B, 1) or
+    (B, T), contiguous or not (nothing is materialised); any other shape raises ValueError.  Host only for an fp32
+    tensor: no GPU call is made and the values are never read.  Integer, fp64 and bf16 tensors, numpy arrays and
+    sequences are converted to fp32 on ``device`` (the activations' device) -- a copy on the current stream, so
+    such a call cannot be captured in a graph; an fp64 control is thereby rounded to fp32, where the reference
+    would promote its predictions to fp64.  A CUDA tensor on another device than ``device`` raises ValueError."""
+    if not isinstance(control, torch.Tensor):
+        control = torch.as_tensor(np.asarray(control))
+    device = control.device if device is None else torch.device(device)
+    if control.is_cuda and control.device != device:
+        raise ValueError(f"control is on {control.device}, the activations on {device}")
+    try:
+        if control.numel() == 0:
+            raise RuntimeError("empty")
+        control.expand(B, T)
+    except RuntimeError:
+        raise ValueError(f"control of shape {tuple(control.shape)} does not broadcast to (B, T) = ({B}, {T})") from None
+    if control.dtype != torch.float32 or control.device != device:
+        control = control.to(device=device, dtype=torch.float32)
+    sb, st = control.expand(B, T).stride()
+    return control, (B - 1) * sb + (T - 1) * st + 1, sb, st
+
+
+def _head_launch(d, h, control, B, T):
+    """vo_variance_head for a Python-number control (already in ``d``), vo_variance_head_ctl for a tensor one."""
+    if control is None:
+        _lib.check(_lib.lib().vo_variance_head(ctypes.byref(d), _stream(h)), "vo_variance_head")
+        return
+    c, n, sb, st = control_view(control, B, T, device=h.device)
+    _lib.check(_lib.lib().vo_variance_head_ctl(ctypes.byref(d), _ptr(c), n, sb, st, _stream(h)),
+               "vo_variance_head_ctl")
+
+
 def duration_head(h, w, b, lens, d_control=1.0, want_round=True):
+    """Duration prediction (+ rounding).  ``d_control``: a Python number, or a per-token control (``control_view``)
+    read on the device.  Returns (log_d, d_round)."""
     B, T, D = h.shape
     pred = torch.empty((B, T), dtype=torch.float32, device=h.device)
     dr = torch.empty((B, T), dtype=torch.float32, device=h.device) if want_round else None
@@ -476,15 +520,17 @@ def duration_head(h, w, b, lens, d_control=1.0, want_round=True):
     d.B, d.T, d.D = B, T, D
     d.pred = pred.data_ptr()
     d.d_round = dr.data_ptr() if dr is not None else None
-    d.d_control = float(d_control)
+    tensor_ctl = not _is_number(d_control)
+    d.d_control = 1.0 if tensor_ctl else float(d_control)
     d.x_dtype = vo_dtype(h)
-    _lib.check(_lib.lib().vo_variance_head(ctypes.byref(d), _stream(h)), "vo_variance_head")
+    _head_launch(d, h, d_control if tensor_ctl else None, B, T)
     return pred, dr
 
 
 def energy_head(h, w, b, lens, x, bins, table, target=None, mean=0.0, std=1.0, control=1.0,
                 want_index=False):
-    """Energy prediction + bucketize + x += table[idx] (in place).  Returns (pred, idx)."""
+    """Energy prediction + bucketize + x += table[idx] (in place).  ``control``: a Python number, or a per-token
+    control (``control_view``) read on the device; unused when ``target`` is given.  Returns (pred, idx)."""
     B, T, D = h.shape
     _contig(x, "x")
     pred = torch.empty((B, T), dtype=torch.float32, device=h.device)
@@ -499,11 +545,12 @@ def energy_head(h, w, b, lens, x, bins, table, target=None, mean=0.0, std=1.0, c
     d.pred = pred.data_ptr()
     d.target = tgt.data_ptr() if tgt is not None else None
     d.bins, d.n_bins = bins.data_ptr(), bins.numel()
-    d.e_mean, d.e_std, d.e_control = float(mean), float(std), float(control)
+    tensor_ctl = not _is_number(control)
+    d.e_mean, d.e_std, d.e_control = float(mean), float(std), 1.0 if tensor_ctl else float(control)
     d.table = table.data_ptr()
     d.x, d.x_dtype = x.data_ptr(), vo_dtype(x)
     d.idx_out = idx.data_ptr() if idx is not None else None
-    _lib.check(_lib.lib().vo_variance_head(ctypes.byref(d), _stream(h)), "vo_variance_head")
+    _head_launch(d, h, control if tensor_ctl else None, B, T)
     return pred, idx
 
 

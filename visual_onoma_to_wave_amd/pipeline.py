@@ -22,7 +22,7 @@ import torch
 
 
 class SynthesisPipeline:
-    """``submit(*model_args)`` starts the acoustic model of a batch; ``next_wav()`` vocodes the
+    """``submit(*model_args, **model_kwargs)`` starts the acoustic model of a batch; ``next_wav()`` vocodes the
     oldest submitted batch on the current stream and returns (acoustic outputs, wav (B, N)).
     ``ragged``: the vocoder runs each batch with the acoustic model's own ``mel_len`` (``out[9]``, on the device:
     no host read) as ``Generator.run``'s ``lengths`` -- the padded frames are not computed, and every waveform
@@ -34,14 +34,14 @@ class SynthesisPipeline:
         self.acoustic_stream = torch.cuda.Stream(self.device)
         self._pending = collections.deque()
 
-    def submit(self, *model_args):
+    def submit(self, *model_args, **model_kwargs):
         caller = torch.cuda.current_stream(self.device)
         self.acoustic_stream.wait_stream(caller)
-        for a in model_args:
+        for a in (*model_args, *model_kwargs.values()):  # keyword tensors too: e_control / d_control as (B, T) tensors
             if torch.is_tensor(a) and a.is_cuda:
                 a.record_stream(self.acoustic_stream)
         with torch.cuda.stream(self.acoustic_stream):
-            out = self.model(*model_args)
+            out = self.model(*model_args, **model_kwargs)
             ev = torch.cuda.Event()
             ev.record(self.acoustic_stream)
         self._pending.append((out, ev))
