@@ -628,6 +628,22 @@ int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void* b, int ldb
                          int M, int N, int K, int S, int dil, int pad, int groups, int pre_a,
                          int pre_b, float slope, int dtype, float* dw, float* db, float* workspace,
                          void* stream);
+/* Which kernel this thread's last vo_conv1d_wgrad[_grouped|_bias] call launched (host bookkeeping, zeroed at the
+ * call's entry: a rejected call reads as zeros).  Copies min(n, VO_CONV1D_WGRAD_LAUNCH_FIELDS) fields into rec
+ * and returns that count (0 for a null rec).  Fields, in order: ROUTE (1 per-tap kernel, 2 multi-tap kernel,
+ * 3 K = 1 kernel), TM (output tile: 64 / 32 or 64 / 128), KG (taps per run; 0 off the multi-tap route), SW (its
+ * window template 1 / 2 / 4; 0 off the multi-tap route), ntg (tap runs; 0 off the multi-tap route), gpt (groups
+ * per tile), splits (row splits), rows_per_split (multi-tap: 64 x chunks per split), direct (1: the kernel wrote
+ * dw / db in their final layout, no reduce ran), reduce_W (waves per output of the reduce: 16 or 1; 0 when
+ * direct), compute_dtype, bias.
+ * vo_conv1d_wgrad_plan launches nothing: the record vo_conv1d_wgrad_bias with the same sizes, flags and
+ * vo_tune knobs would leave (with_bias = a non-null db), from the routing code the launch itself runs.  Returns
+ * 0, or -1 with a zero record and vo_last_error for sizes the launch refuses; it leaves the last-launch
+ * record alone. */
+#define VO_CONV1D_WGRAD_LAUNCH_FIELDS 12
+int vo_conv1d_wgrad_last_launch(int32_t* rec, int n);
+int vo_conv1d_wgrad_plan(int B, int T_A, int T_B, int M, int N, int K, int S, int dil, int pad, int groups,
+                         int pre_a, int pre_b, int dtype, int with_bias, int32_t* rec, int n);
 int64_t vo_colsum_workspace_size(int64_t rows, int C);
 int vo_colsum(const void* x, int64_t rows, int C, int ld, int dtype, float* out, float* workspace, void* stream);
 

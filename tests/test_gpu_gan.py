@@ -615,12 +615,28 @@ def test_conv1d_wgrad_vs_torch(B, T, Ci, Co, K, dil, s, pad, pre, dt, tol):
     (8, 8192, 32, 32, 11, 5, 1, True, 0), (8, 8192, 32, 32, 3, 1, 1, False, 0), (16, 256, 256, 256, 11, 5, 1, True, 0),
     # ragged T (last chunk of each utterance partial), window at its 128-row limit, K > 10 split into runs
     (3, 777, 128, 64, 9, 8, 1, True, 0), (2, 1000, 32, 32, 11, 6, 1, False, 11), (2, 64, 1024, 1024, 41, 1, 16, False, 0),
-    # Ci = 1 padded to 8 (MSD's first conv), Linears (K = 1), T shorter than a chunk
-    (4, 4096, 8, 128, 15, 1, 1, True, 0), (2, 777, 1024, 256, 1, 1, 1, True, 0), (5, 12, 256, 256, 3, 1, 1, True, 0)])
+    # Ci = 1 padded to 8 (MSD's first conv)
+    (4, 4096, 8, 128, 15, 1, 1, True, 0)])
 def test_conv1d_wgrad_multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg):
     """The multi-tap weight gradient (stride-1 bf16: one staged dY chunk and x window per run of taps)
     against the per-tap kernel (vo_tune wgrad_mt 1) on the same bf16 operands -- fp32 sums of the same
-    products in different groupings: <= 1e-6 rel-L2 -- and against torch; deterministic run to run."""
+    products in different groupings: <= 1e-6 rel-L2 -- and against torch; deterministic run to run.  The
+    launch record says which kernel each run took: per-tap, then multi-tap with the forced taps per run."""
+    _multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg, (1, 2))
+
+
+@pytest.mark.parametrize("B,T,Ci,Co,K,dil,g,bias,kg,route", [
+    # Linears (K = 1): the K = 1 kernel whatever wgrad_mt says; T shorter than a chunk (T_A = 12 pads to 64, mostly
+    # padding): the per-tap kernel on both runs
+    (2, 777, 1024, 256, 1, 1, 1, True, 0, 3), (5, 12, 256, 256, 3, 1, 1, True, 0, 1)])
+def test_conv1d_wgrad_shapes_the_multitap_kernel_does_not_take(B, T, Ci, Co, K, dil, g, bias, kg, route):
+    """Shapes the routing keeps off the multi-tap kernel: both runs (wgrad_mt 1 and 0) take the same kernel -- the
+    launch record asserts which -- so the 1e-6 comparison is that kernel against itself (determinism across the
+    knob); the comparison with torch is the check of the values."""
+    _multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg, (route, route))
+
+
+def _multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg, routes):
     from visual_onoma_to_wave_amd import _lib, ops
     L = _lib.lib()
     gen = torch.Generator().manual_seed(B * T + K * dil + Ci)
@@ -633,12 +649,18 @@ def test_conv1d_wgrad_multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg):
     try:
         assert L.vo_tune(b"wgrad_mt", 1) == 0
         ref = ops.conv1d_wgrad(gya, xa, K, **kw)
+        rec_ref = ops.conv1d_wgrad_last_launch()
         assert L.vo_tune(b"wgrad_mt", 0) == 0 and L.vo_tune(b"wgrad_kg", kg) == 0
         got = ops.conv1d_wgrad(gya, xa, K, **kw)
+        rec_got = ops.conv1d_wgrad_last_launch()
         again = ops.conv1d_wgrad(gya, xa, K, **kw)
     finally:
         L.vo_tune(b"wgrad_mt", 0)
         L.vo_tune(b"wgrad_kg", 0)
+    assert (rec_ref["ROUTE"], rec_got["ROUTE"]) == routes, (rec_ref, rec_got)
+    assert ops.conv1d_wgrad_last_launch() == rec_got
+    if kg and routes[1] == 2:
+        assert rec_got["KG"] == kg, rec_got
     refw, gotw, agw = (ref[0], got[0], again[0]) if bias else (ref, got, again)
     assert torch.equal(gotw, agw)
     assert rel_l2(gotw.cpu(), refw.cpu()) < 1e-6, rel_l2(gotw.cpu(), refw.cpu())

@@ -27,10 +27,12 @@ def test_wgrad_k1_vs_per_tap_and_float64(B, T, Ci, Co, bias):
     try:
         assert L.vo_tune(b"wgrad_cfg", 14) == 0
         ref = ops.conv1d_wgrad(gya, xa, 1, with_bias=bias)
+        assert ops.conv1d_wgrad_last_launch()["ROUTE"] == ops.WGRAD_PER_TAP
         outs = []
         for cfg in (0, 15, 16):
             assert L.vo_tune(b"wgrad_cfg", cfg) == 0
             outs.append(ops.conv1d_wgrad(gya, xa, 1, with_bias=bias))
+            assert ops.conv1d_wgrad_last_launch()["ROUTE"] == ops.WGRAD_K1
         assert L.vo_tune(b"wgrad_cfg", 0) == 0
         again = ops.conv1d_wgrad(gya, xa, 1, with_bias=bias)
     finally:
@@ -83,10 +85,23 @@ def test_conv1d_bf16_split_reduction(B, T, Ci, Co, K, out_dt):
     (4, 4096, 128, 128, 41, 2, 4, 20), (4, 4096, 128, 256, 41, 2, 16, 20), (4, 2048, 256, 512, 41, 4, 16, 20),
     (3, 2731, 32, 128, 5, 3, 1, 2), (2, 1000, 64, 64, 7, 2, 1, 3), (2, 777, 128, 256, 41, 2, 16, 20),
     # short utterances (T_out 65..257, up to half of each chunk padding: many-tap convs only)
-    (8, 1025, 256, 512, 41, 4, 16, 20), (8, 257, 512, 1024, 41, 4, 16, 20), (4, 128, 1024, 1024, 41, 1, 16, 20)])
+    (8, 1025, 256, 512, 41, 4, 16, 20), (8, 257, 512, 1024, 41, 4, 16, 20)])
 def test_wgrad_multitap_strided_vs_per_tap(B, T, Ci, Co, K, S, g, pad):
     """Strided convs on the multi-tap kernel (window 64 S + 64 rows, B row = A row x S + tap) against the
-    per-tap kernel (wgrad_mt 2) on the same bf16 operands, <= 1e-6 rel-L2, and against torch; deterministic."""
+    per-tap kernel (wgrad_mt 2) on the same bf16 operands, <= 1e-6 rel-L2, and against torch; deterministic.
+    The launch record says which kernel each run took: per-tap, then multi-tap."""
+    _strided_vs_per_tap(B, T, Ci, Co, K, S, g, pad, 2)
+
+
+@pytest.mark.parametrize("B,T,Ci,Co,K,S,g,pad", [(4, 128, 1024, 1024, 41, 1, 16, 20)])
+def test_wgrad_multitap_short_stride1_vs_per_tap(B, T, Ci, Co, K, S, g, pad):
+    """The MSD's stride-1 many-tap layer at a short T_out: wgrad_mt 2 turns off only the strided multi-tap route, so
+    the per-tap reference of a stride-1 conv needs wgrad_mt 1 (under wgrad_mt 2 both runs were the multi-tap
+    kernel).  Same bars; the launch record asserts per-tap, then multi-tap."""
+    _strided_vs_per_tap(B, T, Ci, Co, K, S, g, pad, 1)
+
+
+def _strided_vs_per_tap(B, T, Ci, Co, K, S, g, pad, off):
     import torch.nn.functional as F
     from visual_onoma_to_wave_amd import _lib, ops
     L = _lib.lib()
@@ -97,10 +112,12 @@ def test_wgrad_multitap_strided_vs_per_tap(B, T, Ci, Co, K, S, g, pad):
     xa, gya = x.cuda(), gy.cuda()
     kw = dict(S=S, pad=pad, pre_b=0.1, groups=g)
     try:
-        assert L.vo_tune(b"wgrad_mt", 2) == 0
+        assert L.vo_tune(b"wgrad_mt", off) == 0
         ref = ops.conv1d_wgrad(gya, xa, K, **kw)
+        assert ops.conv1d_wgrad_last_launch()["ROUTE"] == ops.WGRAD_PER_TAP
         assert L.vo_tune(b"wgrad_mt", 0) == 0
         got = ops.conv1d_wgrad(gya, xa, K, **kw)
+        assert ops.conv1d_wgrad_last_launch()["ROUTE"] == ops.WGRAD_MULTI_TAP
         again = ops.conv1d_wgrad(gya, xa, K, **kw)
     finally:
         L.vo_tune(b"wgrad_mt", 0)

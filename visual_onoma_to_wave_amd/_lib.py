@@ -193,6 +193,8 @@ _SIGNATURES = {
     "vo_conv1d_wgrad_bias": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    "vo_conv1d_wgrad_plan": (c_int, [c_int] * 14 + [ctypes.POINTER(ctypes.c_int32), c_int]),
+    "vo_conv1d_wgrad_last_launch": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int]),
     "vo_lrelu_mask": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_int64, c_int, c_float,
                               c_void_p, c_int, c_void_p]),
     "vo_colsum_workspace_size": (c_int64, [c_int64, c_int]),

@@ -95,7 +95,7 @@ static const char* const kSymbols[] = {
     "vo_stft_mag_bwd_workspace_size", "vo_stft_mag_bwd", "vo_stft_loss", "vo_stft_loss_grad",
     "vo_bucket_embed",   "vo_embed_bwd",     "vo_adam_multi",  "vo_opt_step_increment",
     "vo_resblock_pair_frag", "vo_pack_frag", "vo_attention_lse", "vo_attention_bwd_lse", "vo_dropout",
-    "vo_conv1d_last_launch", "vo_conv1d_plan",
+    "vo_conv1d_last_launch", "vo_conv1d_plan", "vo_conv1d_wgrad_last_launch", "vo_conv1d_wgrad_plan",
     "vo_resblock_pair_lens", "vo_resblock_pair_frag_lens", "vo_resblock3_lens", "vo_conv_post_lens",
     "vo_resblockk", "vo_resblockk_lens", "vo_resblockk_tile_rows", "vo_resblock_pair_tile_rows", "vo_resblock3_tile_rows",
     "vo_vfe_stencil_lds_bytes", "vo_vfe_stencil_ex", "vo_vfe_conv_workspace_size_ex", "vo_vfe_conv_fwd_ex", "vo_vfe_conv_bwd_ex",

@@ -23,6 +23,7 @@
 // the same tiles with 16x16x4 f32 MFMAs.
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 #include "vo_common.h"
@@ -820,70 +821,79 @@ static void wgrad_mt_launch(const WgradArgs& p, const MtPlan& pl, int groups, hi
   hipLaunchKernelGGL((wgrad_mt_kernel<TM, KG, SW>), dim3((unsigned)pl.splits, (unsigned)tiles,
                      (unsigned)(pl.ntg * groups)), dim3(256), 0, st, p, pl.chunks_per_b, pl.cps, pl.ntg);
 }
+// the taps per run a (TM, SW) pair is instantiated for: TM 64 runs at most 8 taps, 5 when strided (wgrad_mt_plan)
+static int wgrad_mt_max_kg(int tm, int sw) { return tm == 32 ? 11 : sw == 1 ? 8 : 5; }
+
+// false: no instantiation for pl.kg, nothing launched (the caller must not reduce the unwritten workspace)
 template <int TM, int SW>
-static void wgrad_mt_dispatch(const WgradArgs& p, const MtPlan& pl, int groups, hipStream_t st) {
+static bool wgrad_mt_dispatch(const WgradArgs& p, const MtPlan& pl, int groups, hipStream_t st) {
   switch (pl.kg) {
-    case 1: return wgrad_mt_launch<TM, 1, SW>(p, pl, groups, st);
-    case 2: return wgrad_mt_launch<TM, 2, SW>(p, pl, groups, st);
-    case 3: return wgrad_mt_launch<TM, 3, SW>(p, pl, groups, st);
-    case 4: return wgrad_mt_launch<TM, 4, SW>(p, pl, groups, st);
-    case 5: return wgrad_mt_launch<TM, 5, SW>(p, pl, groups, st);
+    case 1: wgrad_mt_launch<TM, 1, SW>(p, pl, groups, st); return true;
+    case 2: wgrad_mt_launch<TM, 2, SW>(p, pl, groups, st); return true;
+    case 3: wgrad_mt_launch<TM, 3, SW>(p, pl, groups, st); return true;
+    case 4: wgrad_mt_launch<TM, 4, SW>(p, pl, groups, st); return true;
+    case 5: wgrad_mt_launch<TM, 5, SW>(p, pl, groups, st); return true;
   }
-  if constexpr (TM == 32 || SW == 1) {  // TM 64 runs at most 8 taps, 5 when strided (wgrad_mt_plan)
+  if constexpr (TM == 32 || SW == 1) {
     switch (pl.kg) {
-      case 6: return wgrad_mt_launch<TM, 6, SW>(p, pl, groups, st);
-      case 7: return wgrad_mt_launch<TM, 7, SW>(p, pl, groups, st);
-      case 8: return wgrad_mt_launch<TM, 8, SW>(p, pl, groups, st);
+      case 6: wgrad_mt_launch<TM, 6, SW>(p, pl, groups, st); return true;
+      case 7: wgrad_mt_launch<TM, 7, SW>(p, pl, groups, st); return true;
+      case 8: wgrad_mt_launch<TM, 8, SW>(p, pl, groups, st); return true;
     }
   }
   if constexpr (TM == 32) {
     switch (pl.kg) {
-      case 9: return wgrad_mt_launch<32, 9, SW>(p, pl, groups, st);
-      case 10: return wgrad_mt_launch<32, 10, SW>(p, pl, groups, st);
-      default: return wgrad_mt_launch<32, 11, SW>(p, pl, groups, st);
+      case 9: wgrad_mt_launch<32, 9, SW>(p, pl, groups, st); return true;
+      case 10: wgrad_mt_launch<32, 10, SW>(p, pl, groups, st); return true;
+      case 11: wgrad_mt_launch<32, 11, SW>(p, pl, groups, st); return true;
     }
   }
+  return false;
 }
 
-extern "C" int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M,
-                                    int N, int K, int S, int dil, int pad, int groups, int pre_a, int pre_b,
-                                    float slope, int dtype, float* dw, float* db, float* workspace, void* stream) {
-  VO_CHECK_ARG(a && b && dw && workspace, "conv1d_wgrad: null pointer");
-  VO_CHECK_ARG(!db || !pre_a, "conv1d_wgrad: the fused bias gradient sums A as stored (pre_a must be off)");
-  VO_CHECK_ARG(B > 0 && T_A > 0 && T_B > 0 && K >= 1 && S >= 1 && dil >= 1 && groups >= 1, "conv1d_wgrad: bad sizes");
+// Which kernel a vo_conv1d_wgrad_bias call takes and with what grid: every routing decision, host code without
+// a HIP call.  vo_conv1d_wgrad_plan runs it and stops there; the launch runs it and launches from the same
+// struct it records (wgrad_record), so the two cannot disagree.
+enum { WG_ROUTE_PER_TAP = 1, WG_ROUTE_MULTI_TAP = 2, WG_ROUTE_K1 = 3 };
+struct WgradRoute {
+  int route;       // WG_ROUTE_*
+  int dtype, bias;
+  int abl;         // timing ablation (wgrad_cfg 11), per-tap only
+  int gpt;         // per-tap: groups per tile
+  int tiles;       // per-tap / K = 1: grid y
+  int64_t zk;      // per-tap: grid z
+  int64_t splits;  // per-tap / K = 1 (multi-tap: mt.splits)
+  int rps;         // per-tap / K = 1: rows per split
+  bool direct;     // the kernel writes dW / db in their final layout, no reduce
+  MtPlan mt;
+  int sw;          // multi-tap: window template (1, 2, 4)
+};
+
+static int wgrad_route(int B, int T_A, int T_B, int M, int N, int K, int S, int dil, int pad, int groups, int lda,
+                       int ldb, int pre_a, int pre_b, int dtype, int with_bias, WgradRoute* r) {
+  VO_CHECK_ARG(!with_bias || !pre_a, "conv1d_wgrad: the fused bias gradient sums A as stored (pre_a must be off)");
+  VO_CHECK_ARG(B > 0 && T_A > 0 && T_B > 0 && M > 0 && N > 0 && K >= 1 && S >= 1 && dil >= 1 && groups >= 1,
+               "conv1d_wgrad: bad sizes");
   VO_CHECK_ARG(dtype == VO_BF16 || dtype == VO_F32 || (dtype == VO_F32X3 && S == 1 && groups == 1),
                "conv1d_wgrad: dtype %d (VO_F32X3: stride 1, ungrouped)", dtype);
   const int ev = dtype == VO_BF16 ? 8 : 4;
   VO_CHECK_ARG(M % ev == 0 && N % ev == 0 && lda % ev == 0 && ldb % ev == 0 && lda >= (int64_t)groups * M &&
                    ldb >= (int64_t)groups * N,
                "conv1d_wgrad: M=%d N=%d (per group, and leading dims) must be multiples of %d", M, N, ev);
-  WgradArgs p;
-  p.a = a; p.lda = lda; p.T_A = T_A; p.bsrc = b; p.ldb = ldb; p.T_B = T_B;
-  p.M = M; p.N = N; p.K = K; p.S = S; p.dil = dil; p.pad = pad; p.Bn = B;
-  p.pre_a = pre_a; p.pre_b = pre_b; p.slope = slope;
-  p.part = workspace;
-  p.bias = db != nullptr;
-  p.n_w = (int64_t)groups * K * M * N;
-  p.n_tot = p.n_w + (db ? (int64_t)groups * M : 0);
-  p.abl = vo_tune_get("wgrad_cfg") == 11 ? 2 : 0;  // 11: no loads (timing)
-  p.gpt = 1;
-  p.dwf = p.dbf = nullptr;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  *r = WgradRoute{};
+  r->dtype = dtype;
+  r->bias = with_bias != 0;
+  r->gpt = 1;
+  r->abl = vo_tune_get("wgrad_cfg") == 11 ? 2 : 0;  // 11: no loads (timing)
   // K = 1 (Linear layers, bf16): the 128 x 128 tile kernel (wgrad_cfg 14 = the per-tap kernel, A/B)
   if (dtype == VO_BF16 && K == 1 && S == 1 && pad == 0 && groups == 1 && !pre_a && !pre_b && T_A == T_B &&
-      vo_tune_get("wgrad_cfg") != 14 && p.abl == 0) {
-    int64_t splits;
-    k1_plan(B, T_A, M, N, &splits, &p.rows_per_split);
-    const int tiles = ((M + K1_T - 1) / K1_T) * ((N + K1_T - 1) / K1_T);
-    VO_CHECK_ARG(splits < (1 << 30) && tiles < 65536, "conv1d_wgrad: grid too large");
-    const bool direct = splits == 1;
-    if (direct) {
-      p.dwf = dw;
-      p.dbf = db;
-    }
-    hipLaunchKernelGGL(wgrad_k1_kernel, dim3((unsigned)splits, (unsigned)tiles), dim3(256), 0, st, p);
-    if (!direct) wgrad_reduce_launch(workspace, (int)splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
-    VO_RETURN_LAUNCH();
+      vo_tune_get("wgrad_cfg") != 14 && r->abl == 0) {
+    r->route = WG_ROUTE_K1;
+    k1_plan(B, T_A, M, N, &r->splits, &r->rps);
+    r->tiles = ((M + K1_T - 1) / K1_T) * ((N + K1_T - 1) / K1_T);
+    VO_CHECK_ARG(r->splits < (1 << 30) && r->tiles < 65536, "conv1d_wgrad: grid too large");
+    r->direct = r->splits == 1;
+    return VO_OK;
   }
   // stride-1 bf16 convs: the multi-tap kernel (wgrad_mt 1 = the per-tap kernel, A/B)
   // (K >= 2 and utterances of >= 8 whole chunks' worth: the per-utterance chunks of short sequences --
@@ -897,40 +907,111 @@ extern "C" int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void*
                                 (K >= 16 && padded <= 2 * (int64_t)T_A && vo_tune_get("wgrad_mt") != 3));
   // strided convs (S <= 4: the MSD's grouped layers) on the multi-tap kernel's wider windows (wgrad_mt 2 = off)
   const bool mt_stride = S == 1 || (S <= 4 && vo_tune_get("wgrad_mt") != 2);
-  if (dtype == VO_BF16 && mt_stride && mt_ok && vo_tune_get("wgrad_mt") != 1 && p.abl == 0) {
-    MtPlan pl;
-    wgrad_mt_plan(B, T_A, M, N, K, groups, dil, &pl, S);
-    VO_CHECK_ARG(pl.splits < (1 << 30) && pl.ntg * groups < 65536, "conv1d_wgrad: grid too large");
-    if (S == 1)
-      pl.tm == 32 ? wgrad_mt_dispatch<32, 1>(p, pl, groups, st) : wgrad_mt_dispatch<64, 1>(p, pl, groups, st);
-    else if (S == 2)
-      pl.tm == 32 ? wgrad_mt_dispatch<32, 2>(p, pl, groups, st) : wgrad_mt_dispatch<64, 2>(p, pl, groups, st);
-    else
-      pl.tm == 32 ? wgrad_mt_dispatch<32, 4>(p, pl, groups, st) : wgrad_mt_dispatch<64, 4>(p, pl, groups, st);
-    wgrad_reduce_launch(workspace, pl.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
-    VO_RETURN_LAUNCH();
+  if (dtype == VO_BF16 && mt_stride && mt_ok && vo_tune_get("wgrad_mt") != 1 && r->abl == 0) {
+    r->route = WG_ROUTE_MULTI_TAP;
+    wgrad_mt_plan(B, T_A, M, N, K, groups, dil, &r->mt, S);
+    r->sw = S == 1 ? 1 : S == 2 ? 2 : 4;
+    VO_CHECK_ARG(r->mt.splits < (1 << 30) && r->mt.ntg * groups < 65536, "conv1d_wgrad: grid too large");
+    // wgrad_mt_plan clamps kg to the instantiated range; a kg outside it would launch nothing and leave the
+    // reduce to sum an unwritten workspace
+    VO_CHECK_ARG(r->mt.kg >= 1 && r->mt.kg <= wgrad_mt_max_kg(r->mt.tm, r->sw),
+                 "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", r->mt.kg, r->mt.tm, r->sw);
+    return VO_OK;
   }
-  p.gpt = wgrad_gpt(M, N, groups);
-  const int64_t zk = (int64_t)K * (groups / p.gpt);
-  const int tiles = ((M * p.gpt + WG_T - 1) / WG_T) * ((N * p.gpt + WG_T - 1) / WG_T);
-  int64_t splits;
-  wgrad_plan(B, T_A, M, N, K, groups, &splits, &p.rows_per_split);
-  VO_CHECK_ARG(splits < (1 << 30) && tiles < 65536 && zk < 65536, "conv1d_wgrad: grid too large");
-  dim3 grid((unsigned)splits, (unsigned)tiles, (unsigned)zk);
+  r->route = WG_ROUTE_PER_TAP;
+  r->gpt = wgrad_gpt(M, N, groups);
+  r->zk = (int64_t)K * (groups / r->gpt);
+  r->tiles = ((M * r->gpt + WG_T - 1) / WG_T) * ((N * r->gpt + WG_T - 1) / WG_T);
+  wgrad_plan(B, T_A, M, N, K, groups, &r->splits, &r->rps);
+  VO_CHECK_ARG(r->splits < (1 << 30) && r->tiles < 65536 && r->zk < 65536, "conv1d_wgrad: grid too large");
   // one row split (short sequences: the encoder's 384 rows): the workgroups write dW / db in their final
   // layout -- the reduce pass would only permute (K, M, N) -> (M, N, K); wgrad_cfg 13 keeps it (A/B)
-  const bool direct = splits == 1 && vo_tune_get("wgrad_cfg") != 13;
-  if (direct) {
-    p.dwf = dw;
-    p.dbf = db;
+  r->direct = r->splits == 1 && vo_tune_get("wgrad_cfg") != 13;
+  return VO_OK;
+}
+
+// vo_conv1d_wgrad_last_launch: this thread's last vo_conv1d_wgrad_bias call (zeroed at its entry, filled from
+// the route it launched)
+static thread_local int32_t g_wgrad_last[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {};
+
+static void wgrad_record(const WgradRoute& r, int32_t* rec) {
+  const bool mt = r.route == WG_ROUTE_MULTI_TAP;
+  const int64_t splits = mt ? r.mt.splits : r.splits;
+  const int32_t v[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {
+      r.route, mt ? r.mt.tm : r.route == WG_ROUTE_K1 ? K1_T : WG_T, mt ? r.mt.kg : 0, mt ? r.sw : 0,
+      mt ? r.mt.ntg : 0, r.gpt, (int32_t)splits, mt ? WM_R * r.mt.cps : r.rps, r.direct ? 1 : 0,
+      r.direct ? 0 : splits >= 32 ? 16 : 1, r.dtype, r.bias};
+  memcpy(rec, v, sizeof(v));
+}
+
+static int wgrad_copy_record(const int32_t* src, int32_t* rec, int n) {
+  const int m = rec ? std::max(0, std::min(n, (int)VO_CONV1D_WGRAD_LAUNCH_FIELDS)) : 0;
+  if (m > 0) memcpy(rec, src, (size_t)m * sizeof(int32_t));
+  return m;
+}
+
+extern "C" int vo_conv1d_wgrad_last_launch(int32_t* rec, int n) { return wgrad_copy_record(g_wgrad_last, rec, n); }
+
+extern "C" int vo_conv1d_wgrad_plan(int B, int T_A, int T_B, int M, int N, int K, int S, int dil, int pad, int groups,
+                                    int pre_a, int pre_b, int dtype, int with_bias, int32_t* rec, int n) {
+  int32_t v[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {};
+  WgradRoute r;
+  // the leading dimensions do not enter the routing: the narrowest valid ones
+  const int rc = wgrad_route(B, T_A, T_B, M, N, K, S, dil, pad, groups, groups * M, groups * N, pre_a, pre_b, dtype,
+                             with_bias, &r);
+  if (rc == VO_OK) wgrad_record(r, v);
+  wgrad_copy_record(v, rec, n);
+  return rc;
+}
+
+extern "C" int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M,
+                                    int N, int K, int S, int dil, int pad, int groups, int pre_a, int pre_b,
+                                    float slope, int dtype, float* dw, float* db, float* workspace, void* stream) {
+  memset(g_wgrad_last, 0, sizeof(g_wgrad_last));
+  VO_CHECK_ARG(a && b && dw && workspace, "conv1d_wgrad: null pointer");
+  WgradRoute r;
+  const int rc = wgrad_route(B, T_A, T_B, M, N, K, S, dil, pad, groups, lda, ldb, pre_a, pre_b, dtype, db != nullptr,
+                             &r);
+  if (rc != VO_OK) return rc;
+  WgradArgs p;
+  p.a = a; p.lda = lda; p.T_A = T_A; p.bsrc = b; p.ldb = ldb; p.T_B = T_B;
+  p.M = M; p.N = N; p.K = K; p.S = S; p.dil = dil; p.pad = pad; p.Bn = B;
+  p.pre_a = pre_a; p.pre_b = pre_b; p.slope = slope;
+  p.part = workspace;
+  p.bias = db != nullptr;
+  p.n_w = (int64_t)groups * K * M * N;
+  p.n_tot = p.n_w + (db ? (int64_t)groups * M : 0);
+  p.abl = r.abl;
+  p.gpt = r.gpt;
+  p.rows_per_split = r.rps;
+  p.dwf = r.direct ? dw : nullptr;
+  p.dbf = r.direct ? db : nullptr;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (r.route == WG_ROUTE_K1) {
+    hipLaunchKernelGGL(wgrad_k1_kernel, dim3((unsigned)r.splits, (unsigned)r.tiles), dim3(256), 0, st, p);
+    if (!r.direct) wgrad_reduce_launch(workspace, (int)r.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+  } else if (r.route == WG_ROUTE_MULTI_TAP) {
+    const MtPlan& pl = r.mt;
+    bool launched;
+    if (r.sw == 1)
+      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 1>(p, pl, groups, st) : wgrad_mt_dispatch<64, 1>(p, pl, groups, st);
+    else if (r.sw == 2)
+      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 2>(p, pl, groups, st) : wgrad_mt_dispatch<64, 2>(p, pl, groups, st);
+    else
+      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 4>(p, pl, groups, st) : wgrad_mt_dispatch<64, 4>(p, pl, groups, st);
+    VO_CHECK_ARG(launched, "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", pl.kg, pl.tm, r.sw);
+    wgrad_reduce_launch(workspace, pl.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+  } else {
+    dim3 grid((unsigned)r.splits, (unsigned)r.tiles, (unsigned)r.zk);
+    if (dtype == VO_BF16)
+      hipLaunchKernelGGL(wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, p);
+    else if (dtype == VO_F32X3)
+      hipLaunchKernelGGL(wgrad_kernel<bx3_t>, grid, dim3(256), 0, st, p);
+    else
+      hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
+    if (!r.direct) wgrad_reduce_launch(workspace, (int)r.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
   }
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, p);
-  else if (dtype == VO_F32X3)
-    hipLaunchKernelGGL(wgrad_kernel<bx3_t>, grid, dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
-  if (!direct) wgrad_reduce_launch(workspace, (int)splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+  wgrad_record(r, g_wgrad_last);
   VO_RETURN_LAUNCH();
 }
 

@@ -1559,6 +1559,33 @@ def conv1d_wgrad(a, b, K, S=1, dil=1, pad=0, pre_a=None, pre_b=None, transposed=
     return (w, db) if with_bias else w
 
 
+WGRAD_LAUNCH_FIELDS = ("ROUTE", "TM", "KG", "SW", "ntg", "gpt", "splits", "rows_per_split", "direct", "reduce_W",
+                       "compute_dtype", "bias")
+WGRAD_PER_TAP, WGRAD_MULTI_TAP, WGRAD_K1 = 1, 2, 3  # ROUTE
+
+
+def conv1d_wgrad_plan(B, T_A, T_B, M, N, K, S=1, dil=1, pad=0, groups=1, pre_a=False, pre_b=False, dtype=VO_BF16,
+                      with_bias=False):
+    """The launch record ``vo_conv1d_wgrad_bias`` with these sizes (M, N per group) would leave, a dict over
+    WGRAD_LAUNCH_FIELDS, without launching anything (vo_conv1d_wgrad_plan: the routing the launch itself runs,
+    vo_tune knobs included).  Host only."""
+    rec = (ctypes.c_int32 * len(WGRAD_LAUNCH_FIELDS))()
+    _lib.check(_lib.lib().vo_conv1d_wgrad_plan(B, T_A, T_B, M, N, K, S, dil, pad, groups, int(bool(pre_a)),
+                                               int(bool(pre_b)), dtype, int(bool(with_bias)), rec,
+                                               len(WGRAD_LAUNCH_FIELDS)), "vo_conv1d_wgrad_plan")
+    return dict(zip(WGRAD_LAUNCH_FIELDS, (int(v) for v in rec)))
+
+
+def conv1d_wgrad_last_launch():
+    """What the calling thread's last weight-gradient call launched, as a dict over WGRAD_LAUNCH_FIELDS
+    (vo_conv1d_wgrad_last_launch in include/vonoma.h); all zeros when the call was rejected."""
+    rec = (ctypes.c_int32 * len(WGRAD_LAUNCH_FIELDS))()
+    n = _lib.lib().vo_conv1d_wgrad_last_launch(rec, len(WGRAD_LAUNCH_FIELDS))
+    if n != len(WGRAD_LAUNCH_FIELDS):
+        raise RuntimeError(f"vo_conv1d_wgrad_last_launch returned {n} fields, expected {len(WGRAD_LAUNCH_FIELDS)}")
+    return dict(zip(WGRAD_LAUNCH_FIELDS, (int(v) for v in rec)))
+
+
 def lrelu_mask(g, ref, slope, out=None, add=None, summand=None):
     """g * (ref > 0 ? 1 : slope) (leaky-ReLU / ReLU backward); g, ref (..., C) with row-contiguous
     last dims (ref may be a channel slice of a wider tensor).  out=g computes in place.  ``add``
