@@ -379,6 +379,21 @@ int vo_conv_post(const void* x, int x_dtype, const float* w, float bias, int B, 
 /* vo_conv_post on a ragged batch (per-utterance lengths, above): y[b, t] = 0.0f for t >= R_b. */
 int vo_conv_post_lens(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
                       int K, float slope, float* y, void* stream, const int32_t* lens, int lens_scale);
+/* vo_conv_post / vo_conv_post_lens with 16-bit PCM output: the same kernels (same dispatch, same fp32 order up to
+ * and including tanhf) instantiated with an int16_t output element, y (B, T) int16.  Each sample is stored as
+ *   q = (int16) clamp(trunc(v * scale), -32768, 32767)      v = tanhf(...), the product formed in fp32,
+ * truncated toward zero: what the reference's host-side (wavs * max_wav_value).astype("int16")
+ * (scripts/utils/model.py:73-98) gives for values in range.  A NaN v stores 0; the _lens form stores 0 at t >= R_b.
+ * DELIBERATE DEVIATION (saturation): tanhf returns exactly +-1.0f for large inputs and 1.0f * 32768 lies outside
+ * int16, where the host cast is undefined (in practice it wraps to -32768: an audible click).  These entries store
+ * 32767 there (and -32768 at the negative end, which is in range).
+ * scale must be finite and > 0; everything vo_conv_post refuses is refused here (VO_ERR_INVALID, nothing launched,
+ * text in vo_last_error()).  Rows of y are T samples apart: no alignment beyond 2 bytes is assumed. */
+int vo_conv_post_pcm16(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
+                       int K, float slope, float scale, int16_t* y, void* stream);
+int vo_conv_post_pcm16_lens(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
+                            int K, float slope, float scale, int16_t* y, void* stream, const int32_t* lens,
+                            int lens_scale);
 /* Fused ResBlock1 pair for C = 32 / 64 / 128 (bf16, channels-last (B, T, C)):
  *   y = (x + c2(lrelu(c1_dil(lrelu(x, slope)), slope))) * out_scale (+ acc)
  * c1 / c2: K taps, packed [K][C][C] bf16 (vo_pack_weight VO_PACK_CONV), biases fp32;

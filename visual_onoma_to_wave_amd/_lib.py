@@ -116,6 +116,10 @@ _SIGNATURES = {
                                   c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
     "vo_conv_post_lens": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float,
                                   c_void_p, c_void_p, c_void_p, c_int]),
+    "vo_conv_post_pcm16": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float, c_float,
+                                   c_void_p, c_void_p]),
+    "vo_conv_post_pcm16_lens": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_float,
+                                        c_float, c_void_p, c_void_p, c_void_p, c_int]),
     "vo_resblock3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                              c_int, c_int, c_float, c_float, c_void_p]),
     "vo_resblockk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -3,11 +3,14 @@
 // conv_post_kernel: lrelu(0.01) -> Conv1d(C -> 1, k7, pad 3) -> tanh over channels-last
 //   activations (scripts/hifigan/models.py:161-163).  HBM-bound: C*2 bytes in, 4 out per
 //   sample; a workgroup stages 256 + K - 1 rows in LDS and every lane reduces K*C products.
+//   Both conv_post kernels take the output element type TY: float stores tanh's result, int16_t
+//   stores it as PCM (PostStore<int16_t>: trunc(y * scale) toward zero, saturated, NaN -> 0).
 // transpose_bct_kernel: (B, C, T) fp32 mel -> channels-last (B, T, ldy), zero channel pad.
 // pack_weight_kernel: weight-norm fold (models.py:105-109,167-174), BatchNorm fold and the
 //   [K][Co][Ci] / polyphase ConvTranspose1d layouts the conv1d kernel reads.
 
 #include <algorithm>
+#include <cmath>
 
 #include "vo_common.h"
 
@@ -15,16 +18,38 @@ namespace vo {
 
 constexpr int CP_ROWS = 256;
 
+// How a conv_post kernel stores a sample, by the output element type TY.  float: the value itself (the struct is
+// empty, so the fp32 instantiations are the kernels they were).  int16_t: q = (int16) clamp(trunc(v * scale), -32768,
+// 32767), the product in fp32 -- the host's (wav * max_wav_value).astype("int16") for values in range.  Deliberate
+// deviation: tanhf gives exactly +-1.0f for large inputs and 1.0f * 32768 is outside int16, where the host cast is
+// undefined (it wraps to -32768, a click); this stores 32767.  NaN stores 0.  Element stores only: a row of y is
+// 2-byte aligned when T is odd.
+template <typename TY>
+struct PostStore;
+template <>
+struct PostStore<float> {
+  __device__ float operator()(float v) const { return v; }
+};
+template <>
+struct PostStore<int16_t> {
+  float scale;
+  __device__ int16_t operator()(float v) const {
+    const float p = v * scale;
+    // fminf / fmaxf return the non-NaN operand, so a NaN is caught first; both bounds are exact in fp32
+    return (p != p) ? (int16_t)0 : (int16_t)(int)truncf(fminf(fmaxf(p, -32768.f), 32767.f));
+  }
+};
+
 // CC > 0: compile-time channel count (HiFi-GAN V1: 32) -- the staging loads are then issued
 // as one batch (a runtime-trip loop serialises one HBM round trip per iteration); CC = 0:
 // any C (multiple of 8).
 // RAG (both kernels): ragged batch -- utterance b has Tv = clamp(lens[b] * lens_scale, 0, T_) samples: Tv stands where
 // T does (T_ stays the row stride), and the samples [Tv, T_) are stored as 0.0f.
-template <typename TX, int CC, bool RAG = false>
+template <typename TX, int CC, bool RAG = false, typename TY = float>
 __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x, const float* __restrict__ w,
                                                         float bias, int T_, int C_, int K, float slope,
-                                                        float* __restrict__ y, const int32_t* __restrict__ lens,
-                                                        int lens_scale) {
+                                                        TY* __restrict__ y, const int32_t* __restrict__ lens,
+                                                        int lens_scale, PostStore<TY> store = {}) {
   const int C = CC > 0 ? CC : C_;
   extern __shared__ __attribute__((aligned(16))) float cp_lds[];
   const int b = blockIdx.y;
@@ -32,7 +57,7 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
   const int T = RAG ? rag_rows(lens, lens_scale, b, T_) : T_;
   if constexpr (RAG) {
     if (t0 >= T) {  // the whole tile is past the utterance's end
-      if (t0 + threadIdx.x < T_) y[(int64_t)b * T_ + t0 + threadIdx.x] = 0.f;
+      if (t0 + threadIdx.x < T_) y[(int64_t)b * T_ + t0 + threadIdx.x] = TY(0);
       return;
     }
   }
@@ -81,7 +106,7 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
   __syncthreads();
   const int t = t0 + threadIdx.x;
   if constexpr (RAG) {
-    if (t >= T && t < T_) y[(int64_t)b * T_ + t] = 0.f;
+    if (t >= T && t < T_) y[(int64_t)b * T_ + t] = TY(0);
   }
   if (t >= T) return;
   float acc0 = bias, acc1 = 0.f;
@@ -95,7 +120,7 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
       acc1 += wk[c + 4] * d.x + wk[c + 5] * d.y + wk[c + 6] * d.z + wk[c + 7] * d.w;
     }
   }
-  y[(int64_t)b * T_ + t] = tanhf(acc0 + acc1);
+  y[(int64_t)b * T_ + t] = store(tanhf(acc0 + acc1));
 }
 
 // conv_post_rows_kernel (bf16, compile-time C and K; HiFi-GAN V1: 32, 7): each thread reads
@@ -104,10 +129,11 @@ __global__ void __launch_bounds__(256) conv_post_kernel(const TX* __restrict__ x
 // sum_k z[k][r + k]).  A row is read once (LDS traffic 2K floats per sample) instead of K
 // times from an LDS tile by every output (the stencil kernel above: K*C floats per sample).
 // 256 rows per workgroup give 256 - (K - 1) outputs.
-template <int C, int K, bool RAG = false>
+template <int C, int K, bool RAG = false, typename TY = float>
 __global__ void __launch_bounds__(256) conv_post_rows_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
-                                                             float bias, int T_, float slope, float* __restrict__ y,
-                                                             const int32_t* __restrict__ lens, int lens_scale) {
+                                                             float bias, int T_, float slope, TY* __restrict__ y,
+                                                             const int32_t* __restrict__ lens, int lens_scale,
+                                                             PostStore<TY> store = {}) {
   constexpr int OUT = 256 - (K - 1);
   constexpr int PAD = (K - 1) / 2;
   __shared__ float z[K][256];
@@ -117,7 +143,7 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const bf16_t* __res
   const int T = RAG ? rag_rows(lens, lens_scale, b, T_) : T_;
   if constexpr (RAG) {
     if (t0 >= T) {  // the whole tile is past the utterance's end
-      if (r < OUT && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = 0.f;
+      if (r < OUT && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = TY(0);
       return;
     }
   }
@@ -141,13 +167,13 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const bf16_t* __res
   }
   __syncthreads();
   if constexpr (RAG) {
-    if (r < OUT && t0 + r >= T && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = 0.f;
+    if (r < OUT && t0 + r >= T && t0 + r < T_) y[(int64_t)b * T_ + t0 + r] = TY(0);
   }
   if (r >= OUT || t0 + r >= T) return;
   float acc = bias;
 #pragma unroll
   for (int k = 0; k < K; ++k) acc += z[k][r + k];
-  y[(int64_t)b * T_ + t0 + r] = tanhf(acc);
+  y[(int64_t)b * T_ + t0 + r] = store(tanhf(acc));
 }
 
 template <typename TY>
@@ -248,10 +274,11 @@ __global__ void __launch_bounds__(256) pack_weight_lin_kernel(const float* __res
 
 using namespace vo;
 
-// vo_conv_post (RAG = false, lens unused) and vo_conv_post_lens
-template <bool RAG>
+// vo_conv_post / vo_conv_post_pcm16 (RAG = false, lens unused) and vo_conv_post_lens / vo_conv_post_pcm16_lens
+template <bool RAG, typename TY>
 static int conv_post_entry(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
-                           float slope, float* y, void* stream, const int32_t* lens, int lens_scale) {
+                           float slope, TY* y, void* stream, const int32_t* lens, int lens_scale,
+                           PostStore<TY> store = {}) {
   VO_CHECK_ARG(x && w && y, "conv_post: null pointer");
   VO_CHECK_ARG(C % 8 == 0 && K % 2 == 1 && C <= 512 && K <= 31, "conv_post: C=%d K=%d unsupported", C, K);
   VO_CHECK_ARG(slope >= 0.f && slope <= 1.f, "conv_post: slope %g outside [0, 1]", slope);
@@ -260,21 +287,21 @@ static int conv_post_entry(const void* x, int x_dtype, const float* w, float bia
   if (x_dtype == VO_BF16 && C == 32 && K == 7 && vo_tune_get("post_cfg") != 1) {  // post_cfg 1: stencil kernel
     constexpr int OUT = 256 - 6;
     dim3 g2((unsigned)((T + OUT - 1) / OUT), (unsigned)B);
-    hipLaunchKernelGGL((conv_post_rows_kernel<32, 7, RAG>), g2, dim3(256), 0, st, (const bf16_t*)x, w, bias, T, slope, y,
-                       lens, lens_scale);
+    hipLaunchKernelGGL((conv_post_rows_kernel<32, 7, RAG, TY>), g2, dim3(256), 0, st, (const bf16_t*)x, w, bias, T,
+                       slope, y, lens, lens_scale, store);
     VO_RETURN_LAUNCH();
   }
   dim3 grid((unsigned)((T + CP_ROWS - 1) / CP_ROWS), (unsigned)B);
   const size_t lds = (size_t)(CP_ROWS + K - 1) * (C + 4) * sizeof(float);
   if (x_dtype == VO_BF16 && C == 32)
-    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 32, RAG>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K,
-                       slope, y, lens, lens_scale);
+    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 32, RAG, TY>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T,
+                       C, K, slope, y, lens, lens_scale, store);
   else if (x_dtype == VO_BF16)
-    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 0, RAG>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T, C, K,
-                       slope, y, lens, lens_scale);
+    hipLaunchKernelGGL((conv_post_kernel<bf16_t, 0, RAG, TY>), grid, dim3(256), lds, st, (const bf16_t*)x, w, bias, T,
+                       C, K, slope, y, lens, lens_scale, store);
   else
-    hipLaunchKernelGGL((conv_post_kernel<float, 0, RAG>), grid, dim3(256), lds, st, (const float*)x, w, bias, T, C, K,
-                       slope, y, lens, lens_scale);
+    hipLaunchKernelGGL((conv_post_kernel<float, 0, RAG, TY>), grid, dim3(256), lds, st, (const float*)x, w, bias, T, C,
+                       K, slope, y, lens, lens_scale, store);
   VO_RETURN_LAUNCH();
 }
 
@@ -287,6 +314,22 @@ extern "C" int vo_conv_post_lens(const void* x, int x_dtype, const float* w, flo
                                  float slope, float* y, void* stream, const int32_t* lens, int lens_scale) {
   VO_CHECK_ARG(lens && lens_scale >= 1, "conv_post_lens: lens is null or lens_scale %d < 1", lens_scale);
   return conv_post_entry<true>(x, x_dtype, w, bias, B, T, C, K, slope, y, stream, lens, lens_scale);
+}
+
+extern "C" int vo_conv_post_pcm16(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C, int K,
+                                  float slope, float scale, int16_t* y, void* stream) {
+  VO_CHECK_ARG(std::isfinite(scale) && scale > 0.f, "conv_post_pcm16: scale %g is not finite and positive", scale);
+  return conv_post_entry<false>(x, x_dtype, w, bias, B, T, C, K, slope, y, stream, nullptr, 0,
+                                PostStore<int16_t>{scale});
+}
+
+extern "C" int vo_conv_post_pcm16_lens(const void* x, int x_dtype, const float* w, float bias, int B, int T, int C,
+                                       int K, float slope, float scale, int16_t* y, void* stream, const int32_t* lens,
+                                       int lens_scale) {
+  VO_CHECK_ARG(std::isfinite(scale) && scale > 0.f, "conv_post_pcm16: scale %g is not finite and positive", scale);
+  VO_CHECK_ARG(lens && lens_scale >= 1, "conv_post_pcm16_lens: lens is null or lens_scale %d < 1", lens_scale);
+  return conv_post_entry<true>(x, x_dtype, w, bias, B, T, C, K, slope, y, stream, lens, lens_scale,
+                               PostStore<int16_t>{scale});
 }
 
 extern "C" int vo_transpose_bct(const float* x, int B, int C, int T, void* y, int y_dtype, int ldy, void* stream) {

@@ -41,9 +41,18 @@ class GlyphBatch:
     def margin(self):
         return (self.stride // 2) * self.cell  # pad_2D_gray_image's each_padlen
 
-    def to(self, device):
+    def to(self, device, n_chars=None):
+        """``n_chars``: lay the batch out at the width of an ``n_chars``-character bucket, ``n_chars * cell +
+        2 * margin`` (the static image tensor of ``pipeline.GraphedSynthesis``); the columns past the batch's own
+        width are white (1.0)."""
         from . import ops
-        return ops.glyph_batch(self.strips, self.char_widths, self.cell, self.margin, device)
+        W_out = None
+        if n_chars is not None:
+            longest = max((len(w) for w in self.char_widths), default=0)
+            if int(n_chars) < longest:
+                raise ValueError(f"GlyphBatch.to: n_chars={n_chars} is below the batch's longest text ({longest})")
+            W_out = int(n_chars) * self.cell + 2 * self.margin
+        return ops.glyph_batch(self.strips, self.char_widths, self.cell, self.margin, device, W_out=W_out)
 
 
 def _read_gray(path):

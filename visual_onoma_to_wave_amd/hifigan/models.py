@@ -220,8 +220,9 @@ class Generator(HipModule):
             raise ValueError(f"lengths must be {B} frame counts in [0, {T}], got {host}")
         return ops.mask_from_lengths(torch.tensor(host, dtype=torch.int32, device=device), T, want_mask=False)[1]
 
-    def run(self, mel_cl, lengths=None):
-        """mel_cl (B, T, 80) channels-last (fp32 or compute dtype) -> wav (B, 256*T) fp32.
+    def run(self, mel_cl, lengths=None, pcm_scale=None):
+        """mel_cl (B, T, 80) channels-last (fp32 or compute dtype) -> wav (B, 256*T) fp32; with ``pcm_scale`` (e.g.
+        32768.0) int16 PCM instead, written by conv_post itself (``ops.conv_post``: truncated toward zero, saturated).
         ``lengths`` (optional; int32 / int64 device tensor or host sequence of B frame counts in [0, T]): ragged
         batch -- row b is what ``run(mel_cl[b:b+1, :lengths[b]])`` gives, followed by exact zeros: every layer treats
         utterance b as a tensor of lengths[b] * (rows per frame) rows, so the padded frames are neither computed nor
@@ -243,7 +244,7 @@ class Generator(HipModule):
             scale *= u
             x = self.mrf(i, x, lens=lens, lens_scale=scale)
         wk, bp = p["post"]
-        return ops.conv_post(x, wk, bp, slope=0.01, **rag())
+        return ops.conv_post(x, wk, bp, slope=0.01, pcm_scale=pcm_scale, **rag())
 
     def mrf(self, i, x, lens=None, lens_scale=None):
         """Multi-receptive-field fusion of upsampling stage i (hifigan/models.py:155-160):
@@ -371,11 +372,12 @@ class Generator(HipModule):
         plan.append((self.conv_post, G.ConvSpec(K=7, pad=3, pre_slope=0.01, post="tanh", co_pad=4), (B, T, C), False))
         return plan
 
-    def forward(self, x, lengths=None):
-        """x (B, 80, T) mel -> (B, 1, 256 * T) waveform (reference: models.py:149-165); ``lengths``: as ``run``."""
+    def forward(self, x, lengths=None, pcm_scale=None):
+        """x (B, 80, T) mel -> (B, 1, 256 * T) waveform (reference: models.py:149-165); ``lengths`` and
+        ``pcm_scale``: as ``run``."""
         self._check_inference()
         mel_cl = ops.transpose_bct(x, torch.float32)
-        return self.run(mel_cl, lengths).unsqueeze(1)
+        return self.run(mel_cl, lengths, pcm_scale).unsqueeze(1)
 
     def remove_weight_norm(self):
         print("Removing weight norm...")

@@ -671,13 +671,28 @@ def mask_from_lengths(lens, max_len, want_mask=True):
 
 # ----------------------------------------------------------------------------- vocoder glue
 
-def conv_post(x, w_kc, bias, slope=0.01, lens=None, lens_scale=1):
+def conv_post(x, w_kc, bias, slope=0.01, lens=None, lens_scale=1, pcm_scale=None):
     """x (B, T, C) -> tanh(conv(lrelu(x))) (B, T) fp32; w_kc (K, C) fp32.
     ``lens`` / ``lens_scale`` (ragged batch, as ``conv1d``): sample t of utterance b is computed from its first
-    R_b = clamp(lens[b] * lens_scale, 0, T) rows alone for t < R_b and is exactly 0.0 from R_b on."""
+    R_b = clamp(lens[b] * lens_scale, 0, T) rows alone for t < R_b and is exactly 0.0 from R_b on.
+    ``pcm_scale`` (e.g. 32768.0): the result as int16 (B, T), clamp(trunc(y * pcm_scale), -32768, 32767) stored by
+    the same kernels (vo_conv_post_pcm16: truncation toward zero as numpy's astype("int16"), but saturating where
+    that cast wraps; NaN -> 0); a scale that is not finite and positive is refused by the library."""
     _contig(x, "x")
     B, T, C = x.shape
     K = w_kc.shape[0]
+    if pcm_scale is not None:
+        y = torch.empty((B, T), dtype=torch.int16, device=x.device)
+        if lens is not None:
+            sc = _check_lens(lens, lens_scale, B, x, "conv_post")
+            _lib.check(_lib.lib().vo_conv_post_pcm16_lens(_ptr(x), vo_dtype(x), _ptr(w_kc), float(bias), B, T, C, K,
+                                                          float(slope), float(pcm_scale), _ptr(y), _stream(x),
+                                                          _ptr(lens), sc), "vo_conv_post_pcm16_lens")
+            return y
+        _lib.check(_lib.lib().vo_conv_post_pcm16(_ptr(x), vo_dtype(x), _ptr(w_kc), float(bias), B, T, C, K,
+                                                 float(slope), float(pcm_scale), _ptr(y), _stream(x)),
+                   "vo_conv_post_pcm16")
+        return y
     y = torch.empty((B, T), dtype=torch.float32, device=x.device)
     if lens is not None:
         sc = _check_lens(lens, lens_scale, B, x, "conv_post")

@@ -296,21 +296,24 @@ def _capture_ctx(bucketers):
     return stack
 
 
-def _check_graph_runtime():
+def _check_graph_runtime(what="HIP-graph training"):
+    """Refuse to capture or replay a HIP graph (``what``: the caller, for the message -- the graphed training steps
+    and ``pipeline.GraphedSynthesis``) unless DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was in effect when the HIP runtime
+    initialised."""
     import visual_onoma_to_wave_amd as _pkg
     if _pkg.PACKET_CAPTURE_SET_LATE:
         raise RuntimeError(
-            "HIP-graph training: visual_onoma_to_wave_amd was imported after torch had initialised the HIP "
+            f"{what}: visual_onoma_to_wave_amd was imported after torch had initialised the HIP "
             "runtime, so its DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 setting came too late to take effect. Import the "
             "package (or export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0) before the first CUDA call, e.g. before "
-            "torch.cuda.set_device(local_rank); with the CLR packet-capture launch path replays of the training "
-            "step compute wrong values (DESIGN.md section 7)")
+            "torch.cuda.set_device(local_rank); with the CLR packet-capture launch path replays of a captured "
+            "graph compute wrong values (DESIGN.md section 7)")
     if not packet_capture_disabled():
         raise RuntimeError(
-            "HIP-graph training needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in effect when the HIP runtime "
+            f"{what} needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in effect when the HIP runtime "
             "initialises (visual_onoma_to_wave_amd sets it on import: import the package, or export the "
-            "variable, before the first CUDA call); with the CLR packet-capture launch path replays of the "
-            "training step compute wrong values (DESIGN.md section 7)")
+            "variable, before the first CUDA call); with the CLR packet-capture launch path replays of a "
+            "captured graph compute wrong values (DESIGN.md section 7)")
 
 
 class GraphedTrainStep:

@@ -3,7 +3,8 @@
 
 get_model(restore_step, configs, device, train=False)
 get_vocoder(config, device)
-vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True)
+vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True, ragged=False,
+              device_pcm=False)
 """
 
 import json
@@ -69,12 +70,23 @@ def get_vocoder(config, device, checkpoint=None):
     return vocoder.to(device)
 
 
-def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True, ragged=False):
+def _audio_config(preprocess_config):
+    # the reference reads preprocess_config["preprocessing"]["audio"]["max_wav_value"]
+    # (a key the ICASSP config does not have); accept both layouts
+    return preprocess_config.get("preprocessing", preprocess_config)["audio"]
+
+
+def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, Normalize=True, ragged=False,
+                  device_pcm=False):
     """``ragged`` (with ``lengths`` in samples, as the reference passes them): the vocoder runs the batch as a
     ragged one -- utterance i over its first ceil(lengths[i] / hop) mel frames only (``Generator.run``'s
     ``lengths``), so its waveform is what it gives alone, not a function of the padding it was batched with.
-    The default computes every padded frame, as the reference does."""
+    The default computes every padded frame, as the reference does.
+    ``device_pcm`` (with ``Normalize``): the generator's last kernel stores int16 itself (``Generator.run``'s
+    ``pcm_scale`` = max_wav_value) and the copy to the host moves int16 -- the same samples as the host cast gives
+    wherever |wav * max_wav_value| < 32768; where the host cast wraps (a tanh of exactly 1.0) it stores 32767."""
     name = model_config["vocoder"]["model"]
+    pcm = float(_audio_config(preprocess_config)["max_wav_value"]) if (device_pcm and Normalize) else None
     with torch.no_grad():
         if name != "HiFi-GAN":
             raise NotImplementedError(name)
@@ -85,15 +97,12 @@ def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, 
             for u in vocoder.h.upsample_rates:
                 hop *= u
             frames = [-(-int(n) // hop) for n in lengths]
-            wavs = vocoder(mels, lengths=frames).squeeze(1)
+            wavs = vocoder(mels, lengths=frames, pcm_scale=pcm).squeeze(1)
         else:
-            wavs = vocoder(mels).squeeze(1)
+            wavs = vocoder(mels, pcm_scale=pcm).squeeze(1)
     wavs = wavs.cpu().numpy()
-    if Normalize:
-        # the reference reads preprocess_config["preprocessing"]["audio"]["max_wav_value"]
-        # (a key the ICASSP config does not have); accept both layouts
-        audio = preprocess_config.get("preprocessing", preprocess_config)["audio"]
-        wavs = (wavs * audio["max_wav_value"]).astype("int16")
+    if Normalize and pcm is None:
+        wavs = (wavs * _audio_config(preprocess_config)["max_wav_value"]).astype("int16")
     wavs = [w for w in wavs]
     if lengths is not None:
         for i in range(len(mels)):
