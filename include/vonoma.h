@@ -150,6 +150,14 @@ int vo_conv1d_last_launch(int32_t* rec, int n);
  * before its launch: VO_OK, or VO_ERR_INVALID with the same vo_last_error text.  The calling thread's
  * last-launch record is left as it was. */
 int vo_conv1d_plan(const vo_conv1d_desc* d, int32_t* rec, int n);
+/* 1 when vo_conv1d runs d on the plane conv (csrc/conv_plane.hip: MRF stage 0 in the wave-owned output-plane form)
+ * instead of the tiled kernel, else 0; host only, like vo_conv1d_plan.  It takes the dense variant-1 call with bf16
+ * in, compute and out, Ci = Co = ldx = ldy = 256, K = 3 / 7 / 11, (K - 1) dil <= 64 = 2 pad, T_out = T_in, a bias, the
+ * leaky-ReLU prologue or none (the ResBlock's c1 and c2), no or a leaky-ReLU post-activation, no stride / groups / transposed / ymask / workspace / lens,
+ * every byte offset of an utterance within 31 bits, and "conv_cfg" 0 (5, 6, 9 = the tiled kernels: forced role split,
+ * none, the shipped rule).  The launch record of such a call is the 256 x 256 stage-0 tile's: the plane tile's own
+ * geometry.  Results equal the tiled kernel's bit for bit. */
+int vo_conv1d_plane_takes(const vo_conv1d_desc* d);
 
 /* Weight preparation (load time).  Replaces the weight-norm fold (remove_weight_norm,
  * scripts/hifigan/models.py:105-109,167-174: w = g * v / ||v||, norm over all dims but 0)

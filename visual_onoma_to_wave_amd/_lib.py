@@ -133,6 +133,7 @@ _SIGNATURES = {
     "vo_conv1d_workspace_size": (ctypes.c_int64, [ctypes.POINTER(Conv1dDesc)]),
     "vo_conv1d_last_launch": (c_int, [ctypes.POINTER(ctypes.c_int32), c_int]),
     "vo_conv1d_plan": (c_int, [ctypes.POINTER(Conv1dDesc), ctypes.POINTER(ctypes.c_int32), c_int]),
+    "vo_conv1d_plane_takes": (c_int, [ctypes.POINTER(Conv1dDesc)]),
     "vo_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                c_void_p, c_int, c_void_p]),
     "vo_layernorm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,

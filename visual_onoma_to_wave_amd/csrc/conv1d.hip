@@ -190,16 +190,13 @@ __device__ __forceinline__ void conv_epilogue_vec(const ConvArgs& a, f32x4 (&acc
             x2[2 * u + 1] = __uint_as_float(w[u] & 0xffff0000u);
           }
         }
+        float av[8], bv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const int i = 2 * h + e / 4, r = e & 3;
-          float v = acc[i][j][r] + bias[8 * h + e];
-          v = tanh_act ? tanhf(v) : lrelu_max(v, ps);  // ps in [0, 1]
-          if (r1) v += x1[e];
-          v *= a.out_scale;
-          if (r2) v += x2[e];
-          q[e] = v;
+          av[e] = acc[2 * h + e / 4][j][e & 3];
+          bv[e] = bias[8 * h + e];
         }
+        conv_epilogue8(av, bv, tanh_act, ps, r1, x1, a.out_scale, r2, x2, q);
         if (om) {  // the leaky-ReLU backward of the layer whose output ymask is, on the stored value
           const uint32_t w[4] = {rvm[jj][h].x, rvm[jj][h].y, rvm[jj][h].z, rvm[jj][h].w};
 #pragma unroll
@@ -1044,6 +1041,7 @@ constexpr int kTypeBytes[][3] = {{4, 4, 4}, {4, 4, 4}, {2, 2, 2}, {2, 2, 4}, {4,
 // What one vo_conv1d call launches: all the launch record holds, and what launch_tile needs beyond the tile.
 struct ConvPlan {
   bool ups;          // the streaming upsampler (upsample.hip) takes the descriptor: no tile, an all-zero record
+  bool plane;        // the plane conv (conv_plane.hip) takes the descriptor: the 256 x 256 stage-0 record, its own launch
   int types, role;   // ConvTypes; d->variant where it selects an MRF stage's own tiles (bf16 in, compute and out)
   const Tile* tile;  // null = refused by the selector
   int S;             // conv stride
@@ -1175,6 +1173,7 @@ static const Tile* select_role(const vo_conv1d_desc* d, int role) {
   // 256 x 256 tile at k = 3 / 7 / 11
   // (EJ, the epilogue's position tiles whose residual / accumulator rows are requested together: 4 measured within
   // 1 % of 2, 8 spills and runs 10-20 % slower -- kept at 2)
+  // conv_cfg 9 = this rule as shipped, for the calls the plane conv (conv_plane.hip) takes at conv_cfg 0: A/B in one process
   return cc == 5 || (cc != 6 && d->K >= 5) ? &T256x256_mrf0_rs : &T256x256_mrf0;
 }
 
@@ -1343,7 +1342,10 @@ static int launch_disc(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t s
   }
 }
 
+int vo_conv_plane_launch(const vo_conv1d_desc* d, hipStream_t st);  // conv_plane.hip
+
 static int launch_plan(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  if (p.plane) return vo_conv_plane_launch(d, st);
   const bool rag = d->lens != nullptr;
   int rc = kNoTile;
   if (d->stride > 1 || d->groups > 1)  // discriminator layers: three type triples, no ragged form
@@ -1454,8 +1456,12 @@ static int conv1d_check(const vo_conv1d_desc* d, ConvPlan* p) {
 
 // check, select, plan: on VO_OK *p is what vo_conv1d launches
 static int conv1d_plan(const vo_conv1d_desc* d, ConvPlan* p) {
+  p->plane = false;
   const int rc = conv1d_check(d, p);
   if (rc != VO_OK || p->ups) return rc;
+  // MRF stage 0, dense: wave-owned output planes (conv_plane.hip).  The tile selected below is its true geometry
+  // (256 x 256, NI 4, WCO 4) and stays the launch record
+  p->plane = p->role == 1 && vo_conv1d_plane_takes(d) != 0;
   p->S = d->stride > 1 ? d->stride : 1;
   p->tile = d->stride > 1 || d->groups > 1 ? select_disc(d) : p->role ? select_role(d, p->role)
                                            : select_types(d, kTypeBytes[p->types][0], kTypeBytes[p->types][1]);

@@ -37,6 +37,24 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
 // are identical (a NaN input gives a NaN either way).
 __device__ __forceinline__ float lrelu_max(float v, float s) { return __builtin_elementwise_maximum(v, v * s); }
 
+// The conv epilogue of 8 consecutive channels, q = (post(acc + bias) + x1) * scale + x2 in this order of roundings
+// (post = tanh, or leaky ReLU with slope ps in [0, 1]: 1 = none, 0 = ReLU; x1 / x2 only where r1 / r2).  One
+// definition for conv_epilogue_vec (conv1d.hip) and the plane conv (conv_plane.hip): both compile the same
+// expression, so the two kernels round alike.
+__device__ __forceinline__ void conv_epilogue8(const float (&acc)[8], const float (&bias)[8], bool tanh_act, float ps,
+                                               bool r1, const float (&x1)[8], float scale, bool r2,
+                                               const float (&x2)[8], float (&q)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float v = acc[e] + bias[e];
+    v = tanh_act ? tanhf(v) : lrelu_max(v, ps);  // ps in [0, 1]
+    if (r1) v += x1[e];
+    v *= scale;
+    if (r2) v += x2[e];
+    q[e] = v;
+  }
+}
+
 // Index of the table entry owning item x: the last i < n with start[i] <= x (start ascending,
 // start[0] = 0) -- a binary search over a table in the kernel arguments, so a workgroup near the
 // end of a 32-entry table pays 5 dependent scalar loads instead of 32.

@@ -213,6 +213,15 @@ def conv1d_plan(x, w_packed, bias, *, tag=None, **kw):
     return dict(zip(LAUNCH_FIELDS, (int(v) for v in rec)))
 
 
+def conv1d_plane_takes(x, w_packed, bias, *, tag=None, **kw):
+    """Whether ``conv1d`` with the same arguments runs on the plane conv (vo_conv1d_plane_takes in
+    include/vonoma.h: MRF stage 0 in the wave-owned output-plane form); host only, launches nothing."""
+    d, x, _, ws_bytes = _conv1d_desc(x, w_packed, bias, **kw)
+    if ws_bytes > 0:  # never dereferenced, as in conv1d_plan
+        d.workspace, d.workspace_bytes = d.y, ws_bytes
+    return bool(_lib.lib().vo_conv1d_plane_takes(ctypes.byref(d)))
+
+
 def conv1d_last_launch():
     """The tile the calling thread's last ``conv1d`` launched, as a dict over LAUNCH_FIELDS
     (vo_conv1d_last_launch in include/vonoma.h); all zeros when the call was rejected or went to the
