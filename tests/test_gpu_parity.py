@@ -10,7 +10,6 @@ Tolerances (relative L2 unless stated):
 """
 
 import numpy as np
-import os
 
 import pytest
 import torch
@@ -485,7 +484,7 @@ def _resblock3_case(C, T, with_acc, cfg, dils):
                                  # register-resident frames at C = 32 (today 104 output rows per tile): BT, BT + 1
                                  pytest.param(32, _r3(32), id="32-104"), pytest.param(32, _r3(32, 1, 1), id="32-105"),
                                  (32, 24),
-                                 # the 72-row edges of the C = 64 register frames, a kernel of the A/B library only:
+                                 # the 72-row edges of the C = 64 register frames, a kernel since deleted:
                                  # interior lengths of the shipped plane kernel
                                  (64, 72), (64, 73), (64, 16), (64, 72 * 5 - 1),
                                  # wave-owned planes (resblock_pb3.hip; today 200 (C = 128) / 488 (C = 64) output rows
@@ -500,8 +499,8 @@ def _resblock3_case(C, T, with_acc, cfg, dils):
                                  pytest.param(32, _r3(32, 1, 1, cfg=80), id="32-233")])
 @pytest.mark.parametrize("with_acc", [True, False])
 # cfg 0: the shipped dispatch (C = 32: register-resident frames; C = 64 / 128: wave-owned planes).  80 (any
-# rb3_cfg != 0): the LDS-frame kernels -- at C = 32 in either library; at C = 64 / 128 only in the A/B library
-# (make abl, VO_LIB_PATH), the shipped library has the plane kernel alone there and runs it whatever the knob says
+# rb3_cfg != 0): the LDS-frame kernel at C = 32; at C = 64 / 128 the library has the plane kernel alone and runs it
+# whatever the knob says
 @pytest.mark.parametrize("cfg", [0, 80])
 def test_fused_resblock3_vs_torch_fp32(C, T, with_acc, cfg):
     """vo_resblock3 (a whole k = 3 ResBlock, dilations 1/3/5, in one launch) against the torch fp32
@@ -522,10 +521,8 @@ def test_fused_resblock3_c32_lds_frames_by_default(T, with_acc):
 
 
 # cfg 0: the shipped dispatch (wave-owned planes for C = 64 / 128 k = 7 / 11); 93 and, at C = 64, 111: the LDS-tile
-# kernels there too -- in the shipped library the generic ones that also serve k = 5 / 9 / 13 / 15, in the A/B
-# library (make abl, VO_LIB_PATH) the version-2 kernel at C = 64;
-# VO_PARITY_PAIR_CFGS=94,100 adds A/B candidates of the ablation build
-_PAIR_CFGS = [0, 93, 111] + [int(c) for c in os.environ.get("VO_PARITY_PAIR_CFGS", "").split(",") if c]
+# kernels there too, the generic ones that also serve k = 5 / 9 / 13 / 15
+_PAIR_CFGS = [0, 93, 111]
 
 
 def _pair_case(C, T, k, d, with_acc, cfg):
@@ -646,41 +643,6 @@ def test_pair_plane_frag_bit_identical(C, T, k, d, with_acc, scale):
         if with_acc:
             ref = ref + acc.float()
         assert rel_l2(outs[1].float().cpu(), ref.cpu()) < 1e-2
-
-
-@pytest.mark.parametrize("cand,rs", [(71, 0), (72, 0), (72, 2)])
-@pytest.mark.parametrize("T,k,d", [(32768, 11, 5), (32768, 7, 3), (777, 11, 1), (1, 7, 5)])
-def test_pair_c128_candidates_vs_shipped(T, k, d, cand, rs):
-    """The round-4 C = 128 pair candidates (pair_cfg 71: producer roles; 72: register-streamed weights,
-    rs_cfg 2: its two-waves-per-SIMD variant).  Measured slower and built only into the A/B library
-    (``make abl``; run with VO_LIB_PATH=visual_onoma_to_wave_amd/lib/libvonoma_abl.so).  Against the
-    shipped kernel on the same bf16 operands: they differ only in fp32 summation order before the one
-    bf16 rounding of y."""
-    from visual_onoma_to_wave_amd import _lib, ops
-    if _lib.lib().vo_tune(b"pc_cfg", 8) != 0:
-        pytest.skip("A/B candidates: ablation build only (make abl)")
-    _lib.lib().vo_tune(b"pc_cfg", 0)
-    C, B = 128, 4
-    g = torch.Generator(device="cuda").manual_seed(T + 10 * k + d)
-    x = torch.randn(B, T, C, device="cuda", generator=g).to(torch.bfloat16)
-    acc = torch.randn(B, T, C, device="cuda", generator=g).to(torch.bfloat16)
-    p1 = ops.pack_conv_weight(torch.randn(C, C, k, device="cuda", generator=g) / (C * k) ** 0.5, torch.bfloat16)
-    p2 = ops.pack_conv_weight(torch.randn(C, C, k, device="cuda", generator=g) / (C * k) ** 0.5, torch.bfloat16)
-    b1 = torch.randn(C, device="cuda", generator=g) * 0.1
-    b2 = torch.randn(C, device="cuda", generator=g) * 0.1
-    outs = []
-    for cfg in (0, cand):
-        o = acc.clone()
-        _lib.lib().vo_tune(b"pair_cfg", cfg)
-        _lib.lib().vo_tune(b"rs_cfg", rs if cfg else 0)
-        try:
-            ops.resblock_pair(x, p1, b1, p2, b2, k, d, 0.1, out=o, out_scale=1.0 / 3, acc=o)
-            torch.cuda.synchronize()
-        finally:
-            _lib.lib().vo_tune(b"pair_cfg", 0)
-            _lib.lib().vo_tune(b"rs_cfg", 0)
-        outs.append(o.float())
-    assert rel_l2(outs[0].cpu(), outs[1].cpu()) < 2e-3
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])

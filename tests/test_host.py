@@ -144,7 +144,7 @@ def test_synthetic_glyphs_shape_and_ink():
 
 def test_vo_tune_rejects_timing_ablations():
     """Kernel configurations that skip loads for timing ablations give wrong results: the shipped
-    library refuses to select them (only a -DVO_ABLATIONS build dispatches them)."""
+    library refuses to select them."""
     from visual_onoma_to_wave_amd import _lib
     L = _lib.lib()
     for v in (13, 16, 17, 25):
@@ -154,3 +154,4 @@ def test_vo_tune_rejects_timing_ablations():
     assert L.vo_tune(b"wgrad_cfg", 11) != 0  # the weight gradient without its loads
     assert b"ablation" in L.vo_last_error()
     assert L.vo_tune(b"wgrad_cfg", 14) == 0 and L.vo_tune(b"wgrad_cfg", 0) == 0  # A/B values stay selectable
+    assert L.vo_tune(b"gen_cfg", 1) != 0  # a knob whose every variant was deleted is an unknown key

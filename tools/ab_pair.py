@@ -6,7 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from visual_onoma_to_wave_amd import _lib, ops  # noqa: E402
+from visual_onoma_to_wave_amd import ops  # noqa: E402
 
 
 def t_ms(fn, n=10):
@@ -43,12 +43,8 @@ def main():
             fl = 2 * 2.0 * B * T * C * C * k
             a = t_ms(unfused)
             line = f"C={C} k={k} d={d}: unfused {a:.4f} ms ({fl / a / 1e9:.0f} TF/s)"
-            for cfg in {128: (0, 6), 64: (0,), 32: (0,)}[C]:
-                _lib.lib().vo_tune(b"pair_cfg", cfg)
-                f = t_ms(fused)
-                line += f"  fused[{cfg}] {f:.4f} ms ({fl / f / 1e9:.0f} TF/s)"
-            _lib.lib().vo_tune(b"pair_cfg", 0)
-            print(line, flush=True)
+            f = t_ms(fused)
+            print(line + f"  fused {f:.4f} ms ({fl / f / 1e9:.0f} TF/s)", flush=True)
 
 
 if __name__ == "__main__":

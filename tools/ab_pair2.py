@@ -3,9 +3,9 @@
 accumulate on), interleaved rounds in one process; prints ms per launch, TF/s and the max |diff|
 against pair_cfg 0.
 
-    python tools/ab_pair2.py "128:0,20,21" "64:0,20,21"
+    python tools/ab_pair2.py "128:0,93" "64:0,93,111"  # plane kernel against the LDS-tile kernels
     python tools/ab_pair2.py "rb3:128,64,32"          # the fused k = 3 ResBlock (vo_resblock3)
-    AB_RB3_CFG=0,4 python tools/ab_pair2.py "rb3:128"  # rb3_cfg values (interleaved)
+    AB_RB3_CFG=0,80 python tools/ab_pair2.py "rb3:32"  # rb3_cfg values (interleaved; 80: the LDS-frame kernel, C = 32)
 
 Set VO_LIB_PATH to time another build of the library (tools/ab_libs.sh runs two builds).
 """

@@ -2,7 +2,7 @@
 """A/B of kernel variants on the MRF shapes (B=32): each variant's output is compared with
 config 0's (same MFMA accumulation order -> bit-identical unless the tiling changes).
 
-    python tools/ab_sb.py [pair|conv] [cfg ...]
+    python tools/ab_sb.py [pair|pair64|pair32|conv] [cfg ...]   # pair_cfg 0 / 93 / 111, conv_cfg 0 / 5 / 6 / 9
 """
 import os
 import sys
@@ -65,41 +65,6 @@ def run(kind, C, T, cfgs, key):
         print(line, flush=True)
 
 
-def run_gen(cfgs, dt=torch.bfloat16, T=512):
-    """decoder / PostNet / upsampler shapes through the generic bf16 path (gen_cfg); with
-    dt=float32, T=12: the glyph encoder / variance predictor shapes"""
-    B = 32
-    shapes = [(256, 1024, 9, 1), (1024, 256, 1, 1), (256, 768, 1, 1), (256, 256, 1, 1), (512, 512, 5, 1),
-              (80, 512, 5, 1)] if T > 16 else [(256, 1024, 9, 1), (1024, 256, 1, 1), (256, 768, 1, 1),
-                                                 (256, 256, 1, 1), (256, 256, 3, 1)]
-    for Ci, Co, k, d in shapes:
-        torch.manual_seed(k)
-        x = torch.randn(B, T, Ci, device="cuda").to(dt)
-        w = ops.pack_conv_weight(torch.randn(Co, Ci, k, device="cuda") / (Ci * k) ** 0.5, dt)
-        b = torch.randn(Co, device="cuda") * 0.1
-        y = torch.empty(B, T, Co, device="cuda", dtype=dt)
-        f = lambda: ops.conv1d(x, w, b, Co=Co, K=k, dil=d, pad=d * (k - 1) // 2, out=y,  # noqa: E731
-                               compute_dtype=dt)
-        fl = 2.0 * B * T * Ci * Co * k
-        errs, best, ref = {}, {}, None
-        for cfg in cfgs:
-            _lib.lib().vo_tune(b"gen_cfg", cfg)
-            f()
-            torch.cuda.synchronize()
-            out = y.float().clone()
-            ref = out if ref is None else ref
-            errs[cfg] = float((out - ref).abs().max())
-        for _ in range(3):
-            for cfg in cfgs:
-                _lib.lib().vo_tune(b"gen_cfg", cfg)
-                best[cfg] = min(best.get(cfg, 1e9), t_ms(f))
-        line = f"gen Ci={Ci} Co={Co} k={k}:"
-        for cfg in cfgs:
-            line += f"  [{cfg}] {best[cfg]:.4f} ms {fl / best[cfg] / 1e9:.0f} TF/s d={errs[cfg]:.1e}"
-        _lib.lib().vo_tune(b"gen_cfg", 0)
-        print(line, flush=True)
-
-
 def main():
     kind = sys.argv[1] if len(sys.argv) > 1 else "pair"
     cfgs = [int(c) for c in sys.argv[2:]] or [0]
@@ -109,10 +74,6 @@ def main():
         run("pair", 64, 65536, cfgs, b"pair_cfg")
     elif kind == "pair32":
         run("pair", 32, 131072, cfgs, b"pair_cfg")
-    elif kind == "gen":
-        run_gen(cfgs)
-    elif kind == "genf32":
-        run_gen(cfgs, torch.float32, 12)
     else:
         run("conv", 256, 4096, cfgs, b"conv_cfg")
 

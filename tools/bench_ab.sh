@@ -1,5 +1,5 @@
 #!/bin/bash
-# Bench-level A/B of tuning knobs: tools/bench_ab.sh "pair_cfg=1" "pair_cfg=0" ...
+# Bench-level A/B of tuning knobs: tools/bench_ab.sh "pair_cfg=93" "pair_cfg=0" ...
 # prints ms/step and the per-stage MRF launch averages for each VO_TUNE setting
 # (bench.py --full: the per-stage averages come from its roofline pass); files under $OUT
 OUT=${OUT:-bench_out}

@@ -6,7 +6,7 @@ launch, vo_resblockk, to set against its three pair lines), with the MRF accumul
 bf16 activations and weights.  Each variant of a ``--tune key=v1,v2`` sweep is checked bit for
 bit against the first one and timed in interleaved rounds in this one process.
 
-    python tools/mrf_bench.py [--stages 0,1,2,3] [--tune pair_cfg=0,7] [--rounds 3] [--n 10]
+    python tools/mrf_bench.py [--stages 0,1,2,3] [--tune pair_cfg=0,93] [--rounds 3] [--n 10]
 """
 import argparse
 import itertools

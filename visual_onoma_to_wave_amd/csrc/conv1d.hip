@@ -329,8 +329,7 @@ __device__ __forceinline__ void conv_partial_store(const ConvArgs& a, f32x4 (&ac
 // the loop body is LDS reads + MFMAs + a few global loads / LDS stores per step (the
 // first version spent ~15 VALU+SALU instructions per MFMA on address math).
 // PRIO: s_setprio(1) around each MFMA cluster (keeps hipcc from moving the cluster across
-// the barriers; guide T5) -- A/B via conv_cfg.  ABL (timing ablation, garbage results):
-// 1 = no global loads in the main loop.
+// the barriers; guide T5): the MRF stage-0 tiles.
 // GL (bf16, NICE, stride 1): the weight taps are copied HBM / L2 -> LDS by LDS-DMA
 // (global_load_lds_dwordx4, 1 KiB per wave instruction, the XOR swizzle moved to the source
 // address as in the fused ResBlock kernels): no staging VGPRs and no ds_write for them.  The
@@ -363,7 +362,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 // reads for 9.4 MB of weights).  Halo <= SEG_HALO.
 constexpr int SEG_HALO = 8;
 template <typename TIN, typename TC, typename TOUT, int NI, int NJ, int WCO, int WT, int TPS, bool NICE, int ROLE,
-          int PRIO = 0, int ABL = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false,
+          int PRIO = 0, int S = 1, bool GL = false, bool RS = false, int EJ = 2, bool SEG = false,
           bool RAG = false>
 __global__ void __launch_bounds__(WCO * WT * 64)
 conv1d_kernel(ConvArgs a) {
@@ -374,7 +373,7 @@ conv1d_kernel(ConvArgs a) {
   constexpr int BT = 16 * NJ * WT;
   constexpr int P = Lds<TC>::PITCH;
   constexpr int VPR = KC / 8;                 // 8-element vectors per row (4)
-  constexpr bool DMA = GL && NICE && S == 1 && sizeof(TC) == 2 && sizeof(TIN) == 2 && ABL == 0;
+  constexpr bool DMA = GL && NICE && S == 1 && sizeof(TC) == 2 && sizeof(TIN) == 2;
   constexpr bool SPLIT = RS && DMA && (NT / 64) % 2 == 0;
   constexpr int MAXV = SPLIT ? 1 : SEG ? ((BT / 16) * (16 + SEG_HALO) * VPR + NT - 1) / NT
                                       : (((BT - 1) * S + 1 + HALO_MAX) * VPR + NT - 1) / NT;
@@ -553,9 +552,6 @@ conv1d_kernel(ConvArgs a) {
 #pragma unroll
     for (int s = 0; s < MAXVA; ++s) {
       wo[s] = xr[s] && (NICE || c0 + xc[s] < a.Ci);
-      if constexpr (ABL == 1) {
-        if (c > 0) { wr[s].zero(); continue; }
-      }
       wr[s].load(X + xg[s] + (NICE ? c0 : min(c0, a.Ci - 8 - xc[s])));
     }
   };
@@ -629,9 +625,6 @@ conv1d_kernel(ConvArgs a) {
     for (int s = 0; s < WV; ++s) {
       const int k = min(k0 + wk[s], a.K - 1);  // taps >= K are skipped by the MFMA loop
       wo[s] = wok[s] && (NICE || c0 + wq[s] < a.Ci);
-      if constexpr (ABL == 1) {
-        if (c > 0 || k0 > 0) { wr[s].zero(); continue; }
-      }
       wr[s].load(Wp + k * tap_stride + wg[s] + (NICE ? c0 : min(c0, a.Ci - 8 - wq[s])));
     }
   };
@@ -883,13 +876,13 @@ static bool splitk_bf16_ok(const vo_conv1d_desc* d) {
          d->variant == 0 && !d->bias && !d->res1 && !d->res2 && !d->ymask && d->pre_act == VO_ACT_NONE &&
          d->post_act == VO_ACT_NONE && d->out_scale == 1.f && d->Co <= 256 && d->Co % 64 == 0 && d->Ci % KC == 0 &&
          (int64_t)(d->Ci / KC) * d->K >= 64 && (int64_t)d->B * d->T_out >= 8192 && d->ldy == d->Co &&
-         vo_tune_get("splitk_cfg") != 3 && vo_tune_get("splitk_cfg") != 1 && vo_tune_get("gen_cfg") == 0;
+         vo_tune_get("splitk_cfg") != 3 && vo_tune_get("splitk_cfg") != 1;
 }
 
 static bool splitk_plan(const vo_conv1d_desc* d, int* splits, int* kcs) {
   *splits = 1;
   *kcs = 0;
-  if (vo_tune_get("splitk_cfg") == 1 || vo_tune_get("gen_cfg") != 0) return false;
+  if (vo_tune_get("splitk_cfg") == 1) return false;
   if (d->compute_dtype == VO_BF16) {
     if (!splitk_bf16_ok(d)) return false;
     const int n_chunks = d->Ci / KC;
@@ -918,78 +911,6 @@ static bool splitk_plan(const vo_conv1d_desc* d, int* splits, int* kcs) {
   return true;
 }
 
-// ------------------------------------------------------------------ K = 1 convs (Linear layers)
-// The transformer's fused q/k/v, fc and FFN w_2 are plain GEMMs over B*T = 16k rows with a
-// 256..1024-deep reduction (SubLayers.py:39-54,85-93).  conv1d_kernel stages one 32-channel chunk
-// per barrier with one chunk of prefetch; at 8..32 chunks that pipeline never fills (q/k/v: 21 us
-// for 33 MB, 1.6 TB/s).  Here each wave reads its own A (weight rows) and B (input rows) fragments
-// straight from L2 through a D-step register ring -- no LDS, no barriers; the waves of a workgroup
-// that share weight rows or input rows meet in L1.  Every accumulator sees the same MFMA sequence
-// as in conv1d_kernel (chunks in order, lane group q = channels 8q..8q+7, the same weight-row
-// permutation) and the same epilogue, so the outputs are bit-identical to it.
-// Measured and dropped (tools/probes/lin_probe.py, profiles/r05/lin_probe.txt): 1.3-2.2x SLOWER than
-// conv1d_kernel at every tile (q/k/v 23.0 us -> 30.8 at 128 x 128, 41.3 at 128 co x 64 rows) -- the
-// per-wave fragment loads (16 rows x 64 B per instruction) bind where the LDS tile shares them.
-// A/B library only (make abl; lin_cfg 2 / 3 / 4 / 5).
-#ifdef VO_ABLATIONS
-template <typename TOUT, int NI, int NJ, int WCO, int WT, int D, int NC>
-__global__ void __launch_bounds__(WCO * WT * 64) lin_kernel(ConvArgs a) {
-  // NC = Ci / 32 chunks, fully unrolled: straight-line code, so the compiler's vmcnt waits count
-  // exactly D - 1 chunks of loads in flight (a rolled loop got a near-drain wait at its back-edge)
-  constexpr int BCO = 16 * NI * WCO;
-  constexpr int BT = 16 * NJ * WT;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wave_co0 = (wave % WCO) * 16 * NI;
-  const int wave_t0 = (wave / WCO) * 16 * NJ;
-  const int b = blockIdx.x / a.tiles_per_b;
-  const int t0 = (blockIdx.x - b * a.tiles_per_b) * BT;
-  const int co_blk = blockIdx.y * BCO;
-  const int lr = lane & 15, lq = lane >> 4;
-  const bf16_t* W = reinterpret_cast<const bf16_t*>(a.w) + lq * 8;
-  const bf16_t* X = reinterpret_cast<const bf16_t*>(a.x) + (int64_t)b * a.xbs + lq * 8;
-  const bf16_t* ap[NI];
-  const bf16_t* bp[NJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) ap[i] = W + (int64_t)(co_blk + wave_co0 + NI * 4 * (lr >> 2) + 4 * i + (lr & 3)) * (NC * KC);
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) bp[j] = X + (int64_t)min(t0 + wave_t0 + 16 * j + lr, a.T_in - 1) * a.ldx;
-
-  Frag<bf16_t> af[D][NI], bfr[D][NJ];
-#pragma unroll
-  for (int d = 0; d < D && d < NC; ++d) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) af[d][i].load(ap[i] + d * KC);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) bfr[d][j].load(bp[j] + d * KC);
-  }
-  // sched_barrier: keep every chunk's loads where they are written (hipcc otherwise sinks them next
-  // to their MFMAs -- fewer registers, no loads in flight)
-  __builtin_amdgcn_sched_barrier(0);
-  f32x4 acc[NI][NJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int d = c % D;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma(af[d][i], bfr[d][j], acc[i][j]);
-    if (c + D < NC) {  // chunk c + D into the freed slot
-#pragma unroll
-      for (int i = 0; i < NI; ++i) af[d][i].load(ap[i] + (c + D) * KC);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bfr[d][j].load(bp[j] + (c + D) * KC);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  conv_epilogue<TOUT, NI, NJ>(a, acc, b, t0, co_blk, wave_co0, wave_t0, lane);
-}
-#endif  // VO_ABLATIONS
-
 // ------------------------------------------------------------------ host dispatch
 // vo_conv1d = conv1d_check (arguments -> type triple), a select_* rule (descriptor, compute width, vo_tune knobs -> tile),
 // plan_tile (nice, LDS bytes, reduction splits), launch_plan (tile -> instantiation).  All but the last are plain host
@@ -997,10 +918,10 @@ __global__ void __launch_bounds__(WCO * WT * 64) lin_kernel(ConvArgs a) {
 //
 // A tile, written once: a wave holds NI x NJ MFMA tiles of 16 channels x 16 rows, a workgroup is WCO x WT waves, so
 // BCO = 16 NI WCO output channels x BT = 16 NJ WT rows.  TPS = taps per pipeline step in bf16 compute (4-byte compute
-// steps one tap; 0 = a lin_kernel tile); ROLE .. SEG are conv1d_kernel's parameters of the same names.  The conv stride
+// steps one tap); ROLE .. SEG are conv1d_kernel's parameters of the same names.  The conv stride
 // is the descriptor's, not the tile's: launch_tile takes it beside the tile.
 struct Tile {
-  int NI, NJ, WCO, WT, TPS, ROLE = 0, PRIO = 0, ABL = 0;
+  int NI, NJ, WCO, WT, TPS, ROLE = 0, PRIO = 0;
   bool GL = false, RS = false;
   int EJ = 2;
   bool SEG = false;
@@ -1008,31 +929,19 @@ struct Tile {
   constexpr int bt() const { return 16 * NJ * WT; }
   constexpr Tile role(int r, int prio = 0) const { Tile t = *this; t.ROLE = r; t.PRIO = prio; return t; }
   constexpr Tile dma(bool rs = false) const { Tile t = *this; t.GL = true; t.RS = rs; return t; }  // weights by LDS-DMA; role split
-  constexpr Tile tps(int n) const { Tile t = *this; t.TPS = n; return t; }
   constexpr Tile seg() const { Tile t = *this; t.SEG = true; return t; }
 };
 // T<BCO>x<BT> {NI, NJ, WCO, WT, TPS}; _n<NI>w<WCO> names the twin of equal BCO x BT (128 x 32 and 64 x 64: the strided /
-// grouped convs' tiles, 64 x 64 also gen_cfg 7; 64 x 128: the Co = 80 tile); _seg = utterance-segment tile (BT / 16
+// grouped convs' tiles; 64 x 128: the Co = 80 tile); _seg = utterance-segment tile (BT / 16
 // utterances); _mrf<s> = MRF stage s in its own ROLE (stage 0: s_setprio, weights by LDS-DMA, _rs = role-split staging)
-constexpr Tile T32x16{1, 1, 2, 1, 4}, T64x16{1, 1, 4, 1, 4}, T128x16{2, 1, 4, 1, 4}, T128x32{2, 2, 4, 1, 4},
+constexpr Tile T32x16{1, 1, 2, 1, 4}, T128x16{2, 1, 4, 1, 4}, T128x32{2, 2, 4, 1, 4},
     T128x32_n4w2{4, 1, 2, 2, 2}, T32x64{2, 1, 1, 4, 4}, T64x64{2, 2, 2, 2, 2}, T64x64_n4w1{4, 1, 1, 4, 4},
     T128x64{4, 2, 2, 2, 2}, T64x128{2, 4, 2, 2, 2}, T64x128_n4w1{4, 2, 1, 4, 4}, T128x128{4, 4, 2, 2, 2},
-    T256x128{4, 4, 4, 2, 2}, T32x256{2, 4, 1, 4, 4}, T64x256{4, 4, 1, 4, 4}, T128x256{4, 4, 2, 4, 2}, T256x256{4, 8, 4, 2, 2};
+    T32x256{2, 4, 1, 4, 4}, T64x256{4, 4, 1, 4, 4}, T128x256{4, 4, 2, 4, 2}, T256x256{4, 8, 4, 2, 2};
 constexpr Tile T32x64_seg = Tile{1, 2, 2, 2, 1}.seg(), T64x64_seg = Tile{2, 2, 2, 2, 1}.seg(),
                T32x128_seg = Tile{1, 4, 2, 2, 1}.seg(), T64x128_seg = Tile{2, 4, 2, 2, 1}.seg();
 constexpr Tile T256x256_mrf0 = T256x256.role(1, 1).dma(), T256x256_mrf0_rs = T256x256.role(1, 1).dma(true),
                T128x128_mrf1 = T128x128.role(2), T64x256_mrf2 = T64x256.role(3), T32x256_mrf3 = T32x256.role(4);
-#ifdef VO_ABLATIONS  // A/B library only (measured and dropped): _t<TPS>, _gl / _rs = dma() / dma(true); lin_kernel co x rows
-constexpr Tile A256x256_t1_gl = T256x256.tps(1).dma(), A256x256_t1_rs = T256x256.tps(1).dma(true),
-               A128x128_t1_gl = T128x128.tps(1).dma(), A256x256_t1 = T256x256.tps(1), A64x128_t1 = T64x128.tps(1),
-               A128x128_mrf0 = T128x128.role(1), A256x256_mrf0_plain = T256x256.role(1),
-               A256x256_mrf0_prio = T256x256.role(1, 1), A256x256_mrf0_t3 = T256x256.role(1, 1).tps(3).dma(),
-               A256x256_mrf0_t1 = T256x256.role(1, 1).tps(1).dma(), A256x256_mrf0_t1_rs = T256x256.role(1, 1).tps(1).dma(true);
-constexpr Tile LIN_64x64{2, 2, 2, 2, 0}, LIN_128x128{4, 4, 2, 2, 0}, LIN_64x128{2, 4, 2, 2, 0}, LIN_128x64{4, 2, 2, 2, 0};
-#define VO_AB(...) , __VA_ARGS__
-#else
-#define VO_AB(...)
-#endif
 
 // (TIN, TC, TOUT) of an instantiation: F = float, B = bf16_t, X = bx3_t (split-bf16, VO_F32X3)
 enum ConvTypes { FFF, FXF, BBB, BBF, FBB, FBF };
@@ -1077,8 +986,8 @@ static int launch_tile(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t s
   if (T.SEG) a.tiles_per_b = 1;
   a.partial = p.splits > 1 ? reinterpret_cast<float*>(d->workspace) : nullptr;
   a.kcs = p.kcs;
-  auto kern = p.nice ? conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, true, T.ROLE, T.PRIO, T.ABL, S, T.GL, T.RS, T.EJ, T.SEG, RAG>
-                     : conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, false, T.ROLE, T.PRIO, T.ABL, S, false, false, 2, T.SEG, RAG>;
+  auto kern = p.nice ? conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, true, T.ROLE, T.PRIO, S, T.GL, T.RS, T.EJ, T.SEG, RAG>
+                     : conv1d_kernel<TIN, TC, TOUT, T.NI, T.NJ, T.WCO, T.WT, TPS, false, T.ROLE, T.PRIO, S, false, false, 2, T.SEG, RAG>;
   const unsigned gx = T.SEG ? (unsigned)((d->B + BT / 16 - 1) / (BT / 16)) : (unsigned)(a.tiles_per_b * d->B);
   dim3 grid(gx, (unsigned)a.co_tiles, (unsigned)p.splits);
   hipLaunchKernelGGL(kern, grid, dim3(T.WCO * T.WT * 64), p.lds, st, a);
@@ -1093,7 +1002,6 @@ static int launch_tile(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t s
 static int plan_tile(const vo_conv1d_desc* d, ConvPlan* p) {
   const Tile& t = *p->tile;
   p->nice = false; p->splits = 1; p->kcs = 0; p->lds = 0;
-  if (t.TPS == 0) return VO_OK;  // lin_kernel
   const int S = p->S, tin = kTypeBytes[p->types][0], tc = kTypeBytes[p->types][1];
   const int BCO = t.bco(), BT = t.bt(), tps = tc == 2 ? t.TPS : 1, halo = (d->K - 1) * d->dil;
   // the ragged instantiations exist for the tiles select_types picks and the MRF stage-0 role (strided / grouped
@@ -1102,7 +1010,7 @@ static int plan_tile(const vo_conv1d_desc* d, ConvPlan* p) {
   const int win_rows = t.SEG ? (BT / 16) * (16 + halo) : (BT - 1) * S + 1 + halo;
   p->nice = d->Ci % KC == 0 && d->Co % BCO == 0;
   // role-split kernels (RS): + the raw window staging area of conv1d_kernel (XPW pieces per window wave)
-  const bool spl = t.RS && t.GL && S == 1 && tc == 2 && tin == 2 && t.ABL == 0 && (t.WCO * t.WT) % 2 == 0;
+  const bool spl = t.RS && t.GL && S == 1 && tc == 2 && tin == 2 && (t.WCO * t.WT) % 2 == 0;
   const int nwx = t.WCO * t.WT / 2;
   const size_t raw = spl ? 2 * (size_t)((((BT - 1) * S + 1 + HALO_MAX) * (KC / 8) + 64 * nwx - 1) / (64 * nwx)) * nwx * 1024 : 0;
   p->lds = (size_t)(2 * win_rows + 2 * tps * BCO + 1) * (tc == 2 ? Lds<bf16_t>::PITCH : Lds<float>::PITCH) * tc + (p->nice ? raw : 0);
@@ -1119,9 +1027,9 @@ static int plan_tile(const vo_conv1d_desc* d, ConvPlan* p) {
   return VO_OK;
 }
 
-// the VO_CONV1D_LAUNCH_FIELDS record of a plan (rec zeroed by the caller: it stays so for the upsampler and lin_kernel)
+// the VO_CONV1D_LAUNCH_FIELDS record of a plan (rec zeroed by the caller: it stays so for the upsampler)
 static void plan_record(const vo_conv1d_desc* d, const ConvPlan& p, int32_t* rec) {
-  if (p.ups || p.tile->TPS == 0) return;
+  if (p.ups) return;
   const Tile& t = *p.tile;
   const int32_t r[VO_CONV1D_LAUNCH_FIELDS] = {t.bco(), t.bt(), p.S, t.SEG, p.nice, p.splits, kTypeBytes[p.types][0],
                                               kTypeBytes[p.types][1], kTypeBytes[p.types][2], t.ROLE, d->compute_dtype, t.NI, t.WCO};
@@ -1139,9 +1047,9 @@ static const Tile* select_disc(const vo_conv1d_desc* d) {
   if (d->Co <= 32 || cog <= 32) return &T32x64;
   if (d->Co <= 64 || cog <= 64) return &T64x64_n4w1;
   // 64 x 64 where 128 x 64 tiles would leave fewer than 256 workgroups (the MPD's stride-3 layers over joined
-  // period columns): C5 23.63 -> 23.57 ms in one process (tile_cfg 4 = off)
+  // period columns): C5 23.63 -> 23.57 ms in one process
   const int64_t t64 = (int64_t)d->B * ((d->T_out + 63) / 64) * ((d->Co + 127) / 128);
-  if (vo_tune_get("tile_cfg") != 4 && t64 < 256) return &T64x64_n4w1;
+  if (t64 < 256) return &T64x64_n4w1;
   return &T128x64;
 }
 
@@ -1149,21 +1057,15 @@ static const Tile* select_disc(const vo_conv1d_desc* d) {
 static const Tile* select_role(const vo_conv1d_desc* d, int role) {
   if (role != 1) return role == 2 ? &T128x128_mrf1 : role == 3 ? &T64x256_mrf2 : &T32x256_mrf3;
   // C = 256: 256 x 256 tile, 8 waves of 64 co x 128 rows (each weight tap feeds twice the rows of the 128 x 128 tile:
-  // 0.095/0.151/0.208 -> 0.077/0.125/0.172 ms for k = 3/7/11 at B = 32, bit-identical).  conv_cfg 1 = the 128 x 128 tile.
-  // s_setprio(1) around each MFMA cluster: +1-3 % (0.1667 -> 0.1654 ms at k = 11); conv_cfg 2 = without
+  // 0.095/0.151/0.208 -> 0.077/0.125/0.172 ms for k = 3/7/11 at B = 32, bit-identical).
+  // s_setprio(1) around each MFMA cluster: +1-3 % (0.1667 -> 0.1654 ms at k = 11).
   // Round 2: weights by LDS-DMA (GL): 0.084 / 0.134 / 0.171 -> 0.083 / 0.126 / 0.163 ms for k = 3 / 7 / 11 alone
-  // (tools/ab_conv_cfg.py, bit-identical), within noise in the bench step; conv_cfg 3 = register-staged weights,
-  // 4 = GL with 3-tap steps (spills)
+  // (bit-identical), within noise in the bench step; GL with 3-tap steps spilled
   const int cc = vo_tune_get("conv_cfg");
   if (d->lens && cc != 0) {
     vo_set_error("conv1d: conv_cfg=%d selects a kernel without a ragged (lens) form", cc);
     return nullptr;
   }
-#ifdef VO_ABLATIONS  // measured-and-dropped tiles (A/B builds only: make abl)
-  if (cc >= 1 && cc <= 4) return cc == 1 ? &A128x128_mrf0 : cc == 2 ? &A256x256_mrf0_plain : cc == 3 ? &A256x256_mrf0_prio : &A256x256_mrf0_t3;
-  // one tap per step (k = 3's second 2-tap step re-fetches tap 2 as its padding tap)
-  if (cc == 7 || cc == 8) return cc == 7 ? &A256x256_mrf0_t1 : &A256x256_mrf0_t1_rs;
-#endif
   // Round 2: role-split staging (RS: half the waves issue the weight DMA, half copy the window by LDS-DMA two chunks
   // ahead; bare step barriers): k = 7 / 11 0.137 / 0.175 -> 0.130 / 0.168 ms, k = 3 0.084 -> 0.096 (two-step chunks: the
   // weight waves' 8 DMA pieces per step, not the window, bind) -- k >= 5 only; conv_cfg 5 forces it, 6 disables it
@@ -1177,8 +1079,8 @@ static const Tile* select_role(const vo_conv1d_desc* d, int role) {
   return cc == 5 || (cc != 6 && d->K >= 5) ? &T256x256_mrf0_rs : &T256x256_mrf0;
 }
 
-// Every other conv; tin / tc = sizeof the input and the LDS compute element
-static const Tile* select_types(const vo_conv1d_desc* d, int tin, int tc) {
+// Every other conv; tc = sizeof the LDS compute element
+static const Tile* select_types(const vo_conv1d_desc* d, int tc) {
   const int64_t rows = (int64_t)d->B * d->T_out;
   // short sequences (the glyph encoder / phoneme-level predictors run at T_src ~ 12): one
   // 16- or 32-row time tile, waves spread over output channels
@@ -1195,83 +1097,48 @@ static const Tile* select_types(const vo_conv1d_desc* d, int tin, int tc) {
   if (d->T_out <= 16 && d->Co >= 64) {
     // fp32 (glyph encoder, variance predictors at B = 32, T = 12): 32 x 16 tiles, 4x the
     // workgroups of 128 x 16: FFN w_1 66 -> 51 us, w_2 28 -> 20, predictor k3 20 -> 13
-    // (tools/ab_sb.py genf32 5 3); gen_cfg 2 = 64 x 16, 5 = 128 x 16
-    const int gc = vo_tune_get("gen_cfg");
-    return gc == 2 ? &T64x16 : (gc != 5 && tc == 4) ? &T32x16 : &T128x16;
+    return tc == 4 ? &T32x16 : &T128x16;
   }
   if (d->T_out <= 32 && d->Co >= 64) return &T128x32;
   if (d->Co <= 32) return &T32x256;
   if (d->Co <= 64 || d->Co == 80) {
     // Co = 80 (PostNet output conv, mel_linear at B*T = 16384 rows): 64 x 128 tiles, twice the
     // workgroups of 64 x 256 (512 -> 80 k5 36.7 -> 29.7 us; tools/probes/small_convs.py)
-    const int gc = vo_tune_get("gen_cfg");
-    return (gc == 6 || (d->Co == 80 && gc != 8)) ? &T64x128_n4w1 : gc == 7 ? &T64x64_n4w1 : &T64x256;
+    return d->Co == 80 ? &T64x128_n4w1 : &T64x256;
   }
   if (rows <= 2048) return &T64x64;
-#ifdef VO_ABLATIONS
-  if (tc == 2 && tin == 2) {
-    // K = 1 (Linear layers), A/B only: the LDS-free register-ring kernel, lin_cfg 2 / 3 / 4 / 5 =
-    // 64 x 64, 128 x 128, 64 co x 128 rows, 128 co x 64 rows (measured slower, see lin_kernel)
-    const int lc = vo_tune_get("lin_cfg");
-    if (lc >= 2 && d->K == 1 && d->pad == 0 && d->T_in == d->T_out && !d->transposed && d->variant == 0 &&
-        d->pre_act == VO_ACT_NONE && d->Ci % KC == 0 && d->x_bstride % 8 == 0 &&
-        (d->Ci == 256 || d->Ci == 512 || d->Ci == 1024)) {
-      if (lc == 2 && d->Co % 64 == 0) return &LIN_64x64;
-      if (lc == 3 && d->Co % 128 == 0) return &LIN_128x128;
-      if (lc == 4 && d->Co % 64 == 0) return &LIN_64x128;
-      if (lc == 5 && d->Co % 128 == 0) return &LIN_128x64;
-    }
-  }
-  if (tc == 2) {  // K = 1 staging A/B: one tap per step (TPS 1), weights by LDS-DMA (GL), role split (RS)
-    const int gq = vo_tune_get("gen_cfg");
-    if (gq == 13 && d->Co % 256 == 0) return &A256x256_t1_gl;
-    if (gq == 14 && d->Co % 256 == 0) return &A256x256_t1_rs;
-    if (gq == 15 && d->Co % 128 == 0) return &A128x128_t1_gl;
-    if (gq == 16 && d->Co % 256 == 0) return &A256x256_t1;
-    if (gq == 17) return &A64x128_t1;
-  }
-#endif
   if (tc == 2) {
     if (d->workspace && splitk_bf16_ok(d)) return &T256x256;  // split reduction
-    // decoder shapes at B*T = 16384 rows (tools/ab_sb.py gen): wide outputs (FFN w_1 k9 1024,
+    // decoder shapes at B*T = 16384 rows: wide outputs (FFN w_1 k9 1024,
     // fused q/k/v 768) -> 256 x 256 tiles (-18 %); 1x1 convs to 256 channels -> 64 x 128
-    // (twice the workgroups, -12 %).  gen_cfg 1 forces the 128 x 128 tile (A/B).
-    if (vo_tune_get("gen_cfg") != 1) {
-      // 256 x 256 for the wide convs.  In isolation (tools/probes/wide_convs.py,
-      // profiles/r01j/wide_convs.txt) 256 co x 128 rows looked 11 % faster on FFN w_1, but in the
-      // bench step its 12 decoder launches took 818 us against 584 (profiles/r01k/): kept out.
-      // ups0 (polyphase 512 -> 8 x 256, K = 2) on the role-split staging was 11-20 % slower (its
-      // one-step chunks: 8 weight-DMA pieces per weight wave per 2-tap step; tools/probes/ups0_probe.py)
-      // (unless that leaves fewer than 128 workgroups: the MPD's joined period columns, ~4-5k rows x
-      // 1024 channels, got 68-80 -- there the 128 x 128 tile below)
-      const int64_t t256 = (int64_t)d->B * ((d->T_out + 255) / 256) * (d->Co / 256);
-      // (utterances of >= 256 rows: at T_out = 128 -- the MSD's 1024-channel layers -- half of every 256-row
-      // tile was padding: C5 23.68 -> 23.43 ms with them on the tiles below; tile_cfg 9 = the round-5 rule)
-      const bool t_ok = d->T_out >= 256 || vo_tune_get("tile_cfg") == 9;
-      if (vo_tune_get("gen_cfg") != 11 && t_ok && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return &T256x256;
-      if (vo_tune_get("gen_cfg") < 9 && d->K == 1 && d->Co <= 256) return &T64x128;
-      // Co <= 256 k > 1 with fewer than 512 128 x 128 tiles (the C4 decoder's FFN w_1 input gradient, 1024 ->
-      // 256 k9 at 16384 rows: 125 -> 106 us, tools/probes/dgrad_tiles.py): 64 x 128, twice the workgroups
-      const int64_t t128 = (int64_t)d->B * ((d->T_out + 127) / 128) * ((d->Co + 127) / 128);
-      if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return &T64x128;
-      // wide convs with fewer than 256 128 x 128 tiles (C5's MPD over joined period columns, 1024 -> 1024
-      // k = 5 at 2-5 k rows: 136-312 workgroups) on 64 x 128 tiles too: C5 24.07 -> 23.75 ms (tile_cfg 1 = off)
-      if (vo_tune_get("tile_cfg") != 1 && d->Co % 64 == 0 && t128 < 256) return &T64x128;
-    }
+    // (twice the workgroups, -12 %).
+    // 256 x 256 for the wide convs.  In isolation (profiles/r01j/wide_convs.txt) 256 co x 128 rows looked
+    // 11 % faster on FFN w_1, but in the bench step its 12 decoder launches took 818 us against 584 (profiles/r01k/): kept out.
+    // ups0 (polyphase 512 -> 8 x 256, K = 2) on the role-split staging was 11-20 % slower (its
+    // one-step chunks: 8 weight-DMA pieces per weight wave per 2-tap step; tools/probes/ups0_probe.py)
+    // (unless that leaves fewer than 128 workgroups: the MPD's joined period columns, ~4-5k rows x
+    // 1024 channels, got 68-80 -- there the tiles below)
+    const int64_t t256 = (int64_t)d->B * ((d->T_out + 255) / 256) * (d->Co / 256);
+    // (utterances of >= 256 rows: at T_out = 128 -- the MSD's 1024-channel layers -- half of every 256-row
+    // tile was padding: C5 23.68 -> 23.43 ms with them on the tiles below)
+    if (d->T_out >= 256 && d->Co >= 768 && d->Co % 256 == 0 && t256 >= 128) return &T256x256;
+    if (d->K == 1 && d->Co <= 256) return &T64x128;
+    // Co <= 256 k > 1 with fewer than 512 128 x 128 tiles (the C4 decoder's FFN w_1 input gradient, 1024 ->
+    // 256 k9 at 16384 rows: 125 -> 106 us): 64 x 128, twice the workgroups
+    const int64_t t128 = (int64_t)d->B * ((d->T_out + 127) / 128) * ((d->Co + 127) / 128);
+    if (d->Co <= 256 && d->Co % 64 == 0 && t128 < 512) return &T64x128;
+    // wide convs with fewer than 256 128 x 128 tiles (C5's MPD over joined period columns, 1024 -> 1024
+    // k = 5 at 2-5 k rows: 136-312 workgroups) on 64 x 128 tiles too: C5 24.07 -> 23.75 ms
+    if (d->Co % 64 == 0 && t128 < 256) return &T64x128;
     // mid-width convs (PostNet 512 -> 512 k5, conv_pre 80 -> 512 k7 at 16384 rows): 128 x 256
     // tiles (twice the rows per staged weight tap): 512 k5 67.9 -> 63.4 us, 80 k7 27.6 -> 27.0,
-    // bit-identical (tools/probes/mid_convs.py); the Co = 128 polyphase upsampler is slower with
-    // it (210 -> 234 us).  gen_cfg 9 forces it, gen_cfg 10 = 256 x 128 (no gain), gen_cfg 1 = 128 x 128.
-    const int gc = vo_tune_get("gen_cfg");
-    if (gc == 9 || (gc != 1 && gc != 10 && d->Co >= 512 && d->Co < 768 && d->Co % 128 == 0 && !d->transposed)) return &T128x256;
-    if (gc == 10) return &T256x128;
-    if (gc == 11) return &T64x128;                       // (A/B)
-    if (gc == 12 && d->Co % 256 == 0) return &T256x256;  // (A/B)
-    // bf16: 64 x 128 in place of the 128 x 128 default (C5 23.68 -> 23.52 ms, C4 and inference shapes
-    // unaffected); tile_cfg 9 = the round-5 rule
-    if (vo_tune_get("tile_cfg") != 9) return &T64x128;
+    // bit-identical; the Co = 128 polyphase upsampler is slower with it (210 -> 234 us); 256 x 128: no gain
+    if (d->Co >= 512 && d->Co < 768 && d->Co % 128 == 0 && !d->transposed) return &T128x256;
+    // bf16: 64 x 128 in place of the 128 x 128 tile of 4-byte compute (C5 23.68 -> 23.52 ms, C4 and inference
+    // shapes unaffected)
+    return &T64x128;
   }
-  return &T128x128;
+  return &T128x128;  // 4-byte compute
 }
 
 // ---- tile -> instantiation: the one place that says which (tile, types, RAG, S) combinations are compiled
@@ -1283,53 +1150,28 @@ static int launch_among(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t 
   return rc;
 }
 
-#ifdef VO_ABLATIONS
-// lin_kernel: K = 1, bf16 input and compute, Ci = 32 NC (256 / 512 / 1024), Co % BCO == 0 (checked by select_types)
-template <typename TOUT, const Tile& T, int D, int NC>
-static int launch_lin(const vo_conv1d_desc* d, hipStream_t st) {
-  ConvArgs a = conv_args(d, T.bco(), T.bt());
-  a.K = 1; a.dil = 1; a.pad = 0;
-  a.pre_act = VO_ACT_NONE; a.pre_slope = 0.f;
-  a.transposed = a.up_stride = a.up_pad = a.up_cout = a.up_tout = 0;
-  a.lens = nullptr; a.lens_scale = 0;
-  a.cig = d->Ci; a.cog = d->Co;
-  dim3 grid((unsigned)(a.tiles_per_b * d->B), (unsigned)a.co_tiles);
-  hipLaunchKernelGGL((lin_kernel<TOUT, T.NI, T.NJ, T.WCO, T.WT, D, NC>), grid, dim3(T.WCO * T.WT * 64), 0, st, a);
-  VO_RETURN_LAUNCH();
-}
-template <typename TOUT, int NC>
-static int launch_lin_tile(const vo_conv1d_desc* d, const Tile* t, hipStream_t st) {
-  if (t == &LIN_64x64) return launch_lin<TOUT, LIN_64x64, 4, NC>(d, st);
-  if (t == &LIN_128x128) return launch_lin<TOUT, LIN_128x128, 3, NC>(d, st);
-  if (t == &LIN_64x128) return launch_lin<TOUT, LIN_64x128, 4, NC>(d, st);
-  return launch_lin<TOUT, LIN_128x64, 4, NC>(d, st);
-}
-#endif  // VO_ABLATIONS
-
 // RAG: the ragged instantiations of the same tiles (vo_conv1d with lens); SEG tiles: 4-byte compute only, no ragged form
 template <typename TIN, typename TC, typename TOUT, bool RAG = false>
 static int launch_types(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
+  // the tiles select_types returns at one compute width only, then those of both
   int rc = kNoTile;
-  if constexpr (sizeof(TC) == 4) rc = launch_among<TIN, TC, TOUT, false, 1, T32x64_seg, T64x64_seg, T32x128_seg, T64x128_seg>(d, p, st);
-  if constexpr (sizeof(TC) == 2)
-    rc = launch_among<TIN, TC, TOUT, RAG, 1, T64x128, T256x128, T128x256, T256x256 VO_AB(
-        A256x256_t1_gl, A256x256_t1_rs, A128x128_t1_gl, A256x256_t1, A64x128_t1)>(d, p, st);
-#ifdef VO_ABLATIONS
-  if constexpr (sizeof(TC) == 2 && sizeof(TIN) == 2)
-    if (p.tile->TPS == 0)
-      return d->Ci == 256 ? launch_lin_tile<TOUT, 8>(d, p.tile, st)
-                          : d->Ci == 512 ? launch_lin_tile<TOUT, 16>(d, p.tile, st) : launch_lin_tile<TOUT, 32>(d, p.tile, st);
-#endif
+  if constexpr (sizeof(TC) == 4) {
+    rc = launch_among<TIN, TC, TOUT, false, 1, T32x64_seg, T64x64_seg, T32x128_seg, T64x128_seg>(d, p, st);
+    if (rc == kNoTile) rc = launch_among<TIN, TC, TOUT, RAG, 1, T32x16, T128x128>(d, p, st);
+  } else {
+    rc = launch_among<TIN, TC, TOUT, RAG, 1, T128x16, T64x128, T128x256, T256x256>(d, p, st);
+  }
   if (rc != kNoTile) return rc;
-  return launch_among<TIN, TC, TOUT, RAG, 1, T32x16, T64x16, T128x16, T128x32, T32x256, T64x256, T64x128_n4w1, T64x64_n4w1,
-                      T64x64, T128x128>(d, p, st);
+  return launch_among<TIN, TC, TOUT, RAG, 1, T128x32, T32x256, T64x256, T64x128_n4w1, T64x64>(d, p, st);
 }
 
-// strided / grouped: S = 8 compiles all four tiles (only 128 x 32 is selected there), the other strides three
+// strided / grouped: stride 8 has the one tile select_disc returns for it, the other strides three
 template <typename TIN, typename TC, typename TOUT, int S>
 static int launch_disc_s(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
-  if constexpr (S >= 8) return launch_among<TIN, TC, TOUT, false, S, T128x32_n4w2, T32x64, T64x64_n4w1, T128x64>(d, p, st);
-  return launch_among<TIN, TC, TOUT, false, S, T32x64, T64x64_n4w1, T128x64>(d, p, st);
+  if constexpr (S >= 8)
+    return launch_among<TIN, TC, TOUT, false, S, T128x32_n4w2>(d, p, st);
+  else
+    return launch_among<TIN, TC, TOUT, false, S, T32x64, T64x64_n4w1, T128x64>(d, p, st);
 }
 template <typename TIN, typename TC, typename TOUT>
 static int launch_disc(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t st) {
@@ -1354,8 +1196,7 @@ static int launch_plan(const vo_conv1d_desc* d, const ConvPlan& p, hipStream_t s
   else if (p.role && rag)  // MRF stages: bf16 only, ragged for stage 0 alone
     rc = launch_among<bf16_t, bf16_t, bf16_t, true, 1, T256x256_mrf0, T256x256_mrf0_rs>(d, p, st);
   else if (p.role)
-    rc = launch_among<bf16_t, bf16_t, bf16_t, false, 1, T256x256_mrf0, T256x256_mrf0_rs, T128x128_mrf1, T64x256_mrf2, T32x256_mrf3 VO_AB(
-        A128x128_mrf0, A256x256_mrf0_plain, A256x256_mrf0_prio, A256x256_mrf0_t3, A256x256_mrf0_t1, A256x256_mrf0_t1_rs)>(d, p, st);
+    rc = launch_among<bf16_t, bf16_t, bf16_t, false, 1, T256x256_mrf0, T256x256_mrf0_rs, T128x128_mrf1, T64x256_mrf2, T32x256_mrf3>(d, p, st);
   else switch (p.types) {  // ragged: fp32, and bf16 compute with a bf16 output
     case FXF: rc = launch_types<float, bx3_t, float>(d, p, st); break;
     case FFF: rc = rag ? launch_types<float, float, float, true>(d, p, st) : launch_types<float, float, float>(d, p, st); break;
@@ -1464,7 +1305,7 @@ static int conv1d_plan(const vo_conv1d_desc* d, ConvPlan* p) {
   p->plane = p->role == 1 && vo_conv1d_plane_takes(d) != 0;
   p->S = d->stride > 1 ? d->stride : 1;
   p->tile = d->stride > 1 || d->groups > 1 ? select_disc(d) : p->role ? select_role(d, p->role)
-                                           : select_types(d, kTypeBytes[p->types][0], kTypeBytes[p->types][1]);
+                                           : select_types(d, kTypeBytes[p->types][1]);
   return p->tile ? plan_tile(d, p) : VO_ERR_INVALID;
 }
 

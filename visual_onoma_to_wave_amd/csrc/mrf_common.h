@@ -259,12 +259,3 @@ int vo_pair_rw_try(const vo::MrfPairCall& c, int cfg, int frag, int* handled);  
 int vo_rb3_pb_try(const vo::MrfBlockCall& c, int* handled);                      // resblock_pb3.hip
 int vo_rb3_rr_try(const vo::MrfBlockCall& c, int cfg, int* handled);             // resblock_rr.hip
 int vo_rbk_pb_try(const vo::MrfBlockCall& c, int* handled);                      // resblock_pbk.hip (vo_resblockk)
-#ifdef VO_ABLATIONS  // the A/B library's kernels (resblock_rr.hip and tools/ab/csrc)
-int vo_pair_rr_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rr.hip
-int vo_pair2_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resblock2.hip
-int vo_pair3_try(const vo::MrfPairCall& c, int cfg, int* handled);      // resblock4.hip
-int vo_pair_pc_try(const vo::MrfPairCall& c, int* handled);             // resblock_pc.hip
-int vo_pair_rs_try(const vo::MrfPairCall& c, int cfg, int* handled);    // resblock_rs.hip
-int vo_pair_wave_try(const vo::MrfPairCall& c, int cfg, int* handled);  // resblock5.hip
-int vo_rb3_wave_try(const vo::MrfBlockCall& c, int cfg, int* handled);  // resblock5.hip
-#endif

@@ -36,11 +36,6 @@ struct PairArgs {
 };
 
 // WC x WT waves: wave (wc, wt) owns channels [wc*C/WC, (wc+1)*C/WC) of rows [wt*16*NJ, ..+16*NJ)
-// ABL (timing ablations only, garbage results; dispatched only with -DVO_ABLATIONS): 1 = no
-// weight-group loads, 2 = no window /
-// residual loads, 3 = neither; bit 4 = no weight LDS stores
-// PRIO (A/B only; both within run-to-run noise on the C = 128 pair): 1 = s_setprio(1) around
-// each MFMA cluster; 2 = static: the younger half of the waves runs at priority 1 (guide T5)
 // SB: pin the software pipeline with sched_barrier: the fragment reads of step st + 1 are
 // issued before, and kept above, the MFMAs of step st (hipcc otherwise sinks every
 // ds_read down to its first use and waits lgkmcnt right before each MFMA pair, exposing
@@ -53,7 +48,7 @@ struct PairArgs {
 // zeroing, no bias adds), leaky ReLU in packed fp32, the T1 mask only in boundary tiles.
 // RAG: ragged batch -- the workgroup walks the compacted tile list of MrfWalk, and utterance b's R_b rows stand where
 // T does in the dense form (window / residual clamps, the T1 mask, stored rows); T stays the row stride
-template <int C, int WC, int WT, int NJ, bool RES, int TG, int ABL = 0, int PRIO = 0, bool SB = false, bool GL = false,
+template <int C, int WC, int WT, int NJ, bool RES, int TG, bool SB = false, bool GL = false,
           bool IP = false, bool HP = false, bool LATE = HP, bool VD = true, bool RAG = false>
 __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {  // >= 2 waves per SIMD
   constexpr int NW = WC * WT;
@@ -144,7 +139,6 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
     const int k0 = (gi - ph * NG) * TG;
     const bf16_t* W = ph ? a.w2 : a.w1;
     if constexpr (GL) {
-      if constexpr ((ABL & 1) != 0) return;
       typedef __attribute__((address_space(3))) void lds_void;
       typedef const __attribute__((address_space(1))) void g_void;
       // HP: group gi is half (gi & 1) of tap gi / 2 -- planes [half * NC/2, (half + 1) * NC/2)
@@ -163,14 +157,11 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
 #pragma unroll
     for (int s = 0; s < GV; ++s) {
       const int k = k0 + (wg_t[s] < TG ? wg_t[s] : 0);
-      if constexpr (ABL & 1)
-        wr[s] = u32x4{(unsigned)k, 0u, 0u, 0u};
-      else
-        wr[s] = *reinterpret_cast<const u32x4*>(W + (int64_t)min(k, K - 1) * C * C + wg_g[s]);  // taps >= K unused
+      wr[s] = *reinterpret_cast<const u32x4*>(W + (int64_t)min(k, K - 1) * C * C + wg_g[s]);  // taps >= K unused
     }
   };
   auto store_group = [&](int buf) {
-    if constexpr ((ABL & 4) != 0 || GL) return;
+    if constexpr (GL) return;
 #pragma unroll
     for (int s = 0; s < GV; ++s)
       if (GV * NT == TG * TAPV || wg_t[s] < TG) *reinterpret_cast<u32x4*>(wls + buf * TG * TAPE + wg_l[s]) = wr[s];
@@ -226,10 +217,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
     for (int s = 0; s < MAXW; ++s) {
       const int t = R0 + xr0 + s * RSTEP;
       xw_ok[s] = t >= 0 && t < Tl && xr0 + s * RSTEP < win_rows;
-      if constexpr ((ABL & 2) != 0)
-        xw[s] = u32x4{(unsigned)t, 0u, 0u, 0u};
-      else
-        xw[s] = *reinterpret_cast<const u32x4*>(base + (int64_t)min(max(t, 0), Tl - 1) * C + xg0);
+      xw[s] = *reinterpret_cast<const u32x4*>(base + (int64_t)min(max(t, 0), Tl - 1) * C + xg0);
     }
   };
   auto store_win = [&]() {
@@ -247,8 +235,6 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
   for (int i = 0; i < NI; ++i) a_off[i] = rb_off(cw0 + NI * 4 * (lr >> 2) + 4 * i + (lr & 3), lq, SHW);
   const int brow0 = wt * 16 * NJ + lr;
 
-  if constexpr (PRIO == 2)
-    if (__builtin_amdgcn_readfirstlane(tid) >= NT / 2) __builtin_amdgcn_s_setprio(1);
   load_win(tile);
   store_win();
   if constexpr (GL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -299,12 +285,8 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
         const int64_t off = ((int64_t)b * T + pos) * C + n0;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-          if constexpr ((ABL & 2) != 0) {
-            xres[j][h] = ares[j][h] = u32x4{(unsigned)pos, 0u, 0u, 0u};
-          } else {
-            xres[j][h] = *reinterpret_cast<const u32x4*>(a.x + off + 8 * h);
-            if constexpr (!IP) ares[j][h] = *reinterpret_cast<const u32x4*>(accp + off + 8 * h);
-          }
+          xres[j][h] = *reinterpret_cast<const u32x4*>(a.x + off + 8 * h);
+          if constexpr (!IP) ares[j][h] = *reinterpret_cast<const u32x4*>(accp + off + 8 * h);
         }
       }
     };
@@ -500,12 +482,8 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
         const int64_t off = ((int64_t)b * T + pos) * C + n0;
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-          if constexpr ((ABL & 2) != 0) {
-            xres[j][h] = ares[j][h] = u32x4{(unsigned)pos, 0u, 0u, 0u};
-          } else {
-            xres[j][h] = *reinterpret_cast<const u32x4*>(a.x + off + 8 * h);
-            ares[j][h] = *reinterpret_cast<const u32x4*>(accp + off + 8 * h);
-          }
+          xres[j][h] = *reinterpret_cast<const u32x4*>(a.x + off + 8 * h);
+          ares[j][h] = *reinterpret_cast<const u32x4*>(accp + off + 8 * h);
         }
       }
     } else if constexpr (IP) {  // IP: the MRF accumulator rows are read here (registers are short)
@@ -580,7 +558,7 @@ __global__ void __launch_bounds__(WC * WT * 64, 2) mrf_pair_kernel(PairArgs a) {
   }
 }
 
-template <int C, int WC, int WT, int NJ, bool RES, int TG, int ABL = 0, int PRIO = 0, bool SB = false, bool GL = false,
+template <int C, int WC, int WT, int NJ, bool RES, int TG, bool SB = false, bool GL = false,
           bool IP = false, bool HP = false, bool LATE = HP, bool VD = true, bool RAG = false>
 static int pair_launch(PairArgs a, int B, MrfTo st) {
   constexpr int NW = WC * WT;
@@ -598,7 +576,7 @@ static int pair_launch(PairArgs a, int B, MrfTo st) {
     vo_set_error("resblock_pair: LDS %zu B exceeds 160 KiB", lds);
     return VO_ERR_INVALID;
   }
-  return mrf_launch(mrf_pair_kernel<C, WC, WT, NJ, RES, TG, ABL, PRIO, SB, GL, IP, HP, LATE, VD, RAG>, a, a.ntiles,
+  return mrf_launch(mrf_pair_kernel<C, WC, WT, NJ, RES, TG, SB, GL, IP, HP, LATE, VD, RAG>, a, a.ntiles,
                     NW * 64, lds, true, st);
 }
 
@@ -637,9 +615,7 @@ static int resblock_pair_entry(const void* x, const void* w1, const float* b1, c
   // Shipped dispatch (measured on MI355X at the B = 32 MRF shapes, tools/ab_pair.py, tools/ab_sb.py, tools/mrf_bench.py):
   //   C = 64 / 128, K = 7 / 11: wave-owned output planes (resblock_rw.hip);
   //   everything else: the LDS-tile kernels of this file, tiled per C and K at the end of this function.
-  // pair_cfg 93 (and 99; 111 at C = 64) sends K = 7 / 11 to those LDS-tile kernels as well, in either library.  Every
-  // other pair_cfg value selects a measured-and-dropped variant and means something in the A/B library only
-  // (make abl, VO_ABLATIONS); the shipped library does not contain those kernels and runs its defaults.
+  // pair_cfg 93 (111 at C = 64) sends K = 7 / 11 to those LDS-tile kernels as well: the tests' reference kernels.
   const int cfg = vo_tune_get("pair_cfg");
   int handled = 0;
   if (lens) {
@@ -651,107 +627,16 @@ static int resblock_pair_entry(const void* x, const void* w1, const float* b1, c
     const int rc = vo_pair_rw_try(c, cfg, 0, &handled);
     if (handled) return rc;
     VO_CHECK_ARG(C == 32, "resblock_pair: no ragged (lens) kernel for C=%d K=%d dil=%d", C, K, dil);
-    return pair_launch<32, 1, 8, 4, true, 1, 0, 0, false, false, true, false, true, false, true>(a, B, st);
+    return pair_launch<32, 1, 8, 4, true, 1, false, false, true, false, true, false, true>(a, B, st);
   }
-#ifdef VO_ABLATIONS
-  // round 4: register-resident frames (resblock_rr.hip): C = 32 K = 7 / 11 pair_cfg 90-93, 99; C = 64 94-98 and
-  // 100 = the 144-row k = 7 frames that shipped before the plane kernel
-  if (cfg >= 90 && cfg <= 100) {
-    const int rc = vo_pair_rr_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-#endif
   {
     const int rc = vo_pair_rw_try(c, cfg, 0, &handled);
     if (handled) return rc;
   }
-#ifdef VO_ABLATIONS  // measured-and-dropped variants (A/B builds only: make abl)
-  // round-4 C = 128 candidates (k = 7 / 11): pair_cfg 71 = producer roles (resblock_pc.hip),
-  // 72 = register-streamed weights, one wave per SIMD (resblock_rs.hip; rs_cfg 2: two per SIMD)
-  if (C == 128 && cfg == 71) {
-    const int rc = vo_pair_pc_try(c, &handled);
-    if (handled) return rc;
-  }
-  if (C == 128 && cfg == 72) {
-    const int rc = vo_pair_rs_try(c, vo_tune_get("rs_cfg"), &handled);
-    if (handled) return rc;
-  }
-  if (cfg == 50) {  // round 3: C = 32 with wave-private frames (resblock5.hip)
-    const int rc = vo_pair_wave_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-  if (cfg == 40 || cfg == 41) {  // round 3: two 4-wave workgroups per CU, LDS-DMA windows (resblock4.hip)
-    const int rc = vo_pair3_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-  if (cfg == 30 || cfg == 31) {  // the version-2 kernel at C = 128 (resblock2.hip): -1 % at k = 7, +5 % at k = 11
-    const int rc = vo_pair2_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-  // VALU diet (VD): C = 128 -2..4 % (0.682 -> 0.668 ms at k = 11, 0.505 -> 0.485 at k = 7); C = 32
-  // +2..3 % (0.201 -> 0.205, 0.234 -> 0.240): C = 32 ships without it (tools/mrf_bench.py --tune
-  // pair_cfg=8,0, round 3).  cfg 8 swaps the C = 32 / 128 epilogues, for A/B
-  if (cfg == 8) {
-    if (C == 32) return pair_launch<32, 1, 8, 4, true, 1, 0, 0, false, false, true, false, true, true>(a, B, st);
-    if (C == 128 && K <= 3) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, true, true, false>(a, B, st);
-    if (C == 128) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, false, true, false>(a, B, st);
-  }
-  if (C == 32) {
-    if (cfg == 3) return pair_launch<32, 1, 4, 8, true, 1>(a, B, st);
-    if (cfg == 4) return pair_launch<32, 1, 8, 8, true, 1, 0, 0, false, false, true, false, true>(a, B, st);
-    if (cfg == 6) return pair_launch<32, 1, 8, 6, true, 1, 0, 0, false, false, true, false, true>(a, B, st);
-    if (cfg == 1 || cfg == 2 || cfg == 9) {  // the previous tilings (9: k <= 7 -> 256 rows, else 512)
-      const bool small = cfg == 9 ? K <= 7 : cfg == 1;
-      return small ? pair_launch<32, 1, 8, 2, true, 1>(a, B, st) : pair_launch<32, 1, 8, 4, true, 1>(a, B, st);
-    }
-  }
-  if (C == 128) {
-    // 2 x 4 waves of 64 channels (2 waves/SIMD), weights by LDS-DMA.  pair_cfg 1 = the register-staged
-    // 128-row kernel, 13 = its no-global-load timing ablation.
-    if (cfg == 1) return pair_launch<128, 2, 4, 2, false, 1>(a, B, st);
-    if (cfg == 13) return pair_launch<128, 2, 4, 2, false, 1, 3>(a, B, st);
-    if (cfg == 16) return pair_launch<128, 2, 4, 4, false, 1, 2, 0, false, true, true, true>(a, B, st);
-    if (cfg == 17) return pair_launch<128, 2, 4, 4, false, 1, 2, 0, false, true, true, false, true>(a, B, st);
-    if (cfg == 25) return pair_launch<128, 2, 4, 4, false, 1, 1, 0, false, true, true, false, true>(a, B, st);
-    if (cfg == 2) return pair_launch<128, 2, 4, 2, false, 1, 0, 0, false, true>(a, B, st);
-    if (cfg == 3) return pair_launch<128, 2, 4, 3, false, 1, 0, 0, false, true, true>(a, B, st);
-    // two 4-wave workgroups per CU (79 KB LDS each: 128-row in-place tiles, half-tap weight
-    // buffers), 64 x 64-row wave tiles: one workgroup's epilogue overlaps the other's MFMAs
-    if (cfg == 4) return pair_launch<128, 2, 2, 4, false, 1, 0, 0, false, true, true, true>(a, B, st);
-    // one 8-wave workgroup per CU with half-tap buffers: 256- / 384-row in-place tiles halve the
-    // weight stream per MFMA of the 192-row kernel (384 rows spill)
-    if (cfg == 6) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, true>(a, B, st);
-    if (cfg == 7) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, false, true>(a, B, st);
-    if (cfg == 60) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, true, true, true, false, true>(a, B, st);
-    if (cfg == 9) {  // the round-2 defaults
-      if (K <= 3) return pair_launch<128, 2, 4, 2, false, 1, 0, 0, false, true>(a, B, st);
-      return pair_launch<128, 2, 4, 3, false, 1, 0, 0, false, true, true>(a, B, st);
-    }
-    if (cfg == 61 && K > 3) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, false, true>(a, B, st);
-  }
-  if (C == 64) {
-    // pair_cfg 3 / 4 / 5: 512-row IP + LDS-DMA / 384-row IP + LDS-DMA / 512-row IP
-    // pair_cfg 1 = LDS-DMA weights + pinned fragment pipeline: 7 % faster alone (tools/ab_sb.py)
-    // but 15 % slower inside the bench step with the MRF accumulator (tools/bench_ab.sh)
-    if (cfg == 3) return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, true, true, false, true>(a, B, st);
-    if (cfg == 4) return pair_launch<64, 1, 8, 3, false, 2, 0, 0, false, true, true, false, true>(a, B, st);
-    if (cfg == 5) return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);
-    if (cfg == 1) return pair_launch<64, 1, 8, 3, false, 2, 0, 0, true, true>(a, B, st);
-    if (cfg == 9) return pair_launch<64, 1, 8, 3, false, 2>(a, B, st);  // the round-2 default
-    if (cfg == 2 && K <= 3) return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);
-  }
-  // C = 64, K = 7 / 11 past the plane kernel (pair_cfg 93 / 99 / 111): the version-2 kernel (tools/ab/csrc/resblock2.hip:
-  // compile-time K, next window fetched during P2): 0.453 -> 0.408 ms at k = 11, 0.359 -> 0.326 at k = 7 against the
-  // generic kernel below, bit-identical (tools/ab_pair2.py).  It shipped until the plane kernel took its shapes.
-  if (C == 64) {
-    const int rc = vo_pair2_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-#endif
   if (C == 32) {
     // 512-row in-place tiles, window / residual fetched after P2: k = 11 -13 %, k = 7 -3 %
     // (k = 3 is HBM-bound at ~5 TB/s either way; tools/ab_sb.py pair32 9 5); without the VALU diet
-    return pair_launch<32, 1, 8, 4, true, 1, 0, 0, false, false, true, false, true, false>(a, B, st);
+    return pair_launch<32, 1, 8, 4, true, 1, false, false, true, false, true, false>(a, B, st);
   }
   if (C == 128) {
     // 256-row in-place tiles, window / residual fetched after P2 (no window registers live in the
@@ -761,15 +646,15 @@ static int resblock_pair_entry(const void* x, const void* w1, const float* b1, c
     // section 3): one wave per SIMD with 128 x 64-row wave tiles (20-45 % slower), three waves per SIMD
     // (15 % slower), the next window staged through registers during P2 (+20 %), 320 / 384-row tiles
     // (spill), an L2 / MALL prefetch of the epilogue's bytes by LDS-DMA pieces (+7..18 %), the weights
-    // out of LDS (A fragments from global one tap ahead: +20 %).  Timing ablations (VO_ABLATIONS
-    // builds): no window / residual loads 0.70 -> 0.58 ms at k = 11; no weight DMA 0.70 -> 0.63.
-    if (K <= 3) return pair_launch<128, 2, 4, 4, false, 1, 0, 0, false, true, true, true>(a, B, st);
-    return pair_launch<128, 2, 4, 4, false, 1, 0, 0, true, true, true, false, true>(a, B, st);
+    // out of LDS (A fragments from global one tap ahead: +20 %).  Timing ablations (removed
+    // with their kernels): no window / residual loads 0.70 -> 0.58 ms at k = 11; no weight DMA 0.70 -> 0.63.
+    if (K <= 3) return pair_launch<128, 2, 4, 4, false, 1, false, true, true, true>(a, B, st);
+    return pair_launch<128, 2, 4, 4, false, 1, true, true, true, false, true>(a, B, st);
   }
-  // C = 64: k = 3 -> both convs resident in LDS; other k (k = 7 / 11 only under pair_cfg 93 / 99 / 111) ->
+  // C = 64: k = 3 -> both convs resident in LDS; other k (k = 7 / 11 only under pair_cfg 93 / 111) ->
   // 512-row in-place tiles, window / residual fetched after P2 (-5 % against the 384-row kernel)
   if (K <= 3) return pair_launch<64, 1, 8, 2, true, 1>(a, B, st);
-  return pair_launch<64, 1, 8, 4, false, 2, 0, 0, false, false, true, false, true>(a, B, st);
+  return pair_launch<64, 1, 8, 4, false, 2, false, false, true, false, true>(a, B, st);
 }
 
 extern "C" int vo_resblock_pair(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,

@@ -593,21 +593,13 @@ static int resblock3_entry(const void* x, const void* const* w1, const float* co
   //   C = 64 / 128: wave-owned output planes (resblock_pb3.hip), for every shape accepted above;
   //   C = 32, dilations (1, 3, 5): register-resident frames (resblock_rr.hip);
   //   C = 32 otherwise, and under any rb3_cfg != 0: the LDS-frame kernel of this file.
-  // Every other use of rb3_cfg selects a measured-and-dropped variant and means something in the A/B library only
-  // (make abl, VO_ABLATIONS): there any rb3_cfg != 0 also sends C = 64 / 128 to the LDS-frame kernels (90 by
-  // convention), 77-89 pick the frame shapes of resblock_rr.hip, 1 / 4-7 / 20 / 40-45 the tilings below (1 = 128-row
-  // frames, C = 32: 512-row; 4 = a 3-deep LDS-DMA ring of half / whole taps, within 2 % of double buffering).
+  // (rb3_cfg has no other meaning: the tests pass 80 to reach the LDS-frame kernel as their reference.)
   // The LDS-frame kernels against three vo_resblock_pair launches: C = 128 0.84 vs 1.02 ms, C = 64 0.61 vs 0.67,
   // C = 32 0.39 vs 0.52.
   const int cfg = vo_tune_get("rb3_cfg");
   // a ragged call takes the shipped dispatch: the kernels rb3_cfg selects have no ragged form
   VO_CHECK_ARG(!lens || cfg == 0, "resblock3: rb3_cfg=%d selects a kernel without a ragged (lens) form", cfg);
-#ifdef VO_ABLATIONS
-  const bool plane = cfg == 0;
-#else
-  const bool plane = true;  // the shipped library has no other C = 64 / 128 kernel
-#endif
-  if (plane) {
+  {  // C = 64 / 128 under every rb3_cfg: the library has no other kernel for them
     const int rc = vo_rb3_pb_try(c, &handled);
     if (handled) return rc;
   }
@@ -617,45 +609,6 @@ static int resblock3_entry(const void* x, const void* const* w1, const float* co
   }
   VO_CHECK_ARG(!lens, "resblock3: no ragged (lens) kernel for C=%d with dilations (%d, %d, %d)", C, dil[0], dil[1],
                dil[2]);
-#ifdef VO_ABLATIONS  // measured-and-dropped variants (A/B builds only: make abl)
-  if (C == 32 && (cfg == 30 || cfg == 31)) {  // round 3: wave-private frames (resblock5.hip)
-    const int rc = vo_rb3_wave_try(c, cfg, &handled);
-    if (handled) return rc;
-  }
-  if (cfg == 20) {  // the round-2 kernels (epilogues without the VALU diet), for A/B
-    if (C == 32) return rb3_launch<32, 1, 8, 2, true, 1, 2, false>(a, B, st);
-    if (C == 64) return rb3_launch<64, 1, 8, 4, false, 1, 2, false>(a, B, st);
-    return rb3_launch<128, 2, 4, 4, false, 1, 2, false>(a, B, st);
-  }
-  if (C == 32 && cfg == 1) return rb3_launch<32, 1, 8, 4, true>(a, B, st);
-  if (C == 64) {
-    if (cfg == 1) return rb3_launch<64, 1, 8, 2, false>(a, B, st);
-    if (cfg == 4) return rb3_launch<64, 1, 8, 4, false, 1, 4>(a, B, st);
-    if (cfg == 5) return rb3_launch<64, 1, 4, 4, false>(a, B, st);
-    if (cfg == 7) return rb3_launch<64, 1, 4, 4, false, 1, 4>(a, B, st);
-    // cfg 6 / 7: two 4-wave workgroups of 256-row frames per CU with a 3- / 4-deep weight ring
-    // (round 2, bare LDS barriers): 0.53 -> 0.50 ms alone with the MRF accumulator
-    // (tools/ab_pair2.py), the same 12.40 / 12.46 ms bench step (s2 within noise) -- not default
-    if (cfg == 6) return rb3_launch<64, 1, 4, 4, false, 1, 3>(a, B, st);
-    if (cfg == 40) return rb3_launch<64, 1, 8, 4, false>(a, B, st);  // one tap per group (round 2 / 3)
-    if (cfg == 41) return rb3_launch<64, 1, 8, 3, false, 1, 2, true, 3>(a, B, st);
-    if (cfg == 43) return rb3_launch<64, 1, 8, 3, false, 1, 2, true, 3, true>(a, B, st);
-    if (cfg == 44) return rb3_launch<64, 1, 8, 4, false, 1, 2, true, 1, true>(a, B, st);
-    if (cfg == 45) return rb3_launch<64, 1, 8, 4, false, 1, 2, true, 3>(a, B, st);
-  }
-  if (C == 128) {
-    if (cfg == 1) return rb3_launch<128, 2, 4, 2, false>(a, B, st);
-    if (cfg == 4) return rb3_launch<128, 2, 4, 4, false, 2, 4>(a, B, st);
-    if (cfg == 42) return rb3_launch<128, 2, 4, 4, false>(a, B, st);  // without the PIPE steps
-  }
-  // C = 64: a whole conv (3 taps, 24 KB) per streamed group: 6 barriers per tile instead of 24, 0.476
-  // -> 0.448 ms (tools/mrf_bench.py --stages 2 --tune rb3_cfg=0,40, round 3, bit-identical); with the
-  // software-pipelined steps (PIPE) 0.443 -> 0.437 ms
-  if (C == 64) return rb3_launch<64, 1, 8, 4, false, 1, 2, true, 3, true>(a, B, st);
-  // C = 128: software-pipelined steps (PIPE: the next (tap, plane) step's fragments read during the
-  // current step's MFMAs): 0.720 -> 0.686 ms, bit-identical (tools/mrf_bench.py --tune rb3_cfg=0,42)
-  if (C == 128) return rb3_launch<128, 2, 4, 4, false, 1, 2, true, 1, true>(a, B, st);
-#endif
   if (C != 32) {  // (the plane kernel's guard is this entry's own: not reached)
     vo_set_error("resblock3: no kernel for C=%d", C);
     return VO_ERR_INVALID;

@@ -29,10 +29,6 @@
 
 #include "mrf_plane.h"
 
-#ifndef VO_PB3_PK
-#define VO_PB3_PK 0  // epilogue leaky ReLU with one packed multiply per value pair (A/B)
-#endif
-
 namespace vo {
 
 struct Pb3Args {
@@ -54,13 +50,7 @@ constexpr int pb_np(int C) { return C / 32; }
 // C = 128: 14 (224-row frames, 200 output rows: 89.3 % of the MFMA work kept); C = 64: 16 (512-row frames, 488
 // output rows, 95.3 %).  One more block (C = 128: 16) exceeds 512 registers, and the spill reloads' vmcnt(0)
 // waits drain every prefetch in flight (measured 1.5x slower in an earlier layout)
-#ifndef VO_PB3_NJ128
-#define VO_PB3_NJ128 14
-#endif
-#ifndef VO_PB3_NJ64
-#define VO_PB3_NJ64 16
-#endif
-constexpr int pb_nj(int C) { return C == 128 ? VO_PB3_NJ128 : VO_PB3_NJ64; }
+constexpr int pb_nj(int C) { return C == 128 ? 14 : 16; }
 constexpr int pb_f(int C) { return 16 * pb_nj(C) * (4 / pb_np(C)); }  // frame rows per tile
 constexpr int pb_rp(int C) { return pb_f(C) + 2 * PB_HP + 1; }    // LDS rows per plane (odd)
 constexpr size_t pb_lds(int C) { return (size_t)2 * pb_np(C) * pb_rp(C) * 32 * sizeof(bf16_t) + 6 * C * sizeof(float); }
@@ -241,11 +231,8 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
     // P1 epilogue: T1 = lrelu(acc) (bias in acc), frame rows outside [0, T) = 0 (c2's zero padding)
     auto p1_post = [&](int j, int p) __attribute__((always_inline)) {
       const int t = p >> 1, e = 2 * (p & 1);
-#if VO_PB3_PK
-      pv[p] = lrelu_pk(acc[t][j][e], acc[t][j][e + 1], slope);
-#else
+      // scalar multiplies, as resblock_rw.hip's epilogues: one packed multiply per value pair was tried and not kept
       pv[p] = pk_bf16(lrelu_max(acc[t][j][e], slope), lrelu_max(acc[t][j][e + 1], slope));
-#endif
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
         *reinterpret_cast<u32x4*>(t1 + pw * PL + plane_off(f + PB_HP, lg)) = u32x4{pv[0], pv[1], pv[2], pv[3]};
@@ -259,11 +246,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pb3_kernel(Pb3Args a) {
       const int e = 2 * p;
       const float a0 = acc[e >> 2][j][e & 3], a1 = acc[e >> 2][j][(e & 3) + 1];
       pv[p] = pk_bf16(a0, a1);
-#if VO_PB3_PK
-      lv[p] = lrelu_pk(a0, a1, slope);
-#else
       lv[p] = pk_bf16(lrelu_max(a0, slope), lrelu_max(a1, slope));
-#endif
       if (p == 3) {
         const int f = row0 + 16 * j + lr;
         xres[j] = u32x4{pv[0], pv[1], pv[2], pv[3]};

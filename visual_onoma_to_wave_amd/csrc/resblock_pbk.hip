@@ -31,10 +31,6 @@
 
 #include "mrf_plane.h"
 
-#ifndef VO_PBK_L
-#define VO_PBK_L 4  // taps of a conv that run interleaved with the epilogues (phase B)
-#endif
-
 namespace vo {
 
 struct PbkArgs {
@@ -62,7 +58,7 @@ __global__ void __launch_bounds__(256, 1) mrf_pbk_kernel(PbkArgs a) {
   constexpr int C = PBK_C, F = PBK_F, NJ = PBK_NJ, H2 = pbk_h2(K), HP = pbk_hp(K), HALO = pbk_halo(K);
   constexpr int RP = pbk_rp(K), PL = RP * 32, BT = pbk_bt(K);
   constexpr int RPS = 64, NWV = F / RPS;       // window staging: rows per slot (256 threads x 16 B), slots
-  constexpr int L = VO_PBK_L, KA = K - L;      // phase-B taps, phase-A taps
+  constexpr int L = 4, KA = K - L;             // phase-B taps (interleaved with the epilogues), phase-A taps
   constexpr int R = L + 2;                     // A-fragment ring: tap u of the tile's 6 K in slot u % R
   constexpr int NU = 6 * K;                    // taps per tile
   constexpr int NB = 10, DB = 8;               // B-fragment ring / prefetch distance (steps)

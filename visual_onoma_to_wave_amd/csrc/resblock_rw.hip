@@ -66,29 +66,16 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
   constexpr int RD = 12 * NP;                 // MRF-accumulator prefetch distance (steps)
   constexpr int NST = NJ * NP;                // (row tile, plane) steps per tap
   constexpr int SP2 = (NST - 2 * NAP) / SPT;  // P2 staging: steps between a tap's window slots
-#ifndef VO_PRW_LG
-#define VO_PRW_LG 1
-#endif
-  constexpr int LG = VO_PRW_LG;               // last tap: row tiles per block (see conv)
-#ifndef VO_PRW_XT
-#define VO_PRW_XT 0
-#endif
-  constexpr int XT = K > 2 ? VO_PRW_XT : 0;   // P2 tap whose first plane also adds the residual (see p2_extra)
-#ifndef VO_PRW_AP2
-#define VO_PRW_AP2 1
-#endif
+  constexpr int LG = 1;                       // last tap: row tiles per block (see conv)
   // ACC == 2: the MRF accumulator rows (HBM misses, unlike the residual rows the window staging just
-  // brought into L2) requested over P2 taps 0 .. ANT - 1 and added at tap XA (AP2).  Requested with the
+  // brought into L2) requested over P2 taps 0 .. ANT - 1 and added at tap XA.  Requested with the
   // residual in P1's last two taps, the in-order vmcnt drained them at the next tap's weight wait:
   // those two taps ran 3,996 + 6,240 cycles for 2 x 1,168 (stamps, C = 64 k = 11); in P2 over four taps
   // a tile takes 38.4k cycles against 42.8k (C = 64 k = 11), 61.6k against 64.5k (C = 128 k = 11)
-  constexpr bool AP2 = VO_PRW_AP2 != 0 && ACC == 2;
-#ifndef VO_PRW_ANT
-#define VO_PRW_ANT 4
-#endif
-  constexpr int ANT = VO_PRW_ANT, ARPT = NJ / ANT;  // taps carrying the requests, row tiles per tap
-  constexpr int XA = AP2 ? (ANT + 1 < K - 1 ? ANT + 1 : K - 1) : XT;
-  // (XT = 1 moved the identity MFMAs' cost to tap 1 unchanged: it is their issue, not a dependency stall)
+  constexpr int ANT = 4, ARPT = NJ / ANT;     // taps carrying the requests, row tiles per tap
+  constexpr int XA = ANT + 1 < K - 1 ? ANT + 1 : K - 1;
+  // (the residual is added in P2's tap 0, see p2_extra: in tap 1 the identity MFMAs cost the same -- it is their
+  // issue, not a dependency stall)
   constexpr int NB = 10, DB = 8;              // B-fragment ring / prefetch distance (steps); 12 / 14 measured no faster
   // ACC: 0 = no MRF accumulator; 1 = y = acc_out * out_scale + acc_in (epilogue add); 2 = acc_in / out_scale
   // enters the accumulators through an identity MFMA (1 / out_scale exact in bf16, e.g. 3)
@@ -270,20 +257,14 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     // requested after each tap's A pieces (steps 16, 22, .., 58 of taps K-2 and K-1): vmcnt retires in
     // issue order, so a residual load issued before an A piece would hold up the MFMAs that wait for it
     // (spread over the last K-2 taps, a few row tiles each, they measured slower: 2.5 % per tile)
-#ifndef VO_PRW_NRT
-#define VO_PRW_NRT 2
-#endif
-    constexpr int NRT = VO_PRW_NRT, RPT = NJ / NRT, RT0 = K - NRT, RSP = (NST - 2 * NAP) / RPT;
+    constexpr int NRT = 2, RPT = NJ / NRT, RT0 = K - NRT, RSP = (NST - 2 * NAP) / RPT;
     auto p1_hook = [&](int k, int jj) {
       if (k < RT0 || jj < 2 * NAP || (jj - 2 * NAP) % RSP != 0) return;  // after the tap's A pieces
       const int i = (jj - 2 * NAP) / RSP;
       const int j = (k - RT0) * RPT + i;
       if (i >= RPT || j >= NJ) return;
-      {
-        const int off = ((t0 + row0 + 16 * j + lr) * C + cofs) * 2;  // rows past T: read 0
-        xres[j] = __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0);
-        if constexpr (ACC == 2 && !AP2) ares[j] = __builtin_amdgcn_raw_buffer_load_b128(rsa, off, 0, 0);
-      }
+      const int off = ((t0 + row0 + 16 * j + lr) * C + cofs) * 2;  // rows past T: read 0
+      xres[j] = __builtin_amdgcn_raw_buffer_load_b128(rsx, off, 0, 0);
     };
     const f32x4* bias1 = reinterpret_cast<const f32x4*>(sbias + cofs);
     const f32x4 b1z0 = bias1[0], b1z1 = bias1[1];
@@ -320,7 +301,7 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
         const int i = (jj - 2 * NAP - SP2 / 2) / SP2, sl = (k - 2) * SPT + i;
         if (i < SPT && k >= 2 && sl < NWV) store_win1(sl);
       }
-      if constexpr (AP2) {  // ARPT row tiles' accumulator rows per tap in taps 0 .. ANT - 1
+      if constexpr (ACC == 2) {  // ARPT row tiles' accumulator rows per tap in taps 0 .. ANT - 1
         constexpr int ASP = (NST - 2 * NAP) / ARPT;
         if (k < ANT && jj >= 2 * NAP && (jj - 2 * NAP) % ASP == 0 && (jj - 2 * NAP) / ASP < ARPT) {
           const int j = ARPT * k + (jj - 2 * NAP) / ASP;
@@ -339,14 +320,14 @@ __global__ void __launch_bounds__(256, 1) mrf_prw_kernel(PrwArgs a) {
     const f32x4* bias2 = reinterpret_cast<const f32x4*>(sbias + C + cofs);
     const f32x4 b2z0 = bias2[0], b2z1 = bias2[1];
     auto p2_cinit = [&](int, int t) { return t ? b2z1 : b2z0; };
-    // the residual x (and acc_in / out_scale) added by identity MFMAs in c2's tap XT: the lane's x
+    // the residual x (and, in tap XA, acc_in / out_scale) added by identity MFMAs in c2's tap 0: the lane's x
     // vector of row tile j IS the B fragment of input plane w, and A = I maps its 8 channels onto the
     // accumulator rows that hold them (exact: products of 1 and bf16, fp32 accumulation)
     auto p2_extra = [&](int k, int j, int s) {
       if (s != 0) return;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        if (k == XT)
+        if (k == 0)
           acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aid[t], __builtin_bit_cast(bf16x8, xres[j]), acc[t][j], 0, 0, 0);
         if constexpr (ACC == 2)
           if (k == XA)
@@ -391,10 +372,10 @@ static int prw_launch(PrwArgs a, int B, MrfTo st) {
 using namespace vo;
 
 // Entry from vo_resblock_pair (resblock.hip) and, with frag, vo_resblock_pair_frag: *handled = 1 when this kernel
-// covers the shape (C = 64 / 128, K = 7 / 11, (K - 1) * dil <= 64).  pair_cfg 93 / 99 (and 111 at C = 64) leave the
-// shape to the LDS-tile kernels: the generic ones of resblock.hip in the shipped library; in the A/B library the
-// version-2 kernel at C = 64.  Measured at B = 32 against that version-2 kernel (tools/mrf_bench.py, with the MRF
-// accumulator): C = 64 k = 11 355 us vs 426, k = 7 275 vs 286 (mean over d = 1 / 3 / 5).
+// covers the shape (C = 64 / 128, K = 7 / 11, (K - 1) * dil <= 64).  pair_cfg 93 (and 111 at C = 64) leaves the
+// shape to the LDS-tile kernels of resblock.hip.  Measured at B = 32 against the compile-time-K LDS-tile kernel that
+// shipped before (tools/mrf_bench.py, with the MRF accumulator): C = 64 k = 11 355 us vs 426, k = 7 275 vs 286 (mean
+// over d = 1 / 3 / 5).
 int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
   const int B = c.B, C = c.C, K = c.K;
   const MrfTo st = c.st;
@@ -403,7 +384,7 @@ int vo_pair_rw_try(const MrfPairCall& c, int cfg, int frag, int* handled) {
   // 197-242 for k = 7 / 11, tools/mrf_bench.py --stages 3 -- one 32-channel plane per wave leaves 16
   // steps per tap for the same per-tap A pieces, staging and epilogue work; not dispatched)
   if (!((C == 128 || C == 64) && (K == 7 || K == 11) && c.dil >= 1 && c.dil * (K - 1) <= 64)) return VO_OK;
-  if (!frag && (cfg == 93 || cfg == 99)) return VO_OK;
+  if (!frag && cfg == 93) return VO_OK;
   if (!frag && C == 64 && cfg == 111) return VO_OK;
   PrwArgs a;
   mrf_pair_args(a, c);

@@ -22,8 +22,8 @@ extern "C" int vo_version(void) { return VO_ABI_VERSION; }
 
 // experiment knobs (kernel-variant selection for A/B runs); unknown keys read as 0.
 // VO_TUNE="pair_cfg=1,conv_cfg=1" presets them for a whole process (bench A/B).
-static const char* const kKnobs[] = {"pair_cfg", "conv_cfg", "gen_cfg", "wgrad_cfg", "rb3_cfg", "att_cfg", "ups_cfg", "post_cfg", "splitk_cfg",
-                                      "wgrad_mt", "wgrad_kg", "att_xcd", "pc_cfg", "rs_cfg", "lin_cfg", "seg_cfg", "tile_cfg"};
+static const char* const kKnobs[] = {"pair_cfg", "conv_cfg", "wgrad_cfg", "rb3_cfg", "att_cfg", "ups_cfg", "post_cfg", "splitk_cfg",
+                                      "wgrad_mt", "wgrad_kg", "att_xcd", "seg_cfg"};
 static int g_knobs[sizeof(kKnobs) / sizeof(kKnobs[0])] = {};
 
 static bool is_ablation(const char* key, int value);
@@ -45,22 +45,17 @@ static void knobs_from_env() {
   }
 }
 
-// knob values that select timing ablations (kernels that skip loads: garbage results); only
-// a build with -DVO_ABLATIONS accepts them, and vo_tune rejects them in the shipped library
+// knob values that selected timing ablations (kernels that skip loads: garbage results): refused, so that no
+// caller's old setting passes for a measurement
 static bool is_ablation(const char* key, int value) {
-#ifdef VO_ABLATIONS
-  (void)key; (void)value;
-  return false;
-#else
   return (!strcmp(key, "pair_cfg") && (value == 13 || value == 16 || value == 17 || value == 25)) ||
-         (!strcmp(key, "pc_cfg") && value >= 8) || (!strcmp(key, "wgrad_cfg") && value == 11);
-#endif
+         (!strcmp(key, "wgrad_cfg") && value == 11);
 }
 
 extern "C" int vo_tune(const char* key, int value) {
   knobs_from_env();
   if (key && is_ablation(key, value)) {
-    vo_set_error("vo_tune: %s=%d is a timing ablation (wrong results); build with -DVO_ABLATIONS", key, value);
+    vo_set_error("vo_tune: %s=%d is a timing ablation (wrong results): not in this library", key, value);
     return VO_ERR_INVALID;
   }
   for (size_t i = 0; key && i < sizeof(kKnobs) / sizeof(kKnobs[0]); ++i)
