@@ -496,6 +496,22 @@ int vo_stft_mel_ex(const float* wav, int B, int N, const float* window, const fl
 /* fstats (nullable, (B, F, 2)): per frame sum_k |X_k|^2 and sum_k log(|X_k|^2 + 1e-8), the
  * power-spectrum statistics of Preprocessor._get_kurtosis. */
 
+/* vo_stft_mel_ex with one length per signal (INTEGRATION.md "Ragged batches in the mel front end").  lens
+ * (nullable = every row is N): B device int32 sample counts, clamped to n_b in [0, N] by the kernel and never read on
+ * the host.  Row b has F_b = vo_stft_mel_frames(n_b, n_fft, hop, pad) frames; frames f < F_b are, operation for
+ * operation, those vo_stft_mel_ex gives on wav[b, :n_b] alone (reflect padding against n_b; no sample at index
+ * >= n_b is read); frames F_b <= f < F = vo_stft_mel_frames(N, ...) of mel, energy and fstats are 0.0f, so a finished
+ * call leaves no output element unwritten.  frames (nullable): B device int32, frames[b] = F_b.  mel_layout 0:
+ * mel (B, n_mels, F); 1: channels-last (B, F, n_mels), the vocoder's input layout.  Stream-ordered, no allocation,
+ * no host read: a captured graph follows lengths changed in place.  VO_ERR_INVALID (nothing launched) for whatever
+ * vo_stft_mel_ex refuses at the capacity N, and for another mel_layout.  Additive: VO_ABI_VERSION unchanged. */
+int vo_stft_mel_lens(const float* wav, int B, int N, const float* window, const float* fb, int n_fft, int hop,
+                     int n_mels, int pad, float mag_eps, int clip, float log_floor, float* mel, float* energy,
+                     float* fstats, const int32_t* lens, int32_t* frames, int mel_layout, void* stream);
+/* Frames of an n-sample signal: 1 + (n + 2*pad - n_fft) / hop when n > pad and n + 2*pad >= n_fft, else 0 (a signal
+ * too short to reflect-pad, or shorter than one frame, has none).  Host only, like vo_conv1d_plan: no HIP call. */
+int vo_stft_mel_frames(int n, int n_fft, int hop, int pad);
+
 /* Character-level acoustic features (Preprocessor._process energy
  * averaging and _get_kurtosis, scripts/preprocessor/preprocessor.py:339-357,395-403): for
  * utterance b with characters j in [char_off[b], char_off[b+1]) of dur[j] frames (consecutive,

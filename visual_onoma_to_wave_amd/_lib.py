@@ -189,6 +189,9 @@ _SIGNATURES = {
                             c_void_p, c_void_p, c_void_p]),
     "vo_stft_mel_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vo_stft_mel_lens": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                 c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vo_stft_mel_frames": (c_int, [c_int, c_int, c_int, c_int]),
     "vo_conv1d_wgrad_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "vo_conv1d_wgrad": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),

@@ -59,15 +59,38 @@ def librosa_mel(sr, n_fft, n_mels=128, fmin=0.0, fmax=None):
     return w.astype(np.float32)
 
 
+def padded_window(win_length, n_fft):
+    """The periodic Hann window of ``win_length`` samples centred in ``n_fft``: (n_fft - win_length) // 2 zeros on
+    the left, the rest on the right -- what torch.stft / torchaudio Spectrogram do with win_length < n_fft, and the
+    reference's pad_center(get_window("hann", win_length, fftbins=True), filter_length) (scripts/audio/stft.py:41-43)."""
+    if not 0 < win_length <= n_fft:
+        raise ValueError(f"win_length ({win_length}) must lie in [1, n_fft = {n_fft}]")
+    w = torch.zeros(n_fft)
+    left = (n_fft - win_length) // 2
+    w[left:left + win_length] = torch.hann_window(win_length, periodic=True)
+    return w
+
+
+def pad_waves(wavs):
+    """List of 1-D waveforms -> (wav (B, N_max) fp32 host tensor, zero-filled; lens int32 (B,)): the ragged batch
+    ``MelSpectrogram(wav, lengths)`` / ``ops.stft_mel_lens`` take."""
+    arrs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
+    lens = np.array([len(a) for a in arrs], np.int32)
+    out = np.zeros((len(arrs), int(lens.max()) if len(arrs) else 0), np.float32)
+    for i, a in enumerate(arrs):
+        out[i, :len(a)] = a
+    return torch.from_numpy(out), torch.from_numpy(lens)
+
+
 class MelSpectrogram:
-    """Spectrogram(n_fft, win=n_fft, hop, power=1, center=True) -> MelScale -> log, on HIP."""
+    """Spectrogram(n_fft, win_length, hop, power=1, center=True) -> MelScale -> log, on HIP."""
 
     def __init__(self, n_fft=1024, hop_length=256, n_mels=80, sample_rate=22050, f_min=0.0, f_max=8000.0,
-                 fb=None, log_floor=1e-5):
+                 fb=None, log_floor=1e-5, win_length=None):
         self.n_fft, self.hop, self.n_mels, self.log_floor = n_fft, hop_length, n_mels, log_floor
         self.fb = (melscale_fbanks(n_fft // 2 + 1, f_min, f_max, n_mels, sample_rate) if fb is None
                    else torch.as_tensor(fb)).float().contiguous()
-        self.window = torch.hann_window(n_fft, periodic=True)
+        self.window = padded_window(n_fft if win_length is None else win_length, n_fft)
         self._dev = {}
 
     def _on(self, device):
@@ -76,14 +99,24 @@ class MelSpectrogram:
             self._dev[key] = (self.window.to(device), self.fb.to(device).contiguous())
         return self._dev[key]
 
-    def __call__(self, wav):
-        """wav (N,) or (B, N) fp32 on the GPU -> (log-mel (B, n_mels, F), energy (B, F))."""
+    def __call__(self, wav, lengths=None, channels_last=False):
+        """wav (N,) or (B, N) fp32 on the GPU -> (log-mel (B, n_mels, F), energy (B, F)).  With ``lengths`` (B sample
+        counts: int32 / int64 device tensor, never read on the host, or a host sequence) the batch is ragged:
+        -> (log-mel, energy, frames); row b holds the frames[b] frames of wav[b, :lengths[b]] alone, bit for bit,
+        then zeros (``ops.stft_mel_lens``).  ``channels_last``: log-mel as (B, F, n_mels), the vocoder's input."""
         squeeze = wav.dim() == 1
         w = wav.reshape(1, -1) if squeeze else wav
         window, fb = self._on(w.device)
-        logmel, energy = ops.stft_mel(w.float().contiguous(), window, fb, self.n_fft, self.hop, self.n_mels,
-                                      self.log_floor)
-        return (logmel[0], energy[0]) if squeeze else (logmel, energy)
+        if lengths is None and not channels_last:
+            logmel, energy = ops.stft_mel(w.float().contiguous(), window, fb, self.n_fft, self.hop, self.n_mels,
+                                          self.log_floor)
+            return (logmel[0], energy[0]) if squeeze else (logmel, energy)
+        logmel, energy, _, frames = ops.stft_mel_lens(w.float().contiguous(), window, fb, lengths, self.n_fft,
+                                                      self.hop, clip=True, log_floor=self.log_floor,
+                                                      channels_last=channels_last)
+        if lengths is None:
+            return (logmel[0], energy[0]) if squeeze else (logmel, energy)
+        return (logmel[0], energy[0], frames[0]) if squeeze else (logmel, energy, frames)
 
 
 def get_spec(wav, preprocess_config=None):
@@ -91,7 +124,8 @@ def get_spec(wav, preprocess_config=None):
     a = (preprocess_config or {}).get("audio", {})
     st, mel = a.get("stft", {}), a.get("mel", {})
     m = MelSpectrogram(st.get("filter_length", 1024), st.get("hop_length", 256), mel.get("n_mel_channels", 80),
-                       a.get("sampling_rate", 22050), mel.get("mel_fmin", 0), mel.get("mel_fmax", 8000))
+                       a.get("sampling_rate", 22050), mel.get("mel_fmin", 0), mel.get("mel_fmax", 8000),
+                       win_length=st.get("win_length"))
     return m(wav)
 
 
@@ -101,14 +135,17 @@ class TacotronSTFT(torch.nn.Module):
     def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin,
                  mel_fmax):
         super().__init__()
-        if win_length != filter_length:
-            raise NotImplementedError("the HIP front-end uses win_length == filter_length (the ICASSP config)")
         self.n_mel_channels, self.sampling_rate = n_mel_channels, sampling_rate
         basis = torch.from_numpy(librosa_mel(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax))
         self.register_buffer("mel_basis", basis)
-        self._mel = MelSpectrogram(filter_length, hop_length, n_mel_channels, fb=basis.t().contiguous())
+        self._mel = MelSpectrogram(filter_length, hop_length, n_mel_channels, fb=basis.t().contiguous(),
+                                   win_length=win_length)
 
-    def mel_spectrogram(self, y):
+    def mel_spectrogram(self, y, lengths=None):
+        """(mel, energy) of y (B, N) in [-1, 1]; with ``lengths`` (see MelSpectrogram) -> (mel, energy, frames) of
+        the ragged batch, without the host-side range check (it would read the device)."""
+        if lengths is not None:
+            return self._mel(y, lengths)
         if float(y.min()) < -1 or float(y.max()) > 1:
             raise AssertionError("waveform must lie in [-1, 1]")
         return self._mel(y)

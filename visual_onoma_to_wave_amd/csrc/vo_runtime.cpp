@@ -95,6 +95,7 @@ static const char* const kSymbols[] = {
     "vo_resblockk", "vo_resblockk_lens", "vo_resblockk_tile_rows", "vo_resblock_pair_tile_rows", "vo_resblock3_tile_rows",
     "vo_vfe_stencil_lds_bytes", "vo_vfe_stencil_ex", "vo_vfe_conv_workspace_size_ex", "vo_vfe_conv_fwd_ex", "vo_vfe_conv_bwd_ex",
     "vo_variance_head_ctl", "vo_conv_post_pcm16", "vo_conv_post_pcm16_lens", "vo_conv1d_plane_takes",
+    "vo_stft_mel_lens", "vo_stft_mel_frames",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

@@ -884,6 +884,71 @@ def stft_mel_ex(wav, window, fb, n_fft=1024, hop=256, n_mels=80, pad=None, mag_e
     return mel
 
 
+def stft_mel_frames(n, n_fft=1024, hop=256, pad=None):
+    """Frames of an n-sample signal under ``stft_mel_lens`` (vo_stft_mel_frames, host only): 1 + (n + 2 pad - n_fft)
+    // hop when n > pad and n + 2 pad >= n_fft, else 0."""
+    pad = n_fft // 2 if pad is None else pad
+    return int(_lib.lib().vo_stft_mel_frames(int(n), int(n_fft), int(hop), int(pad)))
+
+
+def _wave_lens32(lens, B, N, ref):
+    """``lens`` of ``stft_mel_lens`` -> contiguous int32 (B,) on ``ref``'s device.  A device tensor (int32 / int64) is
+    converted on the device and never read on the host (the kernel clamps it to [0, N]); a host sequence is
+    validated here."""
+    if isinstance(lens, torch.Tensor):
+        if lens.dtype not in (torch.int32, torch.int64) or lens.shape != (B,):
+            raise ValueError(f"stft_mel_lens: lens must be an int32 / int64 tensor of shape ({B},), got {lens.dtype} "
+                             f"{tuple(lens.shape)}")
+        if lens.device != ref.device:
+            raise ValueError(f"stft_mel_lens: lens is on {lens.device}, the waveform on {ref.device}")
+        return lens.to(torch.int32).contiguous()
+    host = [int(v) for v in lens]
+    if len(host) != B or any(v < 0 or v > N for v in host):
+        raise ValueError(f"stft_mel_lens: lens must be {B} sample counts in [0, {N}], got {host}")
+    return torch.tensor(host, dtype=torch.int32).to(ref.device)
+
+
+def _out_f32(t, shape, ref, name):
+    """A preallocated fp32 output of ``shape`` on ``ref``'s device, or a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=ref.device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != ref.device:
+        raise ValueError(f"stft_mel_lens: {name} must be fp32 {tuple(shape)} on {ref.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+    return _contig(t, name)
+
+
+def stft_mel_lens(wav, window, fb, lens, n_fft=1024, hop=256, pad=None, mag_eps=0.0, clip=False, log_floor=1e-5,
+                  channels_last=False, want_energy=True, want_fstats=False, mel=None, energy=None, fstats=None):
+    """``stft_mel_ex`` of a ragged batch in one launch (vo_stft_mel_lens): wav (B, N) fp32 whose row b holds
+    lens[b] samples -> (mel, energy, fstats, frames).  mel is (B, n_mels, F), or (B, F, n_mels) with
+    ``channels_last``, F = stft_mel_frames(N); energy (B, F) and fstats (B, F, 2) are None unless wanted (or handed
+    in); frames is the device int32 (B,) of per-row frame counts F_b = stft_mel_frames(lens[b]).  Frames f < F_b of
+    row b are bit for bit those of the dense call on wav[b:b+1, :lens[b]] (no sample past lens[b] is read), frames
+    >= F_b are 0.  ``lens``: int32 / int64 device tensor (never read on the host: the call is graph-capturable and
+    a replay follows lengths changed in place), a host sequence of B counts in [0, N], or None (every row is N)."""
+    _contig(wav, "wav")
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError(f"stft_mel_lens: wav must be fp32 (B, N), got {wav.dtype} {tuple(wav.shape)}")
+    B, N = wav.shape
+    n_mels = fb.shape[1]
+    pad = n_fft // 2 if pad is None else pad
+    st = _stream(wav)
+    lens32 = None if lens is None else _wave_lens32(lens, B, N, wav)
+    F = stft_mel_frames(N, n_fft, hop, pad)  # 0: empty outputs; the entry refuses such an N, nothing is launched
+    mel = _out_f32(mel, (B, F, n_mels) if channels_last else (B, n_mels, F), wav, "mel")
+    if want_energy or energy is not None:
+        energy = _out_f32(energy, (B, F), wav, "energy")
+    if want_fstats or fstats is not None:
+        fstats = _out_f32(fstats, (B, F, 2), wav, "fstats")
+    frames = torch.empty(B, dtype=torch.int32, device=wav.device)
+    _lib.check(_lib.lib().vo_stft_mel_lens(_ptr(wav), B, N, _ptr(window), _ptr(fb), n_fft, hop, n_mels, pad,
+                                           float(mag_eps), int(bool(clip)), float(log_floor), _ptr(mel),
+                                           _ptr(energy), _ptr(fstats), _ptr(lens32), _ptr(frames),
+                                           int(channels_last), st), "vo_stft_mel_lens")
+    return mel, energy, fstats, frames
+
+
 def stft_mel_bwd(wav, window, fb, gmel, n_fft=1024, hop=256, pad=None, mag_eps=1e-9, log_floor=1e-5):
     """Backward of ``stft_mel_ex`` (clip off): gmel (B, n_mels, F) = dL/dlogmel -> dL/dwav (B, N) fp32."""
     _contig(wav, "wav")
@@ -1526,9 +1591,11 @@ def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):
     return mel, energy, fstats
 
 
-def char_features(energy, fstats, durations, n_bins):
+def char_features(energy, fstats, durations, n_bins, flat=False):
     """energy (B, F), fstats (B, F, 2), durations: list of B int arrays -> (energy_char, kurtosis_char)
-    lists (per-character mean energy, spectral kurtosis) via vo_char_features."""
+    lists (per-character mean energy, spectral kurtosis) via vo_char_features.  ``flat``: the utterances'
+    characters concatenated instead, (energy_char (n,), kurtosis_char (n,), off) with utterance b's at
+    [off[b], off[b + 1]) (off: host int32 (B + 1,)) -- one buffer per output kind, for one copy to the host."""
     B, F = energy.shape
     dur = np.concatenate([np.asarray(d, np.int32).reshape(-1) for d in durations])
     off = np.zeros(B + 1, np.int32)
@@ -1540,6 +1607,8 @@ def char_features(energy, fstats, durations, n_bins):
     _lib.check(_lib.lib().vo_char_features(_ptr(energy.contiguous()), _ptr(fstats.contiguous()), F, _ptr(dur_d),
                                            _ptr(off_d), B, int(n_bins), _ptr(e), _ptr(k), _stream(energy)),
                "vo_char_features")
+    if flat:
+        return e, k, off
     return [e[off[i]:off[i + 1]] for i in range(B)], [k[off[i]:off[i + 1]] for i in range(B)]
 
 

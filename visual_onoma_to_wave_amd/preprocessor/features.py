@@ -9,30 +9,32 @@ norm of |X| over frequency), the frame -> character energy averaging of ``_proce
 ``build_from_path`` (:113-129, :624-645).  Corpus walking, TextGrid alignment, resampling
 (librosa.load) and glyph rendering stay host-side and are out of scope.
 
-GPU work per batch of utterances: one ``vo_stft_mel_ex`` launch (framing, FFT, |X|, mel, log,
-frame energy and the power statistics the kurtosis needs) and one ``vo_char_features``
-launch (per-character reductions over the duration spans).
+GPU work per call (per chunk under ``max_batch_samples``): the utterances, whatever their lengths, are padded
+into one (B, N_max) batch; one ``vo_stft_mel_lens`` launch (framing per signal length, FFT, |X|, mel
+channels-last, log, frame energy and the power statistics the kurtosis needs), one ``vo_char_features``
+launch (per-character reductions over the duration spans) and one device-to-host copy per output kind.
 """
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..audio import melscale_fbanks
+from ..audio import melscale_fbanks, pad_waves, padded_window
 
 
 class FeatureExtractor:
-    def __init__(self, config, device="cuda"):
+    def __init__(self, config, device="cuda", max_batch_samples=None):
+        """``max_batch_samples``: split a ``process`` call into several launches when B * N_max of the padded
+        batch would exceed it, so that one long clip does not pad a thousand short ones (None: one launch)."""
         a = config["audio"]
         st, mel = a["stft"], a["mel"]
         self.n_fft, self.hop, self.win = st["filter_length"], st["hop_length"], st["win_length"]
-        if self.win != self.n_fft:
-            raise NotImplementedError("win_length != filter_length")
         self.n_mels = mel["n_mel_channels"]
+        self.max_batch_samples = max_batch_samples
         self.device = torch.device(device)
         self.fb = melscale_fbanks(self.n_fft // 2 + 1, mel["mel_fmin"], mel["mel_fmax"], self.n_mels,
                                   a["sampling_rate"]).float().contiguous().to(self.device)
-        self.window = torch.hann_window(self.n_fft, periodic=True).to(self.device)
+        self.window = padded_window(self.win, self.n_fft).to(self.device)
 
     def get_spec(self, audio):
         """Preprocessor._get_spec: 1-D waveform -> (log-mel (80, F), energy (F,)) numpy."""
@@ -40,25 +42,49 @@ class FeatureExtractor:
         mel, energy, _ = ops.spec_features(w, self.window, self.fb, self.n_fft, self.hop)
         return mel[0].cpu().numpy(), energy[0].cpu().numpy()
 
+    def _chunks(self, lens):
+        """Consecutive index runs whose padded size B * N_max stays within max_batch_samples (a single utterance
+        longer than that is a run of its own)."""
+        if self.max_batch_samples is None:
+            return [list(range(len(lens)))]
+        runs, cur, n_max = [], [], 0
+        for i, n in enumerate(lens):
+            if cur and (len(cur) + 1) * max(n_max, n) > self.max_batch_samples:
+                runs.append(cur)
+                cur, n_max = [], 0
+            cur.append(i)
+            n_max = max(n_max, n)
+        if cur:
+            runs.append(cur)
+        return runs
+
     def process(self, wavs, durations):
         """Batch of utterances (1-D float arrays, trimmed as in _process) and their per-character
         durations (frames) -> list of dicts {mel (sum(d), 80), energy (n_chars,), kurtosis (n_chars,)}
-        exactly as _process saves them (mel transposed, truncated to sum(duration))."""
-        B = len(wavs)
-        # utterances of different lengths are framed separately (reflect padding is per signal);
-        # equal-length groups share one launch
-        by_len = {}
-        for i, w in enumerate(wavs):
-            by_len.setdefault(len(w), []).append(i)
-        res = [None] * B
-        for n, idx in by_len.items():
-            w = torch.as_tensor(np.stack([np.asarray(wavs[i], np.float32) for i in idx]), device=self.device)
-            mel, energy, fstats = ops.spec_features(w.contiguous(), self.window, self.fb, self.n_fft, self.hop)
-            e_c, k_c = ops.char_features(energy, fstats, [durations[i] for i in idx], self.n_fft // 2 + 1)
+        exactly as _process saves them (mel transposed, truncated to sum(duration)).  Each utterance is
+        framed as a signal of its own length (reflect padding is per signal): its results do not depend on
+        what it is batched with."""
+        lens = [len(w) for w in wavs]
+        T = [int(np.sum(d)) for d in durations]
+        if len(durations) != len(wavs):
+            raise ValueError(f"process: {len(wavs)} utterances, {len(durations)} duration lists")
+        for i, (n, t) in enumerate(zip(lens, T)):  # host check, before any launch
+            F_i = ops.stft_mel_frames(n, self.n_fft, self.hop, self.n_fft // 2)
+            if t > F_i:
+                raise ValueError(f"process: utterance {i}: durations sum to {t} frames, its {n} samples give {F_i}")
+        res = [None] * len(wavs)
+        for idx in self._chunks(lens):
+            wav, wl = pad_waves([wavs[i] for i in idx])
+            mel, energy, fstats, _ = ops.stft_mel_lens(wav.to(self.device), self.window, self.fb, wl.to(self.device),
+                                                       self.n_fft, self.hop, clip=True, channels_last=True,
+                                                       want_fstats=True)
+            e_c, k_c, off = ops.char_features(energy, fstats, [durations[i] for i in idx], self.n_fft // 2 + 1,
+                                              flat=True)
+            e_h, k_h = e_c.cpu().numpy(), k_c.cpu().numpy()  # one copy per output kind
+            mel_h = mel.cpu().numpy()
             for j, i in enumerate(idx):
-                T = int(np.sum(durations[i]))
-                res[i] = dict(mel=mel[j, :, :T].t().contiguous().cpu().numpy(), energy=e_c[j].cpu().numpy(),
-                              kurtosis=k_c[j].cpu().numpy().astype(np.float64))
+                res[i] = dict(mel=mel_h[j, :T[i]].copy(), energy=e_h[off[j]:off[j + 1]].copy(),
+                              kurtosis=k_h[off[j]:off[j + 1]].astype(np.float64))
         return res
 
 
