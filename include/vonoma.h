@@ -787,6 +787,33 @@ int vo_glyph_batch(const uint8_t* px, const int64_t* img_off, const int32_t* img
                    const int32_t* char_off, const int32_t* char_start, const int32_t* char_len,
                    int B, int H, int cell, int margin, int W_out, float* out, void* stream);
 
+/* Glyph stretching (additive): the per-character resize of the reference's renderers
+ * (scripts/preprocessor/visualtext_generator.py:23-46 `c_im.resize((width, fontsize))`; prediction.ipynb
+ * `c_im.resize((int(new_w), fs))`) with the layout above, from an atlas of unstretched glyphs and device tensors
+ * of ids and pixel widths.  The resize is PIL's bicubic resample, horizontal pass only, bit for bit on gray
+ * glyphs (8-bit fixed point: coefficients of 22 fractional bits, int32 sums).
+ *
+ * vo_glyph_stretch_table (host only, no HIP call): the coefficients of every target width w in 1 .. cell for
+ * source width src_w.  Record w (w - 1) / 2 + c (column c of width w) is 2 + src_w int32: xmin, n, K[0 .. src_w)
+ * with zeros past n; output pixel = clamp((2^21 + sum_x src[y][xmin + x] K[x]) >> 22, 0, 255).  w == src_w is the
+ * identity.  vo_glyph_stretch_table_size: its bytes (546 312 for 24 / 102), -1 for sizes out of range.
+ * VO_ERR_INVALID unless 1 <= src_w <= 64, 1 <= cell <= 256 and table_bytes is enough.
+ *
+ * vo_glyph_stretch: atlas (n_glyphs, H, src_w) uint8, ids (B, T) int64 (the model's `texts`), src_lens (B) int64,
+ * widths (B, T) int32 pixels (NULL: every width is src_w), table as above for (src_w, cell), all device memory ->
+ * out (B, 1, H, W_out) fp32, W_out >= T cell + 2 margin.  Cell t of row b, columns margin + t cell ... + cell - 1,
+ * holds atlas[ids[b, t]] resized to w = min(widths[b, t], cell) columns, centred as vo_glyph_batch centres it
+ * (pleft = (cell - w) / 2 + (cell - w) % 2), white elsewhere, as pixel / 255.  A cell is white when t >= src_lens[b],
+ * widths[b, t] <= 0 or ids[b, t] is outside [0, n_glyphs); the margins and the columns past margin + T cell are
+ * white.  Every element of out is written, and no value of ids, widths or src_lens makes the kernel read outside
+ * atlas or table.  Allocates nothing, never synchronises, reads nothing on the host: graph-capturable.
+ * H <= 65535. */
+int64_t vo_glyph_stretch_table_size(int src_w, int cell);
+int vo_glyph_stretch_table(int src_w, int cell, int32_t* table, int64_t table_bytes);
+int vo_glyph_stretch(const uint8_t* atlas, int n_glyphs, int H, int src_w, const int64_t* ids,
+                     const int64_t* src_lens, const int32_t* widths, int B, int T, int cell, int margin, int W_out,
+                     const int32_t* table, float* out, void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Multi-tensor Adam (decoupled = 0: L2 weight decay on the gradient) / AdamW (decoupled = 1) step over
  * nt fp32 tensors (tables of device pointers and element counts, host memory), torch's

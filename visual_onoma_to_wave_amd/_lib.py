@@ -264,6 +264,10 @@ _SIGNATURES = {
     "vo_stft_loss_grad": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vo_glyph_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_int, c_int, c_void_p, c_void_p]),
+    "vo_glyph_stretch_table_size": (c_int64, [c_int, c_int]),
+    "vo_glyph_stretch_table": (c_int, [c_int, c_int, c_void_p, c_int64]),
+    "vo_glyph_stretch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION

@@ -55,6 +55,137 @@ class GlyphBatch:
         return ops.glyph_batch(self.strips, self.char_widths, self.cell, self.margin, device, W_out=W_out)
 
 
+def widths_from_rates(rates, fontsize):
+    """Per-character pixel widths from the user's stretch rates, as prediction.ipynb computes them
+    (``int(fs * im_w_rate)``: a float64 product truncated toward zero), elementwise -> int32 array."""
+    r = np.asarray(rates, np.float64)
+    return np.array([int(fontsize * float(v)) for v in r.reshape(-1)], np.int32).reshape(r.shape)
+
+
+def allocate_widths(n_chars, canvas_width):
+    """The widths the training renderer gives the characters of an ``n_chars``-character text on a canvas
+    ``canvas_width`` pixels wide (``Generator._canvas_allocate``, visualtext_generator.py:19-21) -> int32 (n_chars,)."""
+    n_chars, canvas_width = int(n_chars), int(canvas_width)
+    return np.array([(canvas_width + i) // n_chars for i in range(n_chars)]).astype(np.int32)
+
+
+class GlyphAtlas:
+    """The unstretched glyphs of the vocabulary, ``glyphs`` (n_symbols, H, S) uint8 indexed by symbol id (row 0: PAD),
+    and what lays a batch of texts out from them on the GPU with a pixel width per character: the resize of the
+    reference's renderers (``c_im.resize((width, fontsize))``, PIL's bicubic, bit-exact) and ``GlyphBatch``'s
+    layout in one launch that reads ids, lengths and widths on the device (``ops.glyph_stretch``, DESIGN.md section
+    13).  Font rasterisation stays with the caller (``render`` does it with PIL).
+
+    ``to(device)`` uploads the glyphs and the coefficient table once and keeps them (``.glyphs_d``, ``.table_d``);
+    ``glyphs_d`` edited in place is what the next launch, or graph replay, reads."""
+
+    def __init__(self, glyphs, cell, stride=1):
+        glyphs = np.ascontiguousarray(glyphs)
+        if glyphs.dtype != np.uint8 or glyphs.ndim != 3 or 0 in glyphs.shape:
+            raise ValueError(f"GlyphAtlas: glyphs must be uint8 (n_symbols, H, S), got {glyphs.dtype} {glyphs.shape}")
+        self.glyphs = glyphs
+        self.cell, self.stride = int(cell), int(stride)
+        if self.cell < 1 or self.stride < 1:
+            raise ValueError(f"GlyphAtlas: cell and stride must be >= 1, got ({cell}, {stride})")
+        self.device = self.glyphs_d = self.table_d = None
+
+    n_symbols = property(lambda self: self.glyphs.shape[0])
+    height = property(lambda self: self.glyphs.shape[1])
+    src_w = property(lambda self: self.glyphs.shape[2])
+
+    @property
+    def margin(self):
+        return (self.stride // 2) * self.cell  # as GlyphBatch.margin
+
+    def to(self, device):
+        import torch
+        from . import ops
+        self.device = torch.device(device)
+        self.glyphs_d = torch.from_numpy(self.glyphs).to(self.device)
+        self.table_d = torch.from_numpy(ops.glyph_stretch_table(self.src_w, self.cell)).to(self.device)
+        return self
+
+    def _ints(self, a, name, dtype, lo, hi, what):
+        """A host sequence validated and uploaded, or a device tensor taken as it is (never read here)."""
+        import torch
+        if torch.is_tensor(a) and a.is_cuda:
+            return a
+        h = np.asarray(a.cpu() if torch.is_tensor(a) else a)
+        if h.dtype.kind not in "iu":
+            raise ValueError(f"GlyphAtlas: {name} must be integers, got {h.dtype}")
+        if lo is not None and h.size and (int(h.min()) < lo or int(h.max()) > hi):
+            raise ValueError(f"GlyphAtlas: {name} must be in [{lo}, {hi}] ({what}), got "
+                             f"[{int(h.min())}, {int(h.max())}]")
+        return torch.from_numpy(np.ascontiguousarray(h, dtype)).to(self.device, non_blocking=True)
+
+    def on_device(self, texts, widths=None):
+        """(texts int64, widths int32 or None) on the atlas's device.  Host sequences are validated (ValueError for
+        an id outside the atlas or a width outside [0, cell]) and uploaded; device tensors are returned as they
+        are, unread: the kernel whitens what is out of range there."""
+        if self.glyphs_d is None:
+            raise RuntimeError("GlyphAtlas: call to(device) first")
+        ids = self._ints(texts, "texts", np.int64, 0, self.n_symbols - 1, "the atlas's symbol ids")
+        w = None if widths is None else self._ints(widths, "widths", np.int32, 0, self.cell, "0 to the cell width")
+        return ids, w
+
+    def layout(self, texts, src_lens, widths=None, n_chars=None, out=None):
+        """``texts`` (B, T) symbol ids, ``src_lens`` (B,), ``widths`` (B, T) pixels (None: the glyphs unstretched) ->
+        (B, 1, H, n_chars * cell + 2 * margin) fp32 on the atlas's device (``n_chars``: T unless given; the columns
+        past T characters are white): what ``GlyphBatch.to(device, n_chars)`` gives for the strips of the same
+        characters at the same widths.  Host sequences are validated and uploaded, device tensors (int64, int64,
+        int32) are not read on the host (``on_device``): there an id outside the atlas or a width <= 0 is a white
+        cell, and a width above the cell is the cell."""
+        from . import ops
+        ids, w = self.on_device(texts, widths)
+        lens = self._ints(src_lens, "src_lens", np.int64, None, None, None)
+        if ids.dim() != 2:
+            raise ValueError(f"GlyphAtlas.layout: texts must have shape (B, T), got {tuple(ids.shape)}")
+        T = ids.shape[1]
+        n_chars = T if n_chars is None else int(n_chars)
+        if n_chars < T:
+            raise ValueError(f"GlyphAtlas.layout: n_chars={n_chars} is below the texts' length ({T})")
+        return ops.glyph_stretch(self.glyphs_d, self.table_d, ids, lens, w, self.cell, self.margin,
+                                 W_out=n_chars * self.cell + 2 * self.margin, out=out)
+
+    @classmethod
+    def render(cls, symbols, font, fontsize, background=(255, 255, 255), text=(0, 0, 0), cell=None, stride=1):
+        """Draw the atlas with PIL as the reference draws a character (visualtext_generator.py:36-38:
+        ``Image.new("RGB", (fs, fs), bg)``, ``draw.text((0, 0), ch, fill, font)``; ``convert("L")`` as its loaders
+        do).  ``symbols``: {character: id} (``utils.symbols.get_symbols``) or a sequence of characters (ids from 1);
+        id 0 (PAD) and ids without a character are background.  ``font``: a path (loaded at ``fontsize``) or a PIL
+        font object.  The colours must be gray: the reference resizes the three channels separately, which is the
+        resize of L only when they are equal."""
+        from PIL import Image, ImageDraw, ImageFont
+        background, text = tuple(int(v) for v in background), tuple(int(v) for v in text)
+        for name, col in (("background", background), ("text", text)):
+            if len(col) != 3 or len(set(col)) != 1 or not 0 <= col[0] <= 255:
+                raise ValueError(f"GlyphAtlas.render: {name} colour {col} is not gray (three equal values in 0..255)")
+        if not isinstance(symbols, dict):
+            symbols = {s: i + 1 for i, s in enumerate(symbols)}
+        if any(int(i) < 1 for i in symbols.values()):
+            raise ValueError("GlyphAtlas.render: symbol ids start at 1 (0 is PAD)")
+        fs = int(fontsize)
+        if isinstance(font, (str, bytes)) or hasattr(font, "__fspath__"):
+            font = ImageFont.truetype(str(font), fs)
+        glyphs = np.full((max(symbols.values(), default=0) + 1, fs, fs), background[0], np.uint8)
+        for ch, i in symbols.items():
+            c_im = Image.new("RGB", (fs, fs), background)
+            ImageDraw.Draw(c_im).text((0, 0), ch, fill=text, font=font)
+            glyphs[int(i)] = np.asarray(c_im.convert("L"), dtype=np.uint8)
+        return cls(glyphs, fs if cell is None else cell, stride)
+
+    @classmethod
+    def from_config(cls, preprocess_config, font=None):
+        """The atlas of a preprocess config: ``visual_text.fontsize / color / stride``, the font at ``path.font``
+        (or ``font``), the vocabulary and ``visual_text.json``'s max_pixelsize of ``path.preprocessed``."""
+        vt = preprocess_config["visual_text"]
+        pre = Path(preprocess_config["path"]["preprocessed"])
+        with open(pre / "visual_text.json") as f:
+            cell = json.load(f)["max_pixelsize"][0]
+        return cls.render(get_symbols(pre), preprocess_config["path"]["font"] if font is None else font,
+                          vt["fontsize"], vt["color"]["background"], vt["color"]["text"], cell, vt["stride"])
+
+
 def _read_gray(path):
     from PIL import Image
     with Image.open(path) as im:

@@ -1574,6 +1574,60 @@ def glyph_batch(strips, char_widths, cell, margin, device, W_out=None):
     return out
 
 
+def glyph_stretch_table(src_w, cell):
+    """The resize coefficients of ``glyph_stretch`` for glyphs ``src_w`` pixels wide and every target width in
+    1 .. cell: numpy int32 (cell (cell + 1) / 2, 2 + src_w), record w (w - 1) / 2 + c = xmin, n, K[0 .. src_w) of
+    output column c at width w (vo_glyph_stretch_table; host only: no GPU call)."""
+    L = _lib.lib()
+    nbytes = int(L.vo_glyph_stretch_table_size(int(src_w), int(cell)))
+    if nbytes < 0:
+        raise ValueError(f"glyph_stretch_table: src_w must be in [1, 64] and cell in [1, 256], got ({src_w}, {cell})")
+    table = np.empty((nbytes // (4 * (2 + int(src_w))), 2 + int(src_w)), np.int32)
+    _lib.check(L.vo_glyph_stretch_table(int(src_w), int(cell), ctypes.c_void_p(table.ctypes.data), nbytes),
+               "vo_glyph_stretch_table")
+    return table
+
+
+def glyph_stretch(atlas, table, ids, src_lens, widths, cell, margin, W_out=None, out=None):
+    """Glyphs ``atlas`` (n_glyphs, H, S) uint8 resized per character to ``widths`` (B, T) int32 pixels (None: S, the
+    glyphs as they are) and centred in ``cell``-wide cells behind ``margin`` white columns -> (B, 1, H, W_out) fp32
+    = pixel / 255, W_out = T cell + 2 margin unless given (wider: white).  ``ids`` (B, T) int64 (the model's texts),
+    ``src_lens`` (B,) int64, ``table`` = ``glyph_stretch_table(S, cell)``; all on the GPU, and never read on the host:
+    characters past src_lens, widths <= 0 and ids outside the atlas are white cells, a width above the cell is the
+    cell (vo_glyph_stretch; one launch on the current stream, graph-capturable).  ``out``: written in full."""
+    if atlas.dtype != torch.uint8 or atlas.dim() != 3:
+        raise ValueError(f"glyph_stretch: atlas must be uint8 (n_glyphs, H, S), got {atlas.dtype} {tuple(atlas.shape)}")
+    n_glyphs, H, S = atlas.shape
+    cell, margin = int(cell), int(margin)
+    if ids.dtype != torch.int64 or ids.dim() != 2:
+        raise ValueError(f"glyph_stretch: ids must be int64 (B, T), got {ids.dtype} {tuple(ids.shape)}")
+    B, T = ids.shape
+    if src_lens.dtype != torch.int64 or tuple(src_lens.shape) != (B,):
+        raise ValueError(f"glyph_stretch: src_lens must be int64 ({B},), got {src_lens.dtype} {tuple(src_lens.shape)}")
+    if widths is not None and (widths.dtype != torch.int32 or tuple(widths.shape) != (B, T)):
+        raise ValueError(f"glyph_stretch: widths must be int32 ({B}, {T}), got {widths.dtype} {tuple(widths.shape)}")
+    if table.dtype != torch.int32 or table.numel() != cell * (cell + 1) // 2 * (2 + S):
+        raise ValueError(f"glyph_stretch: table is not glyph_stretch_table({S}, {cell}) as an int32 tensor")
+    need = T * cell + 2 * margin
+    W_out = need if W_out is None else int(W_out)
+    if out is None:
+        out = torch.empty((B, 1, H, W_out), dtype=torch.float32, device=atlas.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1, H, W_out):
+        raise ValueError(f"glyph_stretch: out must be fp32 {(B, 1, H, W_out)}, got {out.dtype} {tuple(out.shape)}")
+    if W_out < need:
+        raise ValueError(f"glyph_stretch: W_out {W_out} is below T * cell + 2 * margin = {need}")
+    for name, t in (("atlas", atlas), ("table", table), ("ids", ids), ("src_lens", src_lens), ("widths", widths),
+                    ("out", out)):
+        if t is not None:
+            _contig(t, name)
+            if t.device != atlas.device:
+                raise ValueError(f"glyph_stretch: {name} is on {t.device}, the atlas on {atlas.device}")
+    _lib.check(_lib.lib().vo_glyph_stretch(_ptr(atlas), n_glyphs, H, S, _ptr(ids), _ptr(src_lens), _ptr(widths), B, T,
+                                           cell, margin, W_out, _ptr(table), _ptr(out), _stream(out)),
+               "vo_glyph_stretch")
+    return out
+
+
 # ----------------------------------------------------------------------------- offline feature extraction
 
 def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):

@@ -68,9 +68,11 @@ class SynthesisPipeline:
 class SynthesisInputs:
     """The static input tensors of a ``GraphedSynthesis`` (``gs.inputs``): what the captured graph reads.  A call
     copies its arguments here (``GlyphBatch.to(device, n_chars=max_src_len)`` gives the ``images`` argument at this
-    width)."""
+    width).  ``widths`` (int32 (batch, max_src_len), pixels per character) exists with an ``atlas`` only: the graph's
+    first launch then draws ``images`` from ``texts``, ``src_lens`` and ``widths``, so a replay follows a width
+    changed in place here."""
 
-    __slots__ = ("audiotypes", "texts", "src_lens", "images", "e_control", "d_control")
+    __slots__ = ("audiotypes", "texts", "src_lens", "images", "e_control", "d_control", "widths")
 
     def __init__(self, **tensors):
         for k in self.__slots__:
@@ -116,6 +118,16 @@ class GraphedSynthesis:
     not reported.  Controls: whatever ``ops.control_view`` accepts for (n, max_src_len); ``None`` resets to 1.0.
     ``texts`` (the model reads only its shape under ``use_image``): ``None`` stores zeros.
 
+    ``atlas`` (a ``dataset.GlyphAtlas`` already on the device, its ``cell``, ``stride`` and glyph height those of the
+    model's glyph encoder: ValueError otherwise): the images are drawn inside the graph.  The captured body's first
+    launch is ``vo_glyph_stretch`` from ``inputs.texts``, ``inputs.src_lens`` and ``inputs.widths`` into
+    ``inputs.images``, and the call is ``gs(audiotypes, src_lens, texts=..., widths=None)``:
+    ``texts`` (symbol ids) is required, ``images`` is refused, ``widths`` (n, max_src_len) are pixels per character
+    (``None`` resets them to the glyphs' own width: unstretched).  Host arrays are validated as
+    ``GlyphAtlas.layout`` validates them; device tensors are not read.  A replay follows ``inputs.widths`` changed in
+    place and glyphs edited in place in ``atlas.glyphs_d``.  Without ``atlas`` nothing of this exists: the same
+    arguments, the same graph.
+
     The model and the vocoder must be in eval mode (RuntimeError otherwise); the call runs under ``no_grad``.
 
     Capture: on a side stream after ``warmup`` eager runs (they build the weight packs, the vocoder's side streams
@@ -127,7 +139,8 @@ class GraphedSynthesis:
     between) or a submodule has been replaced, the next call captures again before it replays and ``gs.captures``
     goes up by one: a replay never synthesises with weights the modules no longer hold."""
 
-    def __init__(self, model, vocoder, batch, max_src_len, max_mel_len, pcm_scale=None, use_image=True, warmup=2):
+    def __init__(self, model, vocoder, batch, max_src_len, max_mel_len, pcm_scale=None, use_image=True, warmup=2,
+                 atlas=None):
         from .train import _check_graph_runtime
         _check_graph_runtime("GraphedSynthesis (HIP-graph replay)")
         batch, max_src_len, max_mel_len = int(batch), int(max_src_len), int(max_mel_len)
@@ -159,7 +172,21 @@ class GraphedSynthesis:
             vfe = model.encoder.VisualFeatureExtractor
             width = (max_src_len + 2 * (vfe.stride // 2)) * vfe.slice_width  # n_chars * cell + 2 * margin
             images = torch.ones((batch, vfe.dim3, vfe.slice_height, width), dtype=torch.float32, device=dev)
+        self.atlas, widths = atlas, None
+        if atlas is not None:
+            if not self.use_image:
+                raise ValueError("GraphedSynthesis: atlas draws the images: it needs use_image=True")
+            if atlas.glyphs_d is None or atlas.glyphs_d.device != dev:
+                raise ValueError(f"GraphedSynthesis: atlas must be on the vocoder's device {dev} (atlas.to(device)), "
+                                 f"it is on {atlas.device}")
+            have = (atlas.cell, atlas.stride, atlas.height, 1)
+            want = (vfe.slice_width, vfe.stride, vfe.slice_height, vfe.dim3)
+            if have != want:
+                raise ValueError(f"GraphedSynthesis: atlas (cell, stride, height, channels) = {have} does not match "
+                                 f"the model's glyph encoder {want}")
+            widths = torch.full((batch, max_src_len), atlas.src_w, dtype=torch.int32, device=dev)
         self.inputs = SynthesisInputs(
+            widths=widths,
             audiotypes=torch.zeros(batch, dtype=torch.int64, device=dev),
             texts=torch.zeros((batch, max_src_len), dtype=torch.int64, device=dev),
             src_lens=torch.full((batch,), max_src_len, dtype=torch.int64, device=dev),
@@ -211,6 +238,11 @@ class GraphedSynthesis:
 
     def _body(self):
         i = self.inputs
+        if self.atlas is not None:  # every element of i.images is written
+            from . import ops
+            a = self.atlas
+            ops.glyph_stretch(a.glyphs_d, a.table_d, i.texts, i.src_lens, i.widths, a.cell, a.margin,
+                              W_out=i.images.shape[3], out=i.images)
         out = self.model(i.audiotypes, i.texts, i.src_lens, self.max_src_len, None, None, self.max_mel_len, None,
                          None, None, i.images, None, self.use_image, e_control=i.e_control, d_control=i.d_control)
         wav = self.vocoder.run(out[1], out[9], self.pcm_scale)
@@ -248,7 +280,7 @@ class GraphedSynthesis:
         if n < self.batch:  # rows n ... batch - 1: copies of request 0
             dst[n:].copy_(dst[:1].expand(self.batch - n, *dst.shape[1:]))
 
-    def __call__(self, audiotypes, src_lens, images=None, texts=None, e_control=None, d_control=None):
+    def __call__(self, audiotypes, src_lens, images=None, texts=None, e_control=None, d_control=None, widths=None):
         from . import ops
         if self.model.training or self.vocoder.training:
             raise RuntimeError("GraphedSynthesis: the model and the vocoder must be in eval mode")
@@ -258,17 +290,31 @@ class GraphedSynthesis:
             raise ValueError(f"GraphedSynthesis: src_lens must have shape (n,) with 1 <= n <= batch = {self.batch}, "
                              f"got {tuple(src_lens.shape)}")
         i = self.inputs
-        if self.use_image and images is None:
+        atlas = self.atlas
+        if atlas is not None:
+            if images is not None:
+                raise ValueError("GraphedSynthesis: this object draws its images from an atlas inside the graph: pass "
+                                 "texts (and widths), not images")
+            if texts is None:
+                raise ValueError(f"GraphedSynthesis: an atlas needs texts (symbol ids) of shape "
+                                 f"{tuple(i.texts[:n].shape)}")
+            texts, widths = atlas.on_device(texts, widths)  # host arrays: validated; device tensors: not read
+        elif widths is not None:
+            raise ValueError("GraphedSynthesis: widths need an atlas (GraphedSynthesis(..., atlas=...)); this object "
+                             "takes images")
+        elif self.use_image and images is None:
             raise ValueError(f"GraphedSynthesis: use_image needs images of shape {tuple(i.images[:n].shape)}")
         if not self.use_image and texts is None:
             raise ValueError(f"GraphedSynthesis: use_image=False needs texts of shape {tuple(i.texts[:n].shape)}")
         # every argument is checked before the first copy: a refused call leaves the static inputs as they were
         copies = [self._checked(i.audiotypes, audiotypes, n, "audiotypes"),
                   self._checked(i.src_lens, src_lens, n, "src_lens")]
-        if self.use_image:
+        if self.use_image and atlas is None:
             copies.append(self._checked(i.images, images, n, "images"))
         if texts is not None:
             copies.append(self._checked(i.texts, texts, n, "texts"))
+        if widths is not None:
+            copies.append(self._checked(i.widths, widths, n, "widths"))
         with torch.no_grad(), torch.cuda.device(self.device):
             for dst, control in ((i.e_control, e_control), (i.d_control, d_control)):
                 if control is not None:  # converted to fp32 on the device where it is not (ops.control_view)
@@ -282,6 +328,8 @@ class GraphedSynthesis:
             for dst, control in ((i.e_control, e_control), (i.d_control, d_control)):
                 if control is None:
                     dst.fill_(1.0)
+            if atlas is not None and widths is None:  # unstretched, not what an earlier call left
+                i.widths.fill_(atlas.src_w)
             if self._stale():
                 self._capture()
             self.graph.replay()
