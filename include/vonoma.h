@@ -814,6 +814,66 @@ int vo_glyph_stretch(const uint8_t* atlas, int n_glyphs, int H, int src_w, const
                      const int64_t* src_lens, const int32_t* widths, int B, int T, int cell, int margin, int W_out,
                      const int32_t* table, float* out, void* stream);
 
+/* Repeat and consecutive augmentation (additive): a padded training batch assembled on the
+ * device from a base corpus packed once and a plan, one row per utterance.  Replaces the file-writing loop of
+ * scripts/preprocessor/preprocessor.py:468-622 (_augmentation, _repeataug, _consecutiveaug) together with the
+ * collate padding (pad_1D / pad_2D, scripts/utils/tools.py:585-614) and the layout of vo_glyph_batch.
+ *
+ * vo_corpus: U base utterances in device memory.  Utterance u has n = char_off[u + 1] - char_off[u] >= 1
+ * characters at char_off[u] of the flat per-character arrays, F = frame_off[u + 1] - frame_off[u] mel frames at row
+ * frame_off[u] of mel, and a strip of strip_h rows of strip_w[u] uint8 columns at px_off[u] of px.  Character c has
+ * id ch_id, duration d = ch_dur >= 0, duration prefix s_c = ch_dstart = d[0] + ... + d[c - 1] (F = s_n), pixel
+ * width w = ch_width >= 0 and first strip column ch_col = w[0] + ... + w[c - 1] (strip_w = their sum).  ch_energy
+ * and ch_kurtosis may each be NULL (a model without that condition); the output of the same name is then NULL too.
+ *
+ * A plan is (B, 5) int32 in device memory, row b = src, pos, m, m_mel, r: utterance src with m more copies of
+ * character pos, m_mel more copies of that character's frames, the whole repeated r times.  With n' = n + m and
+ * F' = F + m_mel d[pos], row b has n' r characters and F' r frames:
+ *   output character j is base character sigma(j mod n'):  sigma(j') = j' for j' < pos, pos for pos <= j' <= pos + m,
+ *     j' - m above; text id, duration, energy, kurtosis, width and glyph cell are those of that character, the
+ *     cell laid out as vo_glyph_batch lays it out (same pleft for widths above the cell too, same margin);
+ *   output frame f is base frame phi(f mod F'):  phi(f') = f' for f' < s_pos, s_pos + (f' - s_pos) mod d[pos] for
+ *     s_pos <= f' < s_pos + (m_mel + 1) d[pos] (empty when d[pos] = 0), f' - m_mel d[pos] above.
+ * Past a row's length texts, durations, energies, kurtosises and mels are 0 and images 1.0 (white); every element of
+ * every output is written.  The reference's consecutive augmentation of k copies is m = k - 1, m_mel = k (its mel
+ * gains one copy more than its durations); its repeat augmentation is r.
+ *
+ * A row is refused on the device, never raised: it is written as an empty utterance (audiotype 0, src_len =
+ * mel_len = 0, all padding) and status[b] says why, in this order: VO_AUG_BAD_ROW (src outside [0, U), pos outside
+ * [0, n), m < 0, m_mel < 0 or r < 1), VO_AUG_CHARS_OVER (n' r > T_src), VO_AUG_FRAMES_OVER (F' r > T_mel);
+ * VO_AUG_OK otherwise.
+ *
+ * vo_augment_batch: outputs audiotypes (B) int64, texts (B, T_src) int64, src_lens (B) int64, mels (B, T_mel,
+ * n_mels) fp32, mel_lens (B) fp32, energies / kurtosises / durations (B, T_src) fp32, images (B, 1, H, W_out) fp32,
+ * status (B) int32; H == strip_h, T_src cell + 2 margin <= W_out < 2^21, B <= 65535.  One launch; allocates nothing, never
+ * synchronises, reads nothing on the host: graph-capturable, and a plan rewritten in place is what a replay reads.
+ * Frames move as 16-byte vectors when n_mels % 4 == 0 and both mel pointers are 16-byte aligned. */
+#define VO_AUG_OK 0
+#define VO_AUG_BAD_ROW 1
+#define VO_AUG_CHARS_OVER 2
+#define VO_AUG_FRAMES_OVER 3
+typedef struct vo_corpus {
+  int32_t U, n_mels, strip_h;
+  const int32_t* char_off;   /* (U + 1) */
+  const int64_t* frame_off;  /* (U + 1), in frames */
+  const int64_t* px_off;     /* (U), in pixels */
+  const int32_t* strip_w;    /* (U) */
+  const int64_t* audiotype;  /* (U) */
+  const int32_t* ch_id;      /* flat per-character arrays, char_off[U] entries each */
+  const int32_t* ch_dur;
+  const int32_t* ch_dstart;
+  const int32_t* ch_width;
+  const int32_t* ch_col;
+  const float* ch_energy;    /* or NULL */
+  const float* ch_kurtosis;  /* or NULL */
+  const float* mel;          /* (frame_off[U], n_mels) */
+  const uint8_t* px;
+} vo_corpus;
+int vo_augment_batch(const vo_corpus* c, const int32_t* plan, int B, int T_src, int T_mel, int H, int cell, int margin,
+                     int W_out, int64_t* audiotypes, int64_t* texts, int64_t* src_lens, float* mels, float* mel_lens,
+                     float* energies, float* kurtosises, float* durations, float* images, int32_t* status,
+                     void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Multi-tensor Adam (decoupled = 0: L2 weight decay on the gradient) / AdamW (decoupled = 1) step over
  * nt fp32 tensors (tables of device pointers and element counts, host memory), torch's

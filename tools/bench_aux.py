@@ -7,7 +7,13 @@
 * feature extraction (vo_stft_mel_ex + vo_char_features): 64 utterances of 2 s at 22.05 kHz
   -> mel + character energy + kurtosis; CPU baseline = oracle/mel.char_features (torch-CPU).
 
-    python tools/bench_aux.py
+* augmented batch (vo_augment_batch, dataset.DeviceCorpus): a training batch of 48 mixed repeat / consecutive
+  variants from a synthetic corpus of ICASSP-like sizes, assembled on the device from a device plan, against the
+  path it replaces: the variants' files materialised in a temporary directory, read through Dataset.__getitem__,
+  collate_fn and to_device.  Bytes per second are the batch's output bytes over the launch time.
+
+    python tools/bench_aux.py [glyph] [features] [augment] [--out FILE]     (all three by default)
+    rocprofv3 --kernel-trace --stats ... -- python tools/bench_aux.py augment --kernels 200   (launches only)
 """
 import json
 import os
@@ -118,6 +124,131 @@ def features():
                              "kind": "port", "sample": f"{n} utterances, oracle/mel.char_features torch-CPU"}}
 
 
+def augment(kernels=0):
+    import copy
+    import ctypes
+    import shutil
+    import statistics
+    import tempfile
+    from pathlib import Path
+    from PIL import Image
+    import augment_check as C
+    from helpers import DATA, configs
+    from visual_onoma_to_wave_amd import _lib, ops
+    from visual_onoma_to_wave_amd.dataset import Dataset, DeviceCorpus
+    from visual_onoma_to_wave_amd.utils.tools import to_device
+    rng = np.random.default_rng(14)
+    pc, mc, tc = copy.deepcopy(configs())
+    cfg, B, U, H, cell, dev = pc["augmentation"], 48, 120, 24, 102, torch.device("cuda")
+    sym = C.symbol_ids()
+    chars, labels = list(sym), sorted(json.load(open(os.path.join(DATA, "audiotype.json"))))
+    bases = []
+    for u in range(U):  # 2 .. 7 characters of 8 .. 40 frames (0.1 .. 0.46 s) and 30 .. 102 pixels; one in three has a run
+        n = int(rng.integers(2, 8))
+        text = [chars[i] for i in rng.integers(0, len(chars), n)]
+        if u % 3 == 0 and n >= 4:
+            text[1:4] = [text[1]] * 3
+        dur, width = rng.integers(8, 41, n), rng.integers(30, cell + 1, n).astype(np.int32)
+        label = labels[u % len(labels)]
+        bases.append({"id": f"font_24pt_{label}-a1-{u:03d}", "label": label, "text_str": "".join(text),
+                      "audiotype": u % len(labels), "text": np.array([sym[c] for c in text]),
+                      "mel": rng.standard_normal((int(dur.sum()), 80)).astype(np.float32),
+                      "energy": rng.standard_normal(n), "kurtosis": None, "duration": dur,
+                      "image": (rng.integers(0, 256, (H, int(width.sum()))).astype(np.uint8), width),
+                      "event_image_feature": None})
+    corpus = DeviceCorpus.from_arrays(bases, cell, pc["visual_text"]["stride"], dev)
+    names, plan = corpus.variants(cfg)
+    rows = np.sort(rng.choice(len(names), B, replace=False))
+    plan_h = plan[rows]
+    first = corpus.batch(plan_h)
+    T_src, T_mel = first[4], first[7]
+    plan_d = torch.from_numpy(plan_h).to(dev)
+    static = corpus.batch(plan_d, T_src, T_mel)
+    assert all(torch.equal(static[i], first[i]) for i in (1, 2, 3, 5, 6, 8, 10, 11))
+    o = dict(zip(ops.AUGMENT_OUT, [static[i] for i in (1, 2, 3, 5, 6, 8, 9, 10, 11)] + [corpus.last_status]))
+    P = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    W = static[11].shape[-1]
+
+    fn = _lib.lib().vo_augment_batch
+    c_args = (ctypes.byref(corpus.struct), P(plan_d), B, T_src, T_mel, H, cell, corpus.margin, W,
+              *[P(o[k]) for k in ops.AUGMENT_OUT], st)
+
+    def launch():  # the launch alone, through the C ABI
+        fn(*c_args)
+    out_bytes = sum(t.numel() * t.element_size() for t in o.values() if t is not None)
+    if kernels:  # for a kernel trace (rocprofv3 --kernel-trace --stats): launches only
+        for _ in range(kernels):
+            launch()
+        torch.cuda.synchronize()
+        return {"metric": "augment launches for a kernel trace", "value": kernels, "unit": "launches",
+                "bytes_per_launch": out_bytes}
+
+    # the path this replaces: the variants as files, Dataset.__getitem__, collate_fn, to_device
+    tmp = Path(tempfile.mkdtemp(prefix="vo_aug_bench_"))
+    try:
+        for f in ("visual_text.json", "audiotype.json", "symbols.json"):
+            shutil.copy(os.path.join(DATA, f), tmp / f)
+        lines = []
+        for name, (src, pos, m, mm, r) in zip([names[i] for i in rows], plan_h.tolist()):
+            u = bases[src]
+            v = C.model_row(u, pos, m, mm, r)
+            for sub, a in (("mel", v["mel"]), ("energy", v["energy"]), ("duration", v["duration"]),
+                           ("image/width", v["image"][1])):
+                (tmp / sub / u["label"]).mkdir(parents=True, exist_ok=True)
+                np.save(tmp / sub / u["label"] / f"{name}.npy", a)
+            (tmp / "image/png" / u["label"]).mkdir(parents=True, exist_ok=True)
+            Image.fromarray(np.repeat(v["image"][0][:, :, None], 3, axis=2)).save(tmp / "image/png" / u["label"] / f"{name}.png")
+            text = "".join(u["text_str"][c] for c in C.sigma(len(u["text_str"]), pos, m, r))
+            lines.append(f"{name}|{u['label']}|24|font|{text}")
+        (tmp / "bench.txt").write_text("\n".join(lines) + "\n", encoding="utf-8")
+        pc["path"]["preprocessed"] = str(tmp)
+        tc["optimizer"] = dict(tc["optimizer"], batch_size=B)
+        ds = Dataset("bench.txt", pc, tc, mc)
+
+        def host():
+            batch = to_device(ds.collate_fn([ds[i] for i in range(B)])[0], dev)
+            torch.cuda.synchronize()
+            return batch
+        want = host()
+        assert want[0] == first[0] and all(torch.equal(want[i], first[i]) for i in (1, 2, 3, 5, 6, 8, 10, 11))
+        t_host, t_call, t_launch = [], [], []
+        for _ in range(5):  # the two paths alternate; windows of 0.1 s and more
+            t0 = time.perf_counter()
+            for _ in range(3):
+                host()
+            t_host.append((time.perf_counter() - t0) / 3)
+            t_call.append(timed(lambda: corpus.batch(plan_d, T_src, T_mel, out=static), 2000))
+            t_launch.append(timed(launch, 5000))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    med = statistics.median
+    spread = lambda v: [round(min(v) * 1e6, 2), round(max(v) * 1e6, 2)]  # noqa: E731
+    return {"metric": "augmented training batch from a device plan (preprocessor.py:468-622 + collate, DESIGN.md 14)",
+            "unit": "batches/s", "value": round(1 / med(t_call), 1),
+            "config": {"batch": B, "corpus_utterances": U, "rows_in_corpus_plan": len(names), "T_src": T_src,
+                       "T_mel": T_mel, "image_width": W, "n_mels": 80, "windows": 5},
+            "device_path": {"corpus.batch_us": round(med(t_call) * 1e6, 2), "corpus.batch_us_min_max": spread(t_call),
+                            "launch_us": round(med(t_launch) * 1e6, 2), "launch_us_min_max": spread(t_launch),
+                            "note": "back-to-back launches, device events; the 48-row batch stays in the L2 / MALL"},
+            "host_path": {"batch_us": round(med(t_host) * 1e6, 1), "batch_us_min_max": spread(t_host),
+                          "note": "48 x Dataset.__getitem__ (np.load, PNG decode; files in the page cache), collate_fn, "
+                                  "to_device + synchronize, one process"},
+            "speedup_corpus.batch_vs_host": round(med(t_host) / med(t_call), 1),
+            "roofline": {"bound": "hbm", "achieved": round(out_bytes / med(t_launch) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s of output bytes", "frac": round(out_bytes / med(t_launch) / 1e9 / HBM_PEAK_GBS, 4),
+                         "bytes_per_launch": out_bytes}}
+
+
 if __name__ == "__main__":
-    print(json.dumps(glyph()))
-    print(json.dumps(features()))
+    args = sys.argv[1:]
+    out = args.pop(args.index("--out") + 1) if "--out" in args else None
+    kernels = int(args.pop(args.index("--kernels") + 1)) if "--kernels" in args else 0
+    args = [a for a in args if a not in ("--out", "--kernels")]
+    which = {"glyph": glyph, "features": features, "augment": (lambda: augment(kernels)) if kernels else augment}
+    lines = [json.dumps(which[k]()) for k in (args or list(which))]
+    print("\n".join(lines))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")

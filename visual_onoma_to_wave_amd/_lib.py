@@ -96,6 +96,15 @@ class HeadDesc(ctypes.Structure):
     ]
 
 
+class Corpus(ctypes.Structure):
+    """vo_corpus (include/vonoma.h, vo_augment_batch)."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("U", "n_mels", "strip_h")] + [
+        (f, c_void_p) for f in ("char_off", "frame_off", "px_off", "strip_w", "audiotype", "ch_id", "ch_dur",
+                                "ch_dstart", "ch_width", "ch_col", "ch_energy", "ch_kurtosis", "mel", "px")]
+
+
+AUG_OK, AUG_BAD_ROW, AUG_CHARS_OVER, AUG_FRAMES_OVER = 0, 1, 2, 3
+
 _SIGNATURES = {
     "vo_last_error": (ctypes.c_char_p, []),
     "vo_version": (c_int, []),
@@ -268,6 +277,7 @@ _SIGNATURES = {
     "vo_glyph_stretch_table": (c_int, [c_int, c_int, c_void_p, c_int64]),
     "vo_glyph_stretch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vo_augment_batch": (c_int, [ctypes.POINTER(Corpus), c_void_p] + [c_int] * 7 + [c_void_p] * 11),
 }
 
 ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION

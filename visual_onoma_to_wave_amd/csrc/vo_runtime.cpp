@@ -97,6 +97,7 @@ static const char* const kSymbols[] = {
     "vo_variance_head_ctl", "vo_conv_post_pcm16", "vo_conv_post_pcm16_lens", "vo_conv1d_plane_takes",
     "vo_stft_mel_lens", "vo_stft_mel_frames",
     "vo_glyph_stretch_table_size", "vo_glyph_stretch_table", "vo_glyph_stretch",
+    "vo_augment_batch",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

@@ -291,3 +291,167 @@ class Dataset(_TorchDataset):
         if not self.drop_last and len(tail) > 0:
             idx_arr += [tail.tolist()]
         return [self.reprocess(data, idx) for idx in idx_arr]
+
+
+class DeviceCorpus:
+    """The base utterances packed once on the GPU, and training batches assembled from them by a *plan* in one launch
+    (``vo_augment_batch``): the repeat and consecutive augmentations of the reference
+    (scripts/preprocessor/preprocessor.py:468-622), ``pad_1D`` / ``pad_2D`` and ``GlyphBatch``'s layout, without a file
+    or a host copy per variant.  A plan row is ``src, pos, m, m_mel, r`` (``preprocessor.augment``); ``batch`` returns
+    the 13-item tuple ``utils.tools.to_device(Dataset.reprocess(...))`` returns, element for element."""
+
+    def __init__(self):
+        raise TypeError("DeviceCorpus: use from_arrays or from_dataset")
+
+    @classmethod
+    def from_arrays(cls, utterances, cell, stride, device):
+        """``utterances``: a list of dicts with the keys ``Dataset.__getitem__`` returns (id, audiotype, text, mel,
+        energy, kurtosis, duration, image = (strip, widths)); energy / kurtosis None for all or for none."""
+        import torch
+        from . import _lib
+        self = object.__new__(cls)
+        self.cell, self.stride, self.device = int(cell), int(stride), torch.device(device)
+        if self.cell < 1 or self.stride < 1:
+            raise ValueError(f"DeviceCorpus: cell and stride must be >= 1, got ({cell}, {stride})")
+        if not utterances:
+            raise ValueError("DeviceCorpus: no utterances")
+        self.names, self.texts, self.durations = [], [], []
+        flat = {k: [] for k in ("id", "dur", "dstart", "width", "col", "energy", "kurtosis", "mel", "px")}
+        strip_w, audiotype = [], []
+        has = {k: utterances[0][k] is not None for k in ("energy", "kurtosis")}
+        n_mels = H = None
+        for i, u in enumerate(utterances):
+            who = f"DeviceCorpus: utterance {i} ({u.get('id')!r})"
+            text, dur = np.asarray(u["text"]).reshape(-1), np.asarray(u["duration"]).reshape(-1)
+            mel = np.asarray(u["mel"])
+            if u.get("image") is None:
+                raise ValueError(f"{who}: has no image (a Dataset with use_image)")
+            strip, width = np.asarray(u["image"][0]), np.asarray(u["image"][1]).reshape(-1)
+            n = len(text)
+            per_char = {"duration": dur, "widths": width}
+            for k in ("energy", "kurtosis"):
+                if (u[k] is not None) != has[k]:
+                    raise ValueError(f"{who}: {k} is given for some utterances and None for others")
+                if has[k]:
+                    per_char[k] = np.asarray(u[k]).reshape(-1)
+            if n < 1 or any(len(a) != n for a in per_char.values()):
+                raise ValueError(f"{who}: the text has {n} characters, "
+                                 + ", ".join(f"{k} {len(a)}" for k, a in per_char.items()) + " (all equal and >= 1)")
+            if dur.dtype.kind not in "iu" or width.dtype.kind not in "iu" or int(dur.min()) < 0 or int(width.min()) < 0:
+                raise ValueError(f"{who}: durations and widths must be integers >= 0")
+            if mel.ndim != 2 or mel.shape[0] != int(dur.sum()):
+                raise ValueError(f"{who}: the mel has shape {mel.shape}, the durations sum to {int(dur.sum())} frames")
+            if strip.ndim != 2 or strip.dtype != np.uint8 or strip.shape[1] != int(width.sum()):
+                raise ValueError(f"{who}: the strip is {strip.dtype} {strip.shape}, the widths sum to "
+                                 f"{int(width.sum())} columns (a gray uint8 (H, sum widths) strip)")
+            n_mels, H = n_mels or mel.shape[1], H or strip.shape[0]
+            if mel.shape[1] != n_mels or strip.shape[0] != H or min(n_mels, H) < 1:
+                raise ValueError(f"{who}: {mel.shape[1]} mel bins and {strip.shape[0]} strip rows, the corpus has "
+                                 f"{n_mels} and {H}")
+            self.names.append(u.get("id"))
+            self.texts.append(tuple(int(t) for t in text))
+            self.durations.append(dur.astype(np.int64))
+            audiotype.append(int(u["audiotype"]))
+            strip_w.append(strip.shape[1])
+            flat["id"].append(text)
+            flat["dur"].append(dur)
+            flat["dstart"].append(np.cumsum(dur) - dur)
+            flat["width"].append(width)
+            flat["col"].append(np.cumsum(width) - width)
+            flat["mel"].append(mel.astype(np.float32, copy=False))
+            flat["px"].append(strip.reshape(-1))
+            for k in ("energy", "kurtosis"):
+                if has[k]:
+                    flat[k].append(per_char[k].astype(np.float32))  # as to_device's .float()
+        self.n_chars = [len(t) for t in self.texts]
+        self.n_frames = [int(d.sum()) for d in self.durations]
+        self.n_mels, self.height = int(n_mels), int(H)
+        off = lambda sizes: np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])  # noqa: E731
+        host = {"char_off": off(self.n_chars).astype(np.int32), "frame_off": off(self.n_frames).astype(np.int64),
+                "px_off": off([H * w for w in strip_w])[:-1].astype(np.int64), "strip_w": np.asarray(strip_w, np.int32),
+                "audiotype": np.asarray(audiotype, np.int64), "mel": np.concatenate(flat["mel"]),
+                "px": np.concatenate(flat["px"])}
+        if int(host["frame_off"][-1]) * self.n_mels >= 2 ** 62 or int(off(self.n_chars)[-1]) >= 2 ** 31:
+            raise ValueError("DeviceCorpus: too large")
+        for k in ("id", "dur", "dstart", "width", "col"):
+            host["ch_" + k] = np.concatenate(flat[k]).astype(np.int32)
+        for k in ("energy", "kurtosis"):
+            host["ch_" + k] = np.concatenate(flat[k]) if has[k] else None
+        # the device arrays live as long as the corpus: the struct holds their addresses
+        self.tensors = {k: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+                        for k, a in host.items()}
+        self.struct = _lib.Corpus(U=len(self.texts), n_mels=self.n_mels, strip_h=self.height,
+                                  **{k: None if t is None else t.data_ptr() for k, t in self.tensors.items()})
+        self.last_status = None
+        return self
+
+    @classmethod
+    def from_dataset(cls, ds, indices=None, base_only=True, device="cuda"):
+        """The samples ``indices`` (all by default) of a ``Dataset``, each read once through ``ds[i]``.  ``base_only``:
+        names that carry an augmentation suffix (a metadata file that already lists the reference's variants) are
+        left out."""
+        from .preprocessor.augment import is_variant_name
+        idx = range(len(ds)) if indices is None else indices
+        return cls.from_arrays([ds[i] for i in idx if not (base_only and is_variant_name(ds.basename[i]))],
+                               ds.width, ds.stride, device)
+
+    def __len__(self):
+        return len(self.texts)
+
+    @property
+    def margin(self):
+        return (self.stride // 2) * self.cell  # as GlyphBatch.margin
+
+    def variants(self, cfg, mel_copies="reference"):
+        """(names, plan int32 (N, 5)) of the whole augmented corpus: for every utterance its base row and then the
+        variants ``preprocessor.augment.variants`` lists, named as the reference saves them.  An epoch is a shuffle of
+        row indices."""
+        from .preprocessor import augment as AU
+        names, rows = [], []
+        for u, text in enumerate(self.texts):
+            for suffix, pos, m, mm, r, _ in [("", 0, 0, 0, 1, text)] + AU.variants(text, cfg, mel_copies):
+                names.append(f"{self.names[u]}{suffix}")
+                rows.append((u, pos, m, mm, r))
+        return names, np.asarray(rows, np.int32)
+
+    def batch(self, plan, max_src_len=None, max_mel_len=None, out=None, names=None):
+        """The batch of ``plan`` -> (ids, audiotypes, texts, src_lens, max_src_len, mels, mel_lens, max_mel_len,
+        energies, kurtosises, durations, images, None) on the corpus's device, with ``to_device``'s dtypes.
+
+        ``plan`` on the host (numpy or a sequence of rows) is checked first: a row out of range or over a cap is a
+        ValueError naming the row and the rule, and nothing is launched.  Without caps the caps are the batch's own
+        maxima, as ``Dataset.reprocess`` pads.  ``ids`` are the reference's save names (or ``names``).
+        ``plan`` as an int32 (B, 5) tensor on the device is never read back: the caps are required, ``ids`` is
+        ``names`` (None by default), and a bad row comes out as an empty utterance with its reason in
+        ``self.last_status`` (``_lib.AUG_*``).  ``out``: the tuple of an earlier call of the same shapes, refilled in
+        place (a static batch for a captured training step)."""
+        import torch
+        from . import ops
+        from .preprocessor import augment as AU
+        if torch.is_tensor(plan) and plan.is_cuda:
+            if max_src_len is None or max_mel_len is None:
+                raise ValueError("DeviceCorpus.batch: a device plan needs max_src_len and max_mel_len")
+            plan_d, ids = plan, names
+        else:
+            p, src_lens, mel_lens = AU.check_plan(plan.numpy() if torch.is_tensor(plan) else plan, self.n_chars,
+                                                  self.n_frames, self.durations, max_src_len, max_mel_len)
+            max_src_len = max(src_lens) if max_src_len is None else max_src_len
+            max_mel_len = max(max(mel_lens), 1) if max_mel_len is None else max_mel_len
+            ids = names if names is not None else [
+                f"{self.names[s]}{AU.suffix_of(self.texts[s], pos, m, r)}" for s, pos, m, _, r in p.tolist()]
+            plan_d = torch.from_numpy(p).to(self.device, non_blocking=True)
+        max_src_len, max_mel_len = int(max_src_len), int(max_mel_len)
+        if names is not None and len(names) != plan_d.shape[0]:
+            raise ValueError(f"DeviceCorpus.batch: {len(names)} names for {plan_d.shape[0]} plan rows")
+        o = None
+        if out is not None:
+            o = dict(zip(("audiotypes", "texts", "src_lens", "mels", "mel_lens", "energies", "kurtosises", "durations",
+                          "images"), [out[i] for i in (1, 2, 3, 5, 6, 8, 9, 10, 11)]))
+            st = self.last_status
+            if st is None or st.shape[0] != plan_d.shape[0]:
+                st = torch.empty(plan_d.shape[0], dtype=torch.int32, device=self.device)
+            o["status"] = st
+        o = ops.augment_batch(self.struct, plan_d, max_src_len, max_mel_len, self.height, self.cell, self.margin, out=o)
+        self.last_status = o["status"]
+        return (ids, o["audiotypes"], o["texts"], o["src_lens"], max_src_len, o["mels"], o["mel_lens"], max_mel_len,
+                o["energies"], o["kurtosises"], o["durations"], o["images"], None)

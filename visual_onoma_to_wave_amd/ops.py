@@ -1628,6 +1628,52 @@ def glyph_stretch(atlas, table, ids, src_lens, widths, cell, margin, W_out=None,
     return out
 
 
+AUGMENT_OUT = ("audiotypes", "texts", "src_lens", "mels", "mel_lens", "energies", "kurtosises", "durations", "images",
+               "status")
+
+
+def augment_batch(corpus, plan, T_src, T_mel, H, cell, margin, W_out=None, out=None):
+    """A padded training batch from a packed base corpus (``_lib.Corpus`` of device pointers; ``dataset.DeviceCorpus``
+    builds and owns one) and ``plan`` (B, 5) int32 on the GPU, rows ``src, pos, m, m_mel, r`` (include/vonoma.h states
+    the index maps) -> dict of ``AUGMENT_OUT``: audiotypes (B,) int64, texts (B, T_src) int64, src_lens (B,) int64,
+    mels (B, T_mel, n_mels) fp32, mel_lens (B,) fp32, energies / kurtosises / durations (B, T_src) fp32 (the first two
+    None when the corpus has none), images (B, 1, H, W_out) fp32 (W_out = T_src cell + 2 margin unless given; wider:
+    white), status (B,) int32.  The plan is never read on the host: a row out of range or over a cap comes out empty
+    with its reason in ``status`` (``_lib.AUG_*``).  vo_augment_batch: one launch on the current stream, graph-capturable.
+    ``out``: such a dict, every tensor of it written in full."""
+    if not (torch.is_tensor(plan) and plan.is_cuda and plan.dtype == torch.int32 and plan.dim() == 2
+            and plan.shape[1] == 5):
+        raise ValueError("augment_batch: plan must be an int32 (B, 5) tensor on the GPU")
+    _contig(plan, "plan")
+    B, T_src, T_mel, H, cell, margin = plan.shape[0], int(T_src), int(T_mel), int(H), int(cell), int(margin)
+    need = T_src * cell + 2 * margin
+    W_out = need if W_out is None else int(W_out)
+    if W_out < need:
+        raise ValueError(f"augment_batch: W_out {W_out} is below T_src * cell + 2 * margin = {need}")
+    f32, i64 = torch.float32, torch.int64
+    spec = {"audiotypes": ((B,), i64), "texts": ((B, T_src), i64), "src_lens": ((B,), i64),
+            "mels": ((B, T_mel, int(corpus.n_mels)), f32), "mel_lens": ((B,), f32),
+            "energies": ((B, T_src), f32) if corpus.ch_energy else None,
+            "kurtosises": ((B, T_src), f32) if corpus.ch_kurtosis else None,
+            "durations": ((B, T_src), f32), "images": ((B, 1, H, W_out), f32), "status": ((B,), torch.int32)}
+    if out is None:
+        out = {k: None if s is None else torch.empty(s[0], dtype=s[1], device=plan.device) for k, s in spec.items()}
+    for k, s in spec.items():
+        t = out.get(k)
+        if s is None:
+            if t is not None:
+                raise ValueError(f"augment_batch: out[{k!r}] given, but the corpus was packed without it")
+            continue
+        if not torch.is_tensor(t) or t.dtype != s[1] or tuple(t.shape) != s[0] or t.device != plan.device:
+            raise ValueError(f"augment_batch: out[{k!r}] must be {s[1]} {s[0]} on {plan.device}, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else t}")
+        _contig(t, k)
+    _lib.check(_lib.lib().vo_augment_batch(ctypes.byref(corpus), _ptr(plan), B, T_src, T_mel, H, cell, margin, W_out,
+                                           *[_ptr(out[k]) for k in AUGMENT_OUT], _stream(plan)),
+               "vo_augment_batch")
+    return out
+
+
 # ----------------------------------------------------------------------------- offline feature extraction
 
 def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):
