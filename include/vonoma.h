@@ -712,7 +712,26 @@ int vo_lrelu_mask_sum(const void* g, int ldg, int g_dtype, const void* ref, int 
  * visual_feature_extractor.py:40-47).  vo_bn_bwd: dgamma = sum dy xhat, dbeta = sum dy,
  * dx = gamma rstd (dy - dbeta / M - xhat dgamma / M) (dx in x's dtype).  Deterministic.  At C = 1
  * with M a multiple of the 16-byte vector the backward's sums and dx are formed in double (the workspace,
- * 8-byte aligned, holds them as doubles) and rounded once. */
+ * 8-byte aligned, holds them as doubles) and rounded once.
+ *
+ * vo_bn_route is the one place that decides which kernels the two calls launch, and with what geometry;
+ * both take their dispatch from it.  It launches nothing and makes no GPU call (a plan, like
+ * vo_conv1d_wgrad_plan).  dy_dtype < 0: the forward.  x, dy, out (y or dx): the call's pointers, NULL in
+ * a plan call meaning "aligned".  Copies min(n, VO_BN_ROUTE_FIELDS) fields into rec (NULL: none) and
+ * returns that count, or -1 with a zero record and vo_last_error for sizes / dtypes the calls refuse.
+ * Fields, in order: route (0 scalar kernels, 1 vectorised: C a multiple of the 16-byte vector V with
+ * C / V <= 256, 2 FLAT: C = 1 with M a multiple of V), V (elements per vector; 0 on the scalar route),
+ * CV (vector columns C / V; FLAT 1; scalar 0), RL (row lanes 256 / CV of a block; scalar 256 / CT), RB
+ * (rows -- FLAT: vectors -- per block), nb (row blocks = partials per channel), apply_blocks (grid of the
+ * apply kernel; vectorised: its thread count a multiple of CV), CT (channels per block of the scalar
+ * stats kernels, 1 or 64; 0 off the scalar route).
+ * Alignment rule: the vectorised and FLAT kernels issue 16-byte loads and stores, so they need x, dy and
+ * the output 16-byte aligned (a bf16 dy beside an fp32 x is read 8 bytes at a time: 8-byte aligned);
+ * a call whose pointers are not (a contiguous slice that starts inside an allocation) takes the scalar
+ * kernels, as does a bf16 x with an fp32 dy. */
+#define VO_BN_ROUTE_FIELDS 8
+int vo_bn_route(int M, int C, int x_dtype, int dy_dtype, const void* x, const void* dy, const void* out,
+                int32_t* rec, int n);
 int64_t vo_bn_workspace_size(int M, int C);
 int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const float* gamma, const float* beta, float eps,
                     float momentum, float* run_mean, float* run_var, int64_t* nbt, float* mean_rstd,

@@ -248,6 +248,8 @@ _SIGNATURES = {
                               c_void_p]),
     "vo_gan_reduce_grad": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
                                    c_void_p, c_int, c_void_p]),
+    "vo_bn_route": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32),
+                            c_int]),
     "vo_bn_workspace_size": (ctypes.c_int64, [c_int, c_int]),
     "vo_bn_train_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

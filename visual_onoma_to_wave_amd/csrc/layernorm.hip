@@ -110,7 +110,9 @@ static int ln_launch(const void* x, const void* res, const float* g, const float
 // across its waves through LDS, and writes one partial row [2][D] to the workspace; a second
 // kernel adds the partials in workgroup order (deterministic, no atomics).  A wave issues the
 // loads of all its rows before the first reduction (the row chain is latency-, not
-// bandwidth-bound at 16 rows per wave: 37 us at C2 -> see DESIGN.md).
+// bandwidth-bound at 16 rows per wave: 37 us at C2 -> see DESIGN.md).  A dead row (past the end, or
+// t >= lens[b]) loads row 0 in its place and drops what it loaded by selection: v = dy = 0, so its
+// statistics are finite (rstd = eps^-1/2), it adds exact zeros to the gamma / beta sums and writes 0.
 // Replaces the PyTorch autograd recomputation of LayerNorm backward (SubLayers.py:55,91,
 // Layers.py:25,28 under 04_train.py:128-141).  HBM-bound: reads x, res, gy, writes gh.
 constexpr int LN_BWD_RPW = 4;   // rows per wave
@@ -180,8 +182,8 @@ __global__ void __launch_bounds__(1024) layernorm_bwd_kernel(const TX* __restric
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        v[r][i + k] = q[k] + e[k];
-        dy[r][i + k] = ok ? d[k] : 0.f;
+        v[r][i + k] = ok ? q[k] + e[k] : 0.f;  // a dead row is inert by selection: the row 0 it loaded may
+        dy[r][i + k] = ok ? d[k] : 0.f;        // itself be a pad row that holds anything (0 * NaN is NaN)
       }
     }
   }
@@ -212,12 +214,12 @@ __global__ void __launch_bounds__(1024) layernorm_bwd_kernel(const TX* __restric
       accb[i] += dy[r][i];
     }
     const float m1 = wave_sum(s1) * (1.0f / D), m2 = wave_sum(s2) * (1.0f / D);
-    const float sc = live[r] ? rstd : 0.f;  // pad rows: zero gradient
 #pragma unroll
     for (int i = 0; i < NPL; i += 4) {
       float o[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = sc * (g[i + e] * dy[r][i + e] - m1 - v[r][i + e] * m2);
+      for (int e = 0; e < 4; ++e)  // pad rows: zero gradient
+        o[e] = live[r] ? rstd * (g[i + e] * dy[r][i + e] - m1 - v[r][i + e] * m2) : 0.f;
       if (gres) store4(gres + row * D + c0 + i, o);  // res: the gradient of x + res as it is
       if (dr.seed) {  // x: through its dropout
 #pragma unroll

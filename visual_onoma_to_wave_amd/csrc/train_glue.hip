@@ -1033,6 +1033,60 @@ static void bn_geometry(int M, int C, int* CT, int* RB, int* nb) {
   *nb = (M + *RB - 1) / *RB;
 }
 
+// The route of a forward (dy_dtype < 0) or backward call and its geometry: what vo_bn_route reports and
+// what vo_bn_train_fwd / vo_bn_bwd launch (include/vonoma.h).  Host arithmetic only.
+enum { BN_SCALAR = 0, BN_VEC = 1, BN_FLAT = 2 };
+struct BnRoute {
+  int route, V, CV, RL, RB, nb, apply_blocks, CT;
+};
+
+static bool bn_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }  // NULL: aligned
+
+static BnRoute bn_route(int M, int C, int x_dtype, int dy_dtype, const void* x, const void* dy, const void* out) {
+  BnRoute r{};
+  bool flat = false;
+  bool vec = bn_vec_ok(M, C, x_dtype, &flat);
+  // backward: x's vector width sets the layout; dy bf16 under fp32 x is read 4 per lane (8 bytes); bf16 x with
+  // fp32 dy has no vector form
+  if (dy_dtype >= 0 && x_dtype == VO_BF16 && dy_dtype == VO_F32) vec = false;
+  // 16-byte loads and stores of x and the output, 16- or 8-byte loads of dy
+  if (vec && !(bn_aligned(x, 16) && bn_aligned(out, 16) &&
+               bn_aligned(dy, x_dtype == VO_F32 && dy_dtype == VO_BF16 ? 8 : 16)))
+    vec = false;
+  if (vec) {
+    int rows;
+    r.route = flat ? BN_FLAT : BN_VEC;
+    r.V = x_dtype == VO_BF16 ? 8 : 4;
+    r.CV = flat ? 1 : C / r.V;
+    r.RL = 256 / r.CV;
+    bn_vec_geometry(M, C, x_dtype, flat, &rows, &r.RB, &r.nb);
+    r.apply_blocks = (int)bn_apply_blocks((int)((int64_t)M * C / r.V), r.CV);
+    return r;
+  }
+  r.route = BN_SCALAR;
+  bn_geometry(M, C, &r.CT, &r.RB, &r.nb);
+  r.RL = 256 / r.CT;
+  r.apply_blocks = (int)std::min<int64_t>(((int64_t)M * C + 255) / 256, 4096);
+  return r;
+}
+
+extern "C" int vo_bn_route(int M, int C, int x_dtype, int dy_dtype, const void* x, const void* dy, const void* out,
+                           int32_t* rec, int n) {
+  const int m = std::max(0, std::min(n, VO_BN_ROUTE_FIELDS));
+  if (rec) std::fill(rec, rec + m, 0);
+  const bool ok = M > 0 && C > 0 && (x_dtype == VO_F32 || x_dtype == VO_BF16) &&
+                  (dy_dtype < 0 || dy_dtype == VO_F32 || dy_dtype == VO_BF16);
+  if (!ok) {
+    vo_set_error("bn_route: M, C > 0, x fp32 / bf16, dy fp32 / bf16 or < 0 (forward)");
+    return VO_ERR_INVALID;
+  }
+  const BnRoute r = bn_route(M, C, x_dtype, dy_dtype, x, dy, out);
+  const int32_t f[VO_BN_ROUTE_FIELDS] = {r.route, r.V, r.CV, r.RL, r.RB, r.nb, r.apply_blocks, r.CT};
+  if (!rec) return 0;
+  std::copy(f, f + m, rec);
+  return m;
+}
+
 extern "C" int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const float* gamma, const float* beta,
                                float eps, float momentum, float* run_mean, float* run_var, int64_t* nbt,
                                float* mean_rstd, float* workspace, void* y, void* stream) {
@@ -1041,13 +1095,12 @@ extern "C" int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const flo
   VO_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "bn_train_fwd: gamma and beta together");
   VO_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "bn_train_fwd: running stats together");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  bool flat = false;
-  if (bn_vec_ok(M, C, dtype, &flat)) {
-    int rows, RBv, nbv;
-    bn_vec_geometry(M, C, dtype, flat, &rows, &RBv, &nbv);
-    const int V = dtype == VO_BF16 ? 8 : 4;
-    const int nvec = (int)((int64_t)M * C / V);
-    const unsigned ablk = bn_apply_blocks(nvec, flat ? 1 : C / V);
+  const BnRoute rt = bn_route(M, C, dtype, -1, x, nullptr, y);
+  if (rt.route != BN_SCALAR) {
+    const bool flat = rt.route == BN_FLAT;
+    const int rows = flat ? M / rt.V : M, RBv = rt.RB, nbv = rt.nb;
+    const int nvec = (int)((int64_t)M * C / rt.V);
+    const unsigned ablk = (unsigned)rt.apply_blocks;
 #define VO_BN_FWD(TX, FL)                                                                                          \
   do {                                                                                                             \
     hipLaunchKernelGGL((bn_stats_v_kernel<TX, FL>), dim3((unsigned)nbv), dim3(256), 0, st, (const TX*)x, rows, C, RBv, \
@@ -1065,8 +1118,7 @@ extern "C" int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const flo
 #undef VO_BN_FWD
     VO_RETURN_LAUNCH();
   }
-  int CT, RB, nb;
-  bn_geometry(M, C, &CT, &RB, &nb);
+  const int CT = rt.CT, RB = rt.RB, nb = rt.nb;
   const dim3 grid((unsigned)nb, (unsigned)((C + CT - 1) / CT));
   if (dtype == VO_F32) {
     if (CT == 1) hipLaunchKernelGGL((bn_stats_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, M, C, RB, workspace);
@@ -1078,7 +1130,7 @@ extern "C" int vo_bn_train_fwd(const void* x, int dtype, int M, int C, const flo
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, workspace, nb, C, eps,
                      momentum, mean_rstd, run_mean, run_var, nbt);
   const int64_t total = (int64_t)M * C;
-  const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+  const unsigned blocks = (unsigned)rt.apply_blocks;
   if (dtype == VO_F32)
     hipLaunchKernelGGL((bn_apply_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)x, total, C, mean_rstd,
                        gamma, beta, (float*)y);
@@ -1094,14 +1146,12 @@ extern "C" int vo_bn_bwd(const void* x, int x_dtype, const void* dy, int dy_dtyp
   VO_CHECK_ARG((x_dtype == VO_F32 || x_dtype == VO_BF16) && (dy_dtype == VO_F32 || dy_dtype == VO_BF16),
                "bn_bwd: dtypes");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  bool flat = false;
-  // vectorised: x's vector width sets the layout; dy bf16 under fp32 x is read 4 per lane (8 bytes)
-  if (bn_vec_ok(M, C, x_dtype, &flat) && !(x_dtype == VO_BF16 && dy_dtype == VO_F32)) {
-    int rows, RBv, nbv;
-    bn_vec_geometry(M, C, x_dtype, flat, &rows, &RBv, &nbv);
-    const int V = x_dtype == VO_BF16 ? 8 : 4;
-    const int nvec = (int)((int64_t)M * C / V);
-    const unsigned ablk = bn_apply_blocks(nvec, flat ? 1 : C / V);
+  const BnRoute rt = bn_route(M, C, x_dtype, dy_dtype, x, dy, dx);
+  if (rt.route != BN_SCALAR) {
+    const bool flat = rt.route == BN_FLAT;
+    const int rows = flat ? M / rt.V : M, RBv = rt.RB, nbv = rt.nb;
+    const int nvec = (int)((int64_t)M * C / rt.V);
+    const unsigned ablk = (unsigned)rt.apply_blocks;
     const float inv_m = 1.f / (float)M;
     // FLAT: the workspace as doubles -- BN_NB partial pairs, then the pair of totals
     VO_CHECK_ARG(!flat || reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "bn_bwd: workspace must be 8-byte aligned");
@@ -1129,8 +1179,7 @@ extern "C" int vo_bn_bwd(const void* x, int x_dtype, const void* dy, int dy_dtyp
 #undef VO_BNB_V
     VO_RETURN_LAUNCH();
   }
-  int CT, RB, nb;
-  bn_geometry(M, C, &CT, &RB, &nb);
+  const int CT = rt.CT, RB = rt.RB, nb = rt.nb;
   const dim3 grid((unsigned)nb, (unsigned)((C + CT - 1) / CT));
 #define VO_BNB_STATS(TX, TG)                                                                                     \
   do {                                                                                                           \
@@ -1149,7 +1198,7 @@ extern "C" int vo_bn_bwd(const void* x, int x_dtype, const void* dy, int dy_dtyp
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, workspace, nb, C,
                      dgamma, dbeta);
   const int64_t total = (int64_t)M * C;
-  const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
+  const unsigned blocks = (unsigned)rt.apply_blocks;
   const float inv_m = 1.f / (float)M;
 #define VO_BNB_APPLY(TX, TG)                                                                                      \
   hipLaunchKernelGGL((bn_bwd_apply_kernel<TX, TG>), dim3(blocks), dim3(256), 0, st, (const TX*)x, (const TG*)dy, total, \
@@ -1162,7 +1211,6 @@ extern "C" int vo_bn_bwd(const void* x, int x_dtype, const void* dy, int dy_dtyp
   VO_RETURN_LAUNCH();
 }
 
-// ---- glyph-encoder conv: x (N, H, W) fp32, w[10] = 3 x 3 kernel (row-major) + bias
 extern "C" int64_t vo_vfe_conv_workspace_size(int N, int H, int W) {
   const int64_t nb = ((int64_t)N * H * W + VC_TILE - 1) / VC_TILE;
   return nb * 10 * (int64_t)sizeof(float);

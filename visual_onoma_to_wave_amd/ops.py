@@ -1030,6 +1030,25 @@ def _rows(x):
     return x.numel() // C, C
 
 
+BN_ROUTE_FIELDS = ("route", "V", "CV", "RL", "RB", "nb", "apply_blocks", "CT")
+BN_SCALAR, BN_VEC, BN_FLAT = 0, 1, 2  # route
+
+
+def bn_route(M, C, x_dtype, dy_dtype=None, x=None, dy=None, out=None):
+    """The kernels ``bn_train_fwd`` (dy_dtype None) or ``bn_bwd`` would launch for an (M, C) input, as a dict over
+    BN_ROUTE_FIELDS (vo_bn_route in include/vonoma.h: the routing the launches themselves run).  x_dtype /
+    dy_dtype: torch dtypes.  x, dy, out: the call's tensors or addresses, only their alignment is looked at
+    (None: aligned).  Host only: nothing is launched and no tensor is read."""
+    def addr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr() if isinstance(t, torch.Tensor) else int(t))
+    rec = (ctypes.c_int32 * len(BN_ROUTE_FIELDS))()
+    n = _lib.lib().vo_bn_route(int(M), int(C), vo_dtype(x_dtype), -1 if dy_dtype is None else vo_dtype(dy_dtype),
+                               addr(x), addr(dy), addr(out), rec, len(BN_ROUTE_FIELDS))
+    if n != len(BN_ROUTE_FIELDS):
+        _lib.check(n if n < 0 else -1, "vo_bn_route")
+    return dict(zip(BN_ROUTE_FIELDS, (int(v) for v in rec)))
+
+
 def bn_train_fwd(x, gamma, beta, eps, momentum, running_mean=None, running_var=None, num_batches=None):
     """BatchNorm with batch statistics over channels-last x (..., C) or (N, 1, H, W) in fp32 / bf16:
     (y in x's dtype, mean_rstd (2C) fp32); running stats / num_batches updated in place when given."""
