@@ -1,4 +1,4 @@
-"""Checker of one LayerNorm or BatchNorm call (csrc/layernorm.hip, the BatchNorm part of csrc/train_glue.hip)
+"""Checker of one LayerNorm or BatchNorm call (csrc/layernorm.hip, csrc/batchnorm.hip)
 against float64, element by element, with guard bands around every buffer.
 
 A case is a dict (``ln_case`` / ``bn_case``).  ``make`` draws its operands on the CPU (bf16-exact where the
@@ -89,6 +89,9 @@ def lens_of(c):
     B, T, spec = c["B"], c["T"], c["lens"]
     if spec is None:
         return None
+    if isinstance(spec, (list, tuple)):  # the lengths themselves
+        assert len(spec) == B and all(0 <= n <= T for n in spec), spec
+        return list(spec)
     if spec == "full":
         return [T] * B
     if spec == "one":
@@ -120,6 +123,7 @@ def ln_case(entry, B, T, D, tx, tr, t3, *, res=True, p=None, gy2=False, gres=Non
              ill=ill)
     c["name"] = (f"ln_{entry}_{tx}_{c['tr']}_{t3}_D{D}_B{B}_T{T}" + ("" if res else "_nores") +
                  (f"_p{p}" if drop else "") + ("_gy2" if gy2 else "") + ("_y16" if dual and entry == "drop" else "") +
+                 ("_nogres" if entry == "bwd_ex" and not gres else "") +
                  (f"_{lens}" if lens else "") + ("" if profile == "plain" else f"_{profile}"))
     c["seed"] = (B * 1000003 + T * 1009 + D * 31 + len(c["name"]) * 7) % (2 ** 31)
     c["salt"] = 1 + c["seed"] % 97
@@ -166,9 +170,12 @@ def route_args(c, which, ptrs=None):
 
 def reached(c):
     """The kernel instantiations and edges a case exercises: LayerNorm (kernel, TX, TR, TY / TG, NPL, DUAL, drop,
-    gy2, gres); BatchNorm (kernel, template arguments...) from the declared records; edges as strings."""
+    gy2, gres) and the call itself, ("ln_call", entry) + its LN_ACCEPTS form; BatchNorm (kernel, template
+    arguments...) from the declared records; edges as strings."""
     out = set()
     if c["kind"] == "ln":
+        out.add(("ln_call", c["entry"], c["tx"], c["tr"], c["t3"], c["gy2"] if c["bwd"] else c["dual"],
+                 c["bwd"] and c["gres"]))
         npl = c["D"] // 64
         rows = c["B"] * c["T"]
         if c["bwd"]:
@@ -231,6 +238,57 @@ def reached(c):
     if not c["running"]:
         out.add("bn/no_running")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- accept tables
+
+_F, _H = "f32", "bf16"
+# entry -> the calls it takes, as (tx, tr, t3, aux, gres): the dtypes of x and res, of y (forward) or gy (backward);
+# aux: a y16 (forward) / a gy2 (backward) is passed; gres: the separate residual gradient is passed (bwd_ex's gh32,
+# bwd_drop's gres).  Arguments an entry does not have are held at what it implies: vo_layernorm has no y16,
+# vo_layernorm_dual an fp32 y and always a y16, vo_layernorm_bwd res of x's dtype, vo_layernorm_bwd_drop always a
+# gres.  Everything else ``ln_domain`` lists must be refused (the tables of csrc/layernorm.hip).
+LN_ACCEPTS = {
+    "fwd": {(_H, _H, _H, False, False), (_F, _F, _F, False, False), (_H, _H, _F, False, False),
+            (_F, _F, _H, False, False)},
+    "dual": {(_F, _F, _F, True, False), (_H, _H, _F, True, False), (_H, _F, _F, True, False)},
+    "drop": {(_H, _H, _H, False, False), (_F, _F, _F, False, False), (_H, _F, _F, False, False),
+             (_F, _F, _F, True, False), (_H, _F, _F, True, False)},
+    "bwd": {(_H, _H, _H, False, False), (_H, _H, _F, False, False), (_F, _F, _F, False, False),
+            (_F, _F, _H, False, False)},
+    # res of x's dtype: only without gy2 and gh32 (what vo_layernorm_bwd takes); bf16 x with fp32 res: any
+    "bwd_ex": {(_H, _H, _H, False, False), (_H, _H, _F, False, False), (_F, _F, _F, False, False),
+               (_F, _F, _H, False, False)} |
+              {(_H, _F, tg, gy2, gh32) for tg in (_F, _H) for gy2 in (False, True) for gh32 in (False, True)},
+    # res of x's dtype: only without gy2
+    "bwd_drop": {(_H, _H, _H, False, True), (_F, _F, _F, False, True)} |
+                {(_H, _F, tg, gy2, True) for tg in (_F, _H) for gy2 in (False, True)},
+}
+
+
+def ln_domain(entry):
+    """Every call of an entry over {f32, bf16} for each dtype argument it has, with and without each optional
+    pointer it has, in the form of LN_ACCEPTS."""
+    dts, tf = (_F, _H), (False, True)
+    if entry == "fwd":
+        return [(tx, tr, ty, False, False) for tx in dts for tr in dts for ty in dts]
+    if entry == "dual":
+        return [(tx, tr, _F, True, False) for tx in dts for tr in dts]
+    if entry == "drop":
+        return [(tx, tr, ty, y16, False) for tx in dts for tr in dts for ty in dts for y16 in tf]
+    if entry == "bwd":
+        return [(tx, tx, tg, False, False) for tx in dts for tg in dts]
+    if entry == "bwd_ex":
+        return [(tx, tr, tg, gy2, gh32) for tx in dts for tr in dts for tg in dts for gy2 in tf for gh32 in tf]
+    assert entry == "bwd_drop", entry
+    return [(tx, tr, tg, gy2, True) for tx in dts for tr in dts for tg in dts for gy2 in tf]
+
+
+def ln_instantiation(entry, combo):
+    """The kernel template arguments an accepted call launches, less NPL: forward (TX, TR, TY, DUAL), backward
+    (TX, TR, TG)."""
+    tx, tr, t3, aux, _ = combo
+    return ("layernorm_bwd_kernel", tx, tr, t3) if entry.startswith("bwd") else ("layernorm_kernel", tx, tr, t3, aux)
 
 
 # ---------------------------------------------------------------------------------------------- buffers

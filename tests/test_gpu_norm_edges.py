@@ -1,4 +1,4 @@
-"""LayerNorm (csrc/layernorm.hip) and BatchNorm (csrc/train_glue.hip) kernels element by element against float64
+"""LayerNorm (csrc/layernorm.hip) and BatchNorm (csrc/batchnorm.hip) kernels element by element against float64
 (tests/norm_check.py) at their reduction, dtype, lens and data edges.  Each case calls the C entry point with
 pointers into guarded buffers, then once more through the ops wrapper, and the two results must agree bit for
 bit.  CASES and REQUIRED are plain data (no GPU at import): tests/test_norm_check.py checks on the CPU that the
@@ -177,6 +177,11 @@ LN_CASES = _ln_forward() + [
     _bw("bwd_ex", _N17Z, 256, _H, _F, _F, gy2=True), _bw("bwd_ex", _N16, 512, _H, _F, _F, "tiny", gy2=True),
     _bw("bwd_ex", _N65, 256, _H, _F, _H, "constant"), _bw("bwd_ex", _N1B, 512, _H, _F, _H),
     _bw("bwd_ex", _N16F, 256, _H, _F, _H, "offset", gy2=True), _bw("bwd_ex", _N17, 512, _H, _F, _H, gy2=True),
+    # ... without gh32; and res of x's dtype without gy2 and gh32: the forms it shares with vo_layernorm_bwd
+    _bw("bwd_ex", _N17Z, 256, _H, _F, _F, gres=False), _bw("bwd_ex", _N1B, 512, _H, _F, _F, gy2=True, gres=False),
+    _bw("bwd_ex", _N16, 256, _H, _F, _H, gres=False), _bw("bwd_ex", _N17, 512, _H, _F, _H, gy2=True, gres=False),
+    _bw("bwd_ex", _N1B, 256, _H, _H, _H, gres=False), _bw("bwd_ex", _N17, 512, _H, _H, _F, gres=False),
+    _bw("bwd_ex", _N16, 256, _F, _F, _F, gres=False), _bw("bwd_ex", _N17Z, 512, _F, _F, _H, gres=False),
     # vo_layernorm_bwd_drop
     _bw("bwd_drop", _N17Z, 256, _H, _F, _F, p=0.1, gy2=True), _bw("bwd_drop", _N16, 512, _H, _F, _F, "offset", p=0.5),
     _bw("bwd_drop", _N48, 256, _H, _F, _H, "tiny", p=0.5), _bw("bwd_drop", _N17, 512, _H, _F, _H, p=0.0, gy2=True),
@@ -284,11 +289,12 @@ def _dt(t):
     return ops.vo_dtype(t)
 
 
-def _run_ln(c, m, d):
-    """The C entry point on pointers into the guarded device buffers ``d``; then the ops wrapper, bit for bit."""
-    from visual_onoma_to_wave_amd import _lib, ops
+def _call_ln(c, m, d, B=None, D=None):
+    """The C entry point of a LayerNorm case on pointers into the guarded device buffers ``d``; returns its status.
+    B / D: passed in place of the case's (a refused size: the buffers keep the case's)."""
+    from visual_onoma_to_wave_amd import _lib
     L = _lib.lib()
-    B, T, D = c["B"], c["T"], c["D"]
+    B, T, D = c["B"] if B is None else B, c["T"], c["D"] if D is None else D
 
     def v(name):
         return NC.view(m, name, d) if name in m["spec"] else None
@@ -297,48 +303,67 @@ def _run_ln(c, m, d):
         t = v(name)
         return None if t is None else ctypes.c_void_p(t.data_ptr())
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    x, res, lens, gamma = v("x"), v("res"), v("lens"), v("gamma")
-    x3 = x.view(B, T, D)
-    r3 = None if res is None else res.view(B, T, D)
+    x, res = v("x"), v("res")
     e = c["entry"]
     rdt = _dt(res) if res is not None else _dt(x)
     if e == "fwd":
-        _lib.check(L.vo_layernorm(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D, NC.EPS,
-                                  p("y"), _dt(v("y")), st), c["name"])
+        return L.vo_layernorm(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D, NC.EPS,
+                              p("y"), _dt(v("y")), st)
+    if e == "dual":
+        return L.vo_layernorm_dual(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D, NC.EPS,
+                                   p("y"), p("y16"), st)
+    if e == "drop":
+        return L.vo_layernorm_drop(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D, NC.EPS,
+                                   p("y"), _dt(v("y")), p("y16"), c["p"], p("seed"), c["salt"], st)
+    if e == "bwd":
+        return L.vo_layernorm_bwd(p("x"), p("res"), _dt(x), p("gy"), _dt(v("gy")), p("gamma"), p("lens"), B, T, D,
+                                  NC.EPS, p("gh"), p("dgamma"), p("dbeta"), p("ws"), st)
+    if e == "bwd_ex":
+        return L.vo_layernorm_bwd_ex(p("x"), _dt(x), p("res"), rdt, p("gy"), _dt(v("gy")), p("gy2"), p("gamma"),
+                                     p("lens"), B, T, D, NC.EPS, p("gh"), p("gres"), p("dgamma"), p("dbeta"),
+                                     p("ws"), st)
+    return L.vo_layernorm_bwd_drop(p("x"), _dt(x), p("res"), rdt, p("gy"), _dt(v("gy")), p("gy2"), p("gamma"),
+                                   p("lens"), B, T, D, NC.EPS, c["p"], p("seed"), c["salt"], p("gh"), p("gres"),
+                                   p("dgamma"), p("dbeta"), p("ws"), st)
+
+
+def _run_ln(c, m, d):
+    """The C entry point on pointers into the guarded device buffers ``d``; then the ops wrapper, bit for bit."""
+    from visual_onoma_to_wave_amd import _lib, ops
+    B, T, D = c["B"], c["T"], c["D"]
+
+    def v(name):
+        return NC.view(m, name, d) if name in m["spec"] else None
+    _lib.check(_call_ln(c, m, d), c["name"])
+    x, res, lens, gamma = v("x"), v("res"), v("lens"), v("gamma")
+    x3 = x.view(B, T, D)
+    r3 = None if res is None else res.view(B, T, D)
+    g2 = None if v("gy2") is None else v("gy2").view(B, T, D)
+    e = c["entry"]
+    if e == "fwd":
         w = dict(y=ops.layernorm(x3, gamma, v("beta"), res=r3, lens=lens, out_dtype=v("y").dtype, eps=NC.EPS))
     elif e == "dual":
-        _lib.check(L.vo_layernorm_dual(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D,
-                                       NC.EPS, p("y"), p("y16"), st), c["name"])
         w = dict(zip(("y", "y16"), ops.layernorm(x3, gamma, v("beta"), res=r3, lens=lens, out_dtype=torch.float32,
                                                  eps=NC.EPS, with_bf16=True)))
     elif e == "drop":
-        _lib.check(L.vo_layernorm_drop(p("x"), _dt(x), p("res"), rdt, p("gamma"), p("beta"), p("lens"), B, T, D,
-                                       NC.EPS, p("y"), _dt(v("y")), p("y16"), c["p"], p("seed"), c["salt"], st),
-                   c["name"])
         o = ops.layernorm_drop(x3, gamma, v("beta"), r3, c["p"], v("seed"), c["salt"], lens=lens,
                                with_bf16=c["dual"], eps=NC.EPS)
         w = dict(zip(("y", "y16"), o)) if c["dual"] else dict(y=o)
     elif e == "bwd":
-        _lib.check(L.vo_layernorm_bwd(p("x"), p("res"), _dt(x), p("gy"), _dt(v("gy")), p("gamma"), p("lens"), B, T, D,
-                                      NC.EPS, p("gh"), p("dgamma"), p("dbeta"), p("ws"), st), c["name"])
+        w = dict(zip(("gh", "dgamma", "dbeta"),
+                     ops.layernorm_bwd(x3, v("gy").view(B, T, D), gamma, res=r3, lens=lens, eps=NC.EPS)))
+    elif e == "bwd_ex" and c["tx"] == c["tr"]:  # ops.layernorm_bwd_ex takes bf16 x with fp32 res only: the same launch
         w = dict(zip(("gh", "dgamma", "dbeta"),
                      ops.layernorm_bwd(x3, v("gy").view(B, T, D), gamma, res=r3, lens=lens, eps=NC.EPS)))
     elif e == "bwd_ex":
-        _lib.check(L.vo_layernorm_bwd_ex(p("x"), _dt(x), p("res"), rdt, p("gy"), _dt(v("gy")), p("gy2"), p("gamma"),
-                                         p("lens"), B, T, D, NC.EPS, p("gh"), p("gres"), p("dgamma"), p("dbeta"),
-                                         p("ws"), st), c["name"])
-        g2 = v("gy2")
         w = dict(zip(("gh", "gres", "dgamma", "dbeta"),
-                     ops.layernorm_bwd_ex(x3, v("gy").view(B, T, D), gamma, r3, lens=lens,
-                                          gy2=None if g2 is None else g2.view(B, T, D), eps=NC.EPS)))
+                     ops.layernorm_bwd_ex(x3, v("gy").view(B, T, D), gamma, r3, lens=lens, gy2=g2, eps=NC.EPS)))
+        if not c["gres"]:  # the wrapper always passes a gh32
+            del w["gres"]
     else:
-        _lib.check(L.vo_layernorm_bwd_drop(p("x"), _dt(x), p("res"), rdt, p("gy"), _dt(v("gy")), p("gy2"), p("gamma"),
-                                           p("lens"), B, T, D, NC.EPS, c["p"], p("seed"), c["salt"], p("gh"),
-                                           p("gres"), p("dgamma"), p("dbeta"), p("ws"), st), c["name"])
-        g2 = v("gy2")
         w = dict(zip(("gh", "gres", "dgamma", "dbeta"),
                      ops.layernorm_bwd_drop(x3, v("gy").view(B, T, D), gamma, r3, c["p"], v("seed"), c["salt"],
-                                            lens=lens, gy2=None if g2 is None else g2.view(B, T, D), eps=NC.EPS)))
+                                            lens=lens, gy2=g2, eps=NC.EPS)))
     return w
 
 
@@ -397,3 +422,86 @@ def test_norm_case(c):
         assert torch.equal(NC._bits(t.reshape(-1)), NC._bits(NC.view(m, k, d).reshape(-1))), f"{c['name']}: wrapper {k}"
     m["bufs"] = {k: b.cpu() for k, b in d.items()}
     NC.verify(c, m, ref)
+
+
+# ---------------------------------------------------------------------------------------------- refusals
+
+_ENTRY_NAME = {"fwd": b"layernorm", "dual": b"layernorm_dual", "drop": b"layernorm_drop", "bwd": b"layernorm_bwd",
+               "bwd_ex": b"layernorm_bwd_ex", "bwd_drop": b"layernorm_bwd_drop"}
+VO_ERR_INVALID = -1  # include/vonoma.h
+
+
+def _refusal_case(entry, combo):
+    """B = 2, T = 3, D = 256, lens [3, 1]: one call of NC.ln_domain as a case (guards around every output)."""
+    tx, tr, t3, aux, gres = combo
+    bwd = entry.startswith("bwd")
+    return ln_case(entry, 2, 3, 256, tx, tr, t3, lens=(3, 1), p=0.1 if entry in ("drop", "bwd_drop") else None,
+                   gy2=bwd and aux, y16=(not bwd) and aux, gres=gres if bwd else None)
+
+
+def _assert_refused(c, m, d, **size):
+    """VO_ERR_INVALID, the error names the entry, and no buffer changed: outputs and guards keep their patterns."""
+    from visual_onoma_to_wave_amd import _lib
+    rc = _call_ln(c, m, d, **size)
+    err = _lib.lib().vo_last_error()
+    assert rc == VO_ERR_INVALID, (c["name"], size, rc)
+    assert err.startswith(_ENTRY_NAME[c["entry"]] + b":"), (c["name"], size, err)
+    torch.cuda.synchronize()
+    for k, b in d.items():
+        assert torch.equal(NC._bits(b.cpu()), NC._bits(m["bufs"][k])), (c["name"], size, k)
+
+
+@pytest.mark.gpu
+def test_layernorm_entries_refuse_every_call_outside_the_accept_table():
+    """Every entry over every dtype of each of its dtype arguments, with and without y16 / gy2 / gh32: what
+    NC.LN_ACCEPTS leaves out returns VO_ERR_INVALID before any launch; so do D = 128 and B = 0 on a call the entry
+    takes.  (The accepted calls are the cases above: tests/test_norm_check.py.)"""
+    dev = torch.device("cuda")
+    refused = 0
+    for entry in NC.LN_ENTRIES:
+        sized = False
+        for combo in NC.ln_domain(entry):
+            c = _refusal_case(entry, combo)
+            m = NC.make(c)
+            d = {k: b.to(dev) for k, b in m["bufs"].items()}
+            if combo not in NC.LN_ACCEPTS[entry]:
+                _assert_refused(c, m, d)
+                refused += 1
+            elif not sized:
+                _assert_refused(c, m, d, D=128)
+                _assert_refused(c, m, d, B=0)
+                sized = True
+        assert sized, entry
+    assert refused == 46
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wrapper", ["layernorm_bwd_ex", "layernorm_bwd_drop"])
+def test_backward_wrappers_check_gy_res_and_gy2_before_any_launch(wrapper, monkeypatch):
+    """An fp32 gy2 (the kernels read it as bf16: there is no dtype argument), and a gy2, gy or res of another shape:
+    ValueError before the library is even looked up."""
+    from visual_onoma_to_wave_amd import ops
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(5)
+    x, gy2 = (torch.randn(2, 3, 256, device=dev, generator=g).bfloat16() for _ in range(2))
+    res, gy = (torch.randn(2, 3, 256, device=dev, generator=g) for _ in range(2))
+    gamma = torch.ones(256, device=dev)
+    seed = torch.tensor([5], dtype=torch.int64, device=dev)
+
+    def call(**kw):
+        a = dict(x=x, gy=gy, res=res, gy2=gy2)
+        a.update(kw)
+        if wrapper == "layernorm_bwd_ex":
+            return ops.layernorm_bwd_ex(a["x"], a["gy"], gamma, a["res"], gy2=a["gy2"])
+        return ops.layernorm_bwd_drop(a["x"], a["gy"], gamma, a["res"], 0.1, seed, 3, gy2=a["gy2"])
+
+    def other(t):
+        return t[:, :2].contiguous()
+    assert all(t.shape == x.shape for t in call()[:2])  # the call the bad ones are one step from
+
+    def launched():
+        raise AssertionError("reached the library")
+    monkeypatch.setattr(ops._lib, "lib", launched)
+    for bad in (dict(gy2=gy2.float()), dict(gy2=other(gy2)), dict(gy=other(gy)), dict(res=other(res))):
+        with pytest.raises(ValueError, match=wrapper):
+            call(**bad)

@@ -1,4 +1,4 @@
-"""The round-2 training glue on HIP (train_glue.hip, disc.hip adjoints): forward and gradients
+"""The round-2 training glue on HIP (train_glue.hip, batchnorm.hip, disc.hip adjoints): forward and gradients
 against torch autograd of the reference formulation in fp64 on the CPU.
 
 * BatchNorm with batch statistics: PostNet's BatchNorm1d (scripts/transformer/Layers.py:129-137)

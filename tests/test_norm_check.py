@@ -184,6 +184,25 @@ def test_matrix_reaches_every_required_instantiation_and_edge():
     assert len({r for r in M.REQUIRED if isinstance(r, tuple) and r[0].startswith("bn_")}) == 43
 
 
+def test_every_accepted_layernorm_call_is_run_by_a_case():
+    """NC.LN_ACCEPTS against the GPU matrix: every call an entry takes -- that entry, those dtypes, with or without
+    y16 / gy2 / gh32 -- is the C call of some case of CASES (``reached``, at either NPL), so the accepted side of the
+    table is run and checked per element, and no case makes a call outside the table; every accepted call lies in
+    its entry's domain (the refusal test walks the rest); the table names 16 forward and 12 backward kernels."""
+    assert set(NC.LN_ACCEPTS) == set(NC.LN_ENTRIES)
+    ran = {r[1:] for c in M.LN_CASES for r in NC.reached(c) if isinstance(r, tuple) and r[0] == "ln_call"}
+    assert ran == {(e,) + combo for e, combos in NC.LN_ACCEPTS.items() for combo in combos}
+    inst = set()
+    for entry, combos in NC.LN_ACCEPTS.items():
+        assert combos <= set(NC.ln_domain(entry)), entry
+        for combo in combos:
+            assert (entry,) + combo in ran, (entry, combo)
+            inst |= {NC.ln_instantiation(entry, combo) + (npl,) for npl in (4, 8)}
+    assert sum(i[0] == "layernorm_kernel" for i in inst) == 16
+    assert sum(i[0] == "layernorm_bwd_kernel" for i in inst) == 12
+    assert sum(len(NC.ln_domain(e)) - len(NC.LN_ACCEPTS[e]) for e in NC.LN_ENTRIES) == 46
+
+
 def test_bn_route_alignment_rule_and_rejections():
     """Host side of vo_bn_route: 16-byte alignment of x, dy and the output on the vectorised and FLAT routes (8 bytes
     for a bf16 dy beside an fp32 x), null pointers meaning aligned, the bf16 x / fp32 dy exception, the clamped

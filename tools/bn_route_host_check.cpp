@@ -3,7 +3,7 @@
 // launches rely on.  Build and run (no GPU needed):
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
 //     -Xarch_host -fno-sanitize-recover=undefined -I include -I visual_onoma_to_wave_amd/csrc \
-//     tools/bn_route_host_check.cpp visual_onoma_to_wave_amd/csrc/train_glue.hip \
+//     tools/bn_route_host_check.cpp visual_onoma_to_wave_amd/csrc/batchnorm.hip \
 //     visual_onoma_to_wave_amd/csrc/vo_runtime.cpp -o visual_onoma_to_wave_amd/build/bn_route_host_check && \
 //     visual_onoma_to_wave_amd/build/bn_route_host_check
 #include <cstdint>
@@ -64,6 +64,13 @@ int main() {
                 CHECK(vo_bn_workspace_size(M, C) >= need);
               }
             }
+  // the workspace size in closed form: max(ceil(M / RB), 128) row blocks of 3 values per channel, RB = 8192 rows and
+  // doubles at C = 1, 512 rows and floats otherwise
+  for (int M : Ms)
+    for (int C : Cs) {
+      const int64_t RB = C == 1 ? 8192 : 512, nb = (M + RB - 1) / RB;
+      CHECK(vo_bn_workspace_size(M, C) == (nb > 128 ? nb : 128) * C * 3 * (C == 1 ? 8 : 4));
+    }
   // clamped copies, a null record, refused arguments
   int32_t rec[12];
   for (int i = 0; i < 12; ++i) rec[i] = 7;

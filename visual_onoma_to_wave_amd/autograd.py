@@ -14,7 +14,7 @@ The forward of every op is the same HIP kernel the inference path runs.  Backwar
   deterministic);
 * training-mode BatchNorm (PostNet, glyph encoder) forward / backward and the glyph encoder's
   kh x kw conv forward / backward: HIP -- ``vo_bn_*`` and ``vo_vfe_conv_*`` (3 x 3) / ``vo_vfe_conv_*_ex``
-  (train_glue.hip).
+  (batchnorm.hip, train_glue.hip).
 
 All functions take and return channels-last (B, T, C) activations.
 """

@@ -628,6 +628,8 @@ __global__ void __launch_bounds__(256) gan_multi_grad_kernel(GanArgs A, const fl
 }
 
 static bool v8_ok(const void* p, int64_t ld) { return p == nullptr || (((uintptr_t)p & 15) == 0 && ld % 8 == 0); }
+// vo_pack_dgrad_phase and the GAN reductions read every dtype value but VO_BF16 as fp32
+static int bf16_else_f32(int dtype) { return dtype == VO_BF16 ? VO_BF16 : VO_F32; }
 
 
 // leaky-ReLU backward mask: out = g * (ref > 0 ? 1 : slope) over a (rows x width) view with
@@ -726,16 +728,14 @@ extern "C" int vo_pack_dgrad_phase(const float* w, int Co, int cig, int K, int g
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = blocks_only ? (int64_t)J * cig * groups * (Co / groups) : (int64_t)J * ci_out * co_in;
   const int g = grid_for(n);
-#define VO_PDP(TD, B)                                                                                          \
-  hipLaunchKernelGGL((pack_dgrad_phase_kernel<TD, B>), dim3(g), dim3(256), 0, st, w, Co, cig, K, groups, S, k_r, \
-                     J, ci_out, co_in, (TD*)dst)
-  if (dst_dtype == VO_BF16) {
-    if (blocks_only) VO_PDP(bf16_t, true); else VO_PDP(bf16_t, false);
-  } else {
-    if (blocks_only) VO_PDP(float, true); else VO_PDP(float, false);
-  }
-#undef VO_PDP
-  VO_RETURN_LAUNCH();
+  return with_dtype(bf16_else_f32(dst_dtype), "pack_dgrad_phase", [&](auto td) {
+    return with_bool(blocks_only != 0, [&](auto blocks) {
+      using TD = typename decltype(td)::type;
+      hipLaunchKernelGGL((pack_dgrad_phase_kernel<TD, decltype(blocks)::value>), dim3(g), dim3(256), 0, st, w, Co, cig,
+                         K, groups, S, k_r, J, ci_out, co_in, (TD*)dst);
+      VO_RETURN_LAUNCH();
+    });
+  });
 }
 
 extern "C" int vo_pack_batch(int n, const VoPackJob* jobs, int dst_dtype, void* stream) {
@@ -904,28 +904,23 @@ extern "C" int vo_gan_reduce(int kind, const void* a, int lda, const void* b, in
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // at most 512 block partials (workspace: 512 floats), added in order by one wave (deterministic;
   // the grid-stride loop keeps the loads coalesced)
-  int g = std::min(grid_for(rows * width), 512);
-  if (width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb)) {
-    g = std::min(grid_for(rows * (width / 8)), 512);
-    const bool flat = lda == width && (!b || ldb == width);
-#define VO_GR(TA, F)                                                                                     \
-  hipLaunchKernelGGL((gan_reduce_v8_kernel<TA, F>), dim3(g), dim3(256), 0, st, kind, (const TA*)a, lda, \
-                     (const TA*)b, ldb, rows, width, workspace)
-    if (dtype == VO_BF16) {
-      if (flat) VO_GR(bf16_t, true); else VO_GR(bf16_t, false);
-    } else {
-      if (flat) VO_GR(float, true); else VO_GR(float, false);
-    }
-#undef VO_GR
-  } else if (dtype == VO_BF16) {
-    hipLaunchKernelGGL(gan_reduce_kernel<bf16_t>, dim3(g), dim3(256), 0, st, kind, (const bf16_t*)a, lda,
-                       (const bf16_t*)b, ldb, rows, width, workspace);
-  } else {
-    hipLaunchKernelGGL(gan_reduce_kernel<float>, dim3(g), dim3(256), 0, st, kind, (const float*)a, lda,
-                       (const float*)b, ldb, rows, width, workspace);
-  }
-  hipLaunchKernelGGL(gan_reduce_final_kernel, dim3(1), dim3(64), 0, st, workspace, g, out);
-  VO_RETURN_LAUNCH();
+  const bool v8 = width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb);
+  const bool flat = lda == width && (!b || ldb == width);
+  const int g = std::min(grid_for(rows * (v8 ? width / 8 : width)), 512);
+  return with_dtype(bf16_else_f32(dtype), "gan_reduce", [&](auto ta) {
+    using TA = typename decltype(ta)::type;
+    if (v8)
+      with_bool(flat, [&](auto fl) {
+        hipLaunchKernelGGL((gan_reduce_v8_kernel<TA, decltype(fl)::value>), dim3(g), dim3(256), 0, st, kind,
+                           (const TA*)a, lda, (const TA*)b, ldb, rows, width, workspace);
+        return 0;
+      });
+    else
+      hipLaunchKernelGGL(gan_reduce_kernel<TA>, dim3(g), dim3(256), 0, st, kind, (const TA*)a, lda, (const TA*)b, ldb,
+                         rows, width, workspace);
+    hipLaunchKernelGGL(gan_reduce_final_kernel, dim3(1), dim3(64), 0, st, workspace, g, out);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 // the term table of one launch: the block grid of each term as the single-term entry points size it
@@ -1001,72 +996,63 @@ extern "C" int vo_gan_reduce_grad(int kind, const void* a, int lda, const void* 
   VO_CHECK_ARG(a && ga && scale && kind >= 0 && kind <= 2 && (kind != 0 || b), "gan_reduce_grad: bad arguments");
   VO_CHECK_ARG(rows > 0 && width > 0 && lda >= width && ldg >= width, "gan_reduce_grad: bad shape");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb) && v8_ok(ga, ldg)) {
-    const int gv = grid_for(rows * (width / 8));
-    const bool flat = lda == width && (!b || ldb == width) && ldg == width;
-#define VO_GG(TA, F)                                                                                           \
-  hipLaunchKernelGGL((gan_reduce_grad_v8_kernel<TA, F>), dim3(gv), dim3(256), 0, st, kind, (const TA*)a, lda, \
-                     (const TA*)b, ldb, rows, width, scale, (TA*)ga, ldg)
-    if (dtype == VO_BF16) {
-      if (flat) VO_GG(bf16_t, true); else VO_GG(bf16_t, false);
-    } else {
-      if (flat) VO_GG(float, true); else VO_GG(float, false);
-    }
-#undef VO_GG
+  const bool v8 = width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb) && v8_ok(ga, ldg);
+  const bool flat = lda == width && (!b || ldb == width) && ldg == width;
+  const int g = grid_for(rows * (v8 ? width / 8 : width));
+  return with_dtype(bf16_else_f32(dtype), "gan_reduce_grad", [&](auto ta) {
+    using TA = typename decltype(ta)::type;
+    if (v8)
+      with_bool(flat, [&](auto fl) {
+        hipLaunchKernelGGL((gan_reduce_grad_v8_kernel<TA, decltype(fl)::value>), dim3(g), dim3(256), 0, st, kind,
+                           (const TA*)a, lda, (const TA*)b, ldb, rows, width, scale, (TA*)ga, ldg);
+        return 0;
+      });
+    else
+      hipLaunchKernelGGL(gan_reduce_grad_kernel<TA>, dim3(g), dim3(256), 0, st, kind, (const TA*)a, lda, (const TA*)b,
+                         ldb, rows, width, scale, (TA*)ga, ldg);
     VO_RETURN_LAUNCH();
-  }
-  const int g = grid_for(rows * width);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(gan_reduce_grad_kernel<bf16_t>, dim3(g), dim3(256), 0, st, kind, (const bf16_t*)a, lda,
-                       (const bf16_t*)b, ldb, rows, width, scale, (bf16_t*)ga, ldg);
-  else
-    hipLaunchKernelGGL(gan_reduce_grad_kernel<float>, dim3(g), dim3(256), 0, st, kind, (const float*)a, lda,
-                       (const float*)b, ldb, rows, width, scale, (float*)ga, ldg);
-  VO_RETURN_LAUNCH();
+  });
+}
+
+// The three leaky-ReLU mask entries after their own checks: every (g, ref) dtype pair, named once.  add == NULL:
+// out = mask(g), in 8-element vectors where the rows allow (v8; FLAT when no row is padded), else per element;
+// add != NULL (v8 only, the caller checked): ADD 1, or ADD 2 when presum.
+static int lrelu_mask_launch(const char* who, const void* g, int ldg, int g_dtype, const void* ref, int ldr,
+                             int ref_dtype, const void* add, int lda, bool presum, int64_t rows, int width,
+                             float slope, void* out, int ldo, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool v8 = width % 8 == 0 && v8_ok(g, ldg) && v8_ok(ref, ldr) && v8_ok(out, ldo) && v8_ok(add, lda);
+  const bool flat = ldg == width && ldr == width && ldo == width;
+  const int gr = grid_for(rows * (v8 ? width / 8 : width));
+  return with_dtypes(g_dtype, ref_dtype, who, [&](auto tg, auto tr) {
+    using TG = typename decltype(tg)::type;
+    using TR = typename decltype(tr)::type;
+    auto v8_form = [&](auto fl, auto mode) {
+      hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, decltype(fl)::value, decltype(mode)::value>), dim3(gr),
+                         dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo,
+                         (const TG*)add, lda);
+      return 0;
+    };
+    using std::integral_constant;
+    if (!v8)
+      hipLaunchKernelGGL((lrelu_mask_kernel<TG, TR>), dim3(gr), dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref,
+                         ldr, rows, width, slope, (TG*)out, ldo);
+    else if (!add)
+      with_bool(flat, [&](auto fl) { return v8_form(fl, integral_constant<int, 0>{}); });
+    else if (presum)
+      v8_form(std::false_type{}, integral_constant<int, 2>{});
+    else
+      v8_form(std::false_type{}, integral_constant<int, 1>{});
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_lrelu_mask(const void* g, int ldg, int g_dtype, const void* ref, int ldr, int ref_dtype,
                              int64_t rows, int width, float slope, void* out, int ldo, void* stream) {
   VO_CHECK_ARG(g && ref && out, "lrelu_mask: null pointer");
   VO_CHECK_ARG(rows > 0 && width > 0 && ldg >= width && ldr >= width && ldo >= width, "lrelu_mask: bad shape");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (width % 8 == 0 && v8_ok(g, ldg) && v8_ok(ref, ldr) && v8_ok(out, ldo)) {
-    const int gv = grid_for(rows * (width / 8));
-    const bool flat = ldg == width && ldr == width && ldo == width;
-#define VO_LM8(TG, TR)                                                                                             \
-  do {                                                                                                             \
-    if (flat)                                                                                                      \
-      hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, true>), dim3(gv), dim3(256), 0, st, (const TG*)g, ldg,      \
-                         (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo);                                  \
-    else                                                                                                           \
-      hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, false>), dim3(gv), dim3(256), 0, st, (const TG*)g, ldg,     \
-                         (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo);                                  \
-  } while (0)
-    if (g_dtype == VO_BF16 && ref_dtype == VO_BF16) VO_LM8(bf16_t, bf16_t);
-    else if (g_dtype == VO_F32 && ref_dtype == VO_F32) VO_LM8(float, float);
-    else if (g_dtype == VO_BF16 && ref_dtype == VO_F32) VO_LM8(bf16_t, float);
-    else if (g_dtype == VO_F32 && ref_dtype == VO_BF16) VO_LM8(float, bf16_t);
-    else {
-      vo_set_error("lrelu_mask: bad dtypes");
-      return VO_ERR_INVALID;
-    }
-#undef VO_LM8
-    VO_RETURN_LAUNCH();
-  }
-  const int gr = grid_for(rows * width);
-#define VO_LM(TG, TR)                                                                                          \
-  hipLaunchKernelGGL((lrelu_mask_kernel<TG, TR>), dim3(gr), dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref, \
-                     ldr, rows, width, slope, (TG*)out, ldo)
-  if (g_dtype == VO_BF16 && ref_dtype == VO_BF16) VO_LM(bf16_t, bf16_t);
-  else if (g_dtype == VO_F32 && ref_dtype == VO_F32) VO_LM(float, float);
-  else if (g_dtype == VO_BF16 && ref_dtype == VO_F32) VO_LM(bf16_t, float);
-  else if (g_dtype == VO_F32 && ref_dtype == VO_BF16) VO_LM(float, bf16_t);
-  else {
-    vo_set_error("lrelu_mask: bad dtypes");
-    return VO_ERR_INVALID;
-  }
-#undef VO_LM
-  VO_RETURN_LAUNCH();
+  return lrelu_mask_launch("lrelu_mask", g, ldg, g_dtype, ref, ldr, ref_dtype, nullptr, 0, false, rows, width, slope,
+                           out, ldo, stream);
 }
 
 static int lrelu_mask_add_run(const void* g, int ldg, int g_dtype, const void* ref, int ldr, int ref_dtype,
@@ -1077,25 +1063,8 @@ static int lrelu_mask_add_run(const void* g, int ldg, int g_dtype, const void* r
                "lrelu_mask_add: bad shape");
   VO_CHECK_ARG(width % 8 == 0 && v8_ok(g, ldg) && v8_ok(ref, ldr) && v8_ok(out, ldo) && v8_ok(add, lda),
                "lrelu_mask_add: rows must be 8-element vectors, 16-byte aligned");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int gv = grid_for(rows * (width / 8));
-#define VO_LMA(TG, TR)                                                                                                 \
-  if (presum)                                                                                                          \
-    hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, false, 2>), dim3(gv), dim3(256), 0, st, (const TG*)g, ldg,         \
-                       (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo, (const TG*)add, lda);                   \
-  else                                                                                                                 \
-    hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, false, 1>), dim3(gv), dim3(256), 0, st, (const TG*)g, ldg,         \
-                       (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo, (const TG*)add, lda)
-  if (g_dtype == VO_BF16 && ref_dtype == VO_BF16) VO_LMA(bf16_t, bf16_t);
-  else if (g_dtype == VO_F32 && ref_dtype == VO_F32) VO_LMA(float, float);
-  else if (g_dtype == VO_BF16 && ref_dtype == VO_F32) VO_LMA(bf16_t, float);
-  else if (g_dtype == VO_F32 && ref_dtype == VO_BF16) VO_LMA(float, bf16_t);
-  else {
-    vo_set_error("lrelu_mask_add: bad dtypes");
-    return VO_ERR_INVALID;
-  }
-#undef VO_LMA
-  VO_RETURN_LAUNCH();
+  return lrelu_mask_launch("lrelu_mask_add", g, ldg, g_dtype, ref, ldr, ref_dtype, add, lda, presum, rows, width,
+                           slope, out, ldo, stream);
 }
 
 extern "C" int vo_lrelu_mask_add(const void* g, int ldg, int g_dtype, const void* ref, int ldr, int ref_dtype,

@@ -86,20 +86,45 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TX* __restrict__ x
   }
 }
 
-template <typename TX, typename TR, typename TY, bool DUAL = false>
-static int ln_launch(const void* x, const void* res, const float* g, const float* bt, const int32_t* lens,
-                     int B, int T, int D, float eps, void* y, hipStream_t st, void* y16 = nullptr,
-                     LnDrop dr = LnDrop{nullptr, 0u, 0u, 1.f}) {
-  const int64_t rows = (int64_t)B * T;
-  dim3 grid((unsigned)((rows + 3) / 4));
-  if (D == 256)
-    hipLaunchKernelGGL((layernorm_kernel<TX, TR, TY, 4, DUAL>), grid, dim3(256), 0, st, (const TX*)x,
-                       (const TR*)res, g, bt, lens, B, T, eps, (TY*)y, (bf16_t*)y16, dr);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<TX, TR, TY, 8, DUAL>), grid, dim3(256), 0, st, (const TX*)x,
-                       (const TR*)res, g, bt, lens, B, T, eps, (TY*)y, (bf16_t*)y16, dr);
-  VO_RETURN_LAUNCH();
-}
+// ---- host: each direction has one call struct the entries fill, one list of rows -- a row is one compiled kernel
+// (at NPL 4 and 8: D = 256 / 512) and the entries that may launch it -- and one launcher that walks the rows.  A
+// call that matches no row of its entry is refused before any HIP call; nothing but the rows is instantiated.
+enum : unsigned { LN_PLAIN = 1, LN_DUAL = 2, LN_DROP = 4 };      // forward entries
+enum : unsigned { LN_BWD = 1, LN_BWD_EX = 2, LN_BWD_DROP = 4 };  // backward entries
+constexpr LnDrop LN_NO_DROP{nullptr, 0u, 0u, 1.f};
+template <typename T> constexpr int ln_dtype = std::is_same_v<T, bf16_t> ? VO_BF16 : VO_F32;
+
+// res_dtype: x's when res == NULL; y16 != NULL: the DUAL kernels; dr.seed != NULL: dropout of x
+struct LnFwdCall {
+  const char* who;  // the entry's name in errors
+  const void *x, *res;
+  int x_dtype, res_dtype;
+  const float *gamma, *beta;
+  const int32_t* lens;
+  int B, T, D;
+  float eps;
+  void *y, *y16;
+  int y_dtype;
+  LnDrop dr;
+  hipStream_t st;
+};
+
+template <typename TX, typename TR, typename TY, bool DUAL, unsigned ENTRIES>
+struct LnFwdRow {
+  static int run(const LnFwdCall& c, unsigned entry) {  // VO_NOT_HANDLED: not this row's call
+    if (!(ENTRIES & entry) || c.x_dtype != ln_dtype<TX> || c.res_dtype != ln_dtype<TR> ||
+        c.y_dtype != ln_dtype<TY> || (c.y16 != nullptr) != DUAL)
+      return VO_NOT_HANDLED;
+    const dim3 grid((unsigned)(((int64_t)c.B * c.T + 3) / 4));
+    auto go = [&](auto npl) {
+      hipLaunchKernelGGL((layernorm_kernel<TX, TR, TY, decltype(npl)::value, DUAL>), grid, dim3(256), 0, c.st,
+                         (const TX*)c.x, (const TR*)c.res, c.gamma, c.beta, c.lens, c.B, c.T, c.eps, (TY*)c.y,
+                         (bf16_t*)c.y16, c.dr);
+    };
+    if (c.D == 256) go(std::integral_constant<int, 4>{}); else go(std::integral_constant<int, 8>{});
+    VO_RETURN_LAUNCH();
+  }
+};
 
 // ---------------------------------------------------------------- backward (training, C4)
 // Gradient of y = pad ? 0 : LN(x + res) * gamma + beta (the forward above).  One wave per row
@@ -278,179 +303,153 @@ __global__ void __launch_bounds__(1024) ln_partial_sum_kernel(const float* __res
   }
 }
 
-template <typename TX, typename TG, typename TR = TX>
-static int ln_bwd_launch(const void* x, const void* res, const void* gy, const float* g, const int32_t* lens,
-                         int B, int T, int D, float eps, void* gh, float* dgamma, float* dbeta, float* ws,
-                         hipStream_t st, const void* gy2 = nullptr, void* gres = nullptr,
-                         LnDrop dr = LnDrop{nullptr, 0u, 0u, 1.f}) {
-  const int64_t rows = (int64_t)B * T;
-  const int nblk = (int)((rows + LN_BWD_NW * LN_BWD_RPW - 1) / (LN_BWD_NW * LN_BWD_RPW));
-  if (D == 256)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TR, TG, 4>), dim3(nblk), dim3(1024), 0, st, (const TX*)x,
-                       (const TR*)res, (const TG*)gy, (const bf16_t*)gy2, g, lens, B, T, eps, (TX*)gh, (TR*)gres,
-                       ws, dr);
-  else
-    hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TR, TG, 8>), dim3(nblk), dim3(1024), 0, st, (const TX*)x,
-                       (const TR*)res, (const TG*)gy, (const bf16_t*)gy2, g, lens, B, T, eps, (TX*)gh, (TR*)gres,
-                       ws, dr);
-  hipLaunchKernelGGL(ln_partial_sum_kernel, dim3((2 * D + 63) / 64), dim3(1024), 0, st, (const float*)ws, nblk,
-                     2 * D, dgamma, dbeta);
-  VO_RETURN_LAUNCH();
+// gy2 (bf16, optional): the gradient of the y16 copy; gres (optional, res's dtype): the gradient of res beside gh
+// (vo_layernorm_bwd_ex's gh32, vo_layernorm_bwd_drop's gres); dr.seed != NULL: the forward's dropout of x
+struct LnBwdCall {
+  const char* who;
+  const void *x, *res, *gy, *gy2;
+  int x_dtype, res_dtype, gy_dtype;
+  const float* gamma;
+  const int32_t* lens;
+  int B, T, D;
+  float eps;
+  void *gh, *gres;
+  float *dgamma, *dbeta, *ws;
+  LnDrop dr;
+  hipStream_t st;
+};
+
+// ALWAYS: the entries that reach the row whatever gy2 / gres are; BARE: those that reach it only without a gy2
+// (and vo_layernorm_bwd_ex only without its gh32 as well: the forms vo_layernorm_bwd takes, passed through)
+template <typename TX, typename TR, typename TG, unsigned ALWAYS, unsigned BARE = 0>
+struct LnBwdRow {
+  static int run(const LnBwdCall& c, unsigned entry) {
+    const bool bare = c.gy2 == nullptr && (entry != LN_BWD_EX || c.gres == nullptr);
+    if (!((ALWAYS | (bare ? BARE : 0u)) & entry) || c.x_dtype != ln_dtype<TX> || c.res_dtype != ln_dtype<TR> ||
+        c.gy_dtype != ln_dtype<TG>)
+      return VO_NOT_HANDLED;
+    const int nblk = (int)(((int64_t)c.B * c.T + LN_BWD_NW * LN_BWD_RPW - 1) / (LN_BWD_NW * LN_BWD_RPW));
+    auto go = [&](auto npl) {
+      hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TR, TG, decltype(npl)::value>), dim3(nblk), dim3(1024), 0, c.st,
+                         (const TX*)c.x, (const TR*)c.res, (const TG*)c.gy, (const bf16_t*)c.gy2, c.gamma, c.lens,
+                         c.B, c.T, c.eps, (TX*)c.gh, (TR*)c.gres, c.ws, c.dr);
+    };
+    if (c.D == 256) go(std::integral_constant<int, 4>{}); else go(std::integral_constant<int, 8>{});
+    hipLaunchKernelGGL(ln_partial_sum_kernel, dim3((2 * c.D + 63) / 64), dim3(1024), 0, c.st, (const float*)c.ws,
+                       nblk, 2 * c.D, c.dgamma, c.dbeta);
+    VO_RETURN_LAUNCH();
+  }
+};
+
+// the checks every entry shares (the dropout counter is the flat element index, 32 bits), then the first row that fits
+template <typename... Rows, typename Call>
+static int ln_run(const Call& c, unsigned entry, bool ptrs) {
+  VO_CHECK_ARG(ptrs, "%s: null pointer", c.who);
+  VO_CHECK_ARG(c.D == 256 || c.D == 512, "%s: D=%d unsupported (256 or 512)", c.who, c.D);
+  VO_CHECK_ARG(c.B > 0 && c.T > 0 && (!c.dr.seed || (int64_t)c.B * c.T * c.D < (1LL << 32)),
+               "%s: empty, or > 2^32 elements under dropout", c.who);
+  int rc = VO_NOT_HANDLED;
+  if ((((rc = Rows::run(c, entry)) != VO_NOT_HANDLED) || ...)) return rc;
+  vo_set_error("%s: unsupported dtype combination", c.who);
+  return VO_ERR_INVALID;
+}
+
+using F = float; using H = bf16_t;
+
+static int ln_forward(const LnFwdCall& c, unsigned entry) {  // rows: TX, TR, TY, DUAL (the call has a y16), entries
+  return ln_run<LnFwdRow<H, H, H, false, LN_PLAIN | LN_DROP>,
+                LnFwdRow<F, F, F, false, LN_PLAIN | LN_DROP>,
+                LnFwdRow<H, H, F, false, LN_PLAIN>,
+                LnFwdRow<F, F, H, false, LN_PLAIN>,
+                LnFwdRow<H, F, F, false, LN_DROP>,
+                LnFwdRow<F, F, F, true, LN_DUAL | LN_DROP>,
+                LnFwdRow<H, H, F, true, LN_DUAL>,
+                LnFwdRow<H, F, F, true, LN_DUAL | LN_DROP>>(  // round 6: bf16 sublayer output, fp32 residual stream
+      c, entry, c.x && c.gamma && c.beta && c.y);
+}
+
+static int ln_backward(const LnBwdCall& c, unsigned entry) {  // rows: TX, TR, TG, ALWAYS, BARE
+  return ln_run<LnBwdRow<H, H, H, LN_BWD, LN_BWD_EX | LN_BWD_DROP>,
+                LnBwdRow<H, H, F, LN_BWD, LN_BWD_EX>,
+                LnBwdRow<F, F, F, LN_BWD, LN_BWD_EX | LN_BWD_DROP>,
+                LnBwdRow<F, F, H, LN_BWD, LN_BWD_EX>,
+                LnBwdRow<H, F, F, LN_BWD_EX | LN_BWD_DROP>,  // round 6: the mixed decoder's fp32 residual stream
+                LnBwdRow<H, F, H, LN_BWD_EX | LN_BWD_DROP>>(
+      c, entry, c.x && c.gy && c.gamma && c.gh && c.dgamma && c.dbeta && c.ws);
 }
 
 }  // namespace vo
 
 using namespace vo;
 
+// ---- the entries: fill the call, check what only this entry asks, hand it to ln_forward / ln_backward
 extern "C" int vo_layernorm(const void* x, int x_dtype, const void* res, int res_dtype, const float* gamma,
                             const float* beta, const int32_t* lens, int B, int T, int D, float eps, void* y,
                             int y_dtype, void* stream) {
-  VO_CHECK_ARG(x && gamma && beta && y, "layernorm: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0, "layernorm: empty");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!res) res_dtype = x_dtype;
-#define VO_LN(TX, TR, TY) return ln_launch<TX, TR, TY>(x, res, gamma, beta, lens, B, T, D, eps, y, st)
-  if (x_dtype == VO_BF16 && res_dtype == VO_BF16 && y_dtype == VO_BF16) VO_LN(bf16_t, bf16_t, bf16_t);
-  if (x_dtype == VO_F32 && res_dtype == VO_F32 && y_dtype == VO_F32) VO_LN(float, float, float);
-  if (x_dtype == VO_BF16 && res_dtype == VO_BF16 && y_dtype == VO_F32) VO_LN(bf16_t, bf16_t, float);
-  if (x_dtype == VO_F32 && res_dtype == VO_F32 && y_dtype == VO_BF16) VO_LN(float, float, bf16_t);
-#undef VO_LN
-  vo_set_error("layernorm: unsupported dtype combination");
-  return VO_ERR_INVALID;
+  const LnFwdCall c{"layernorm", x, res, x_dtype, res ? res_dtype : x_dtype, gamma, beta, lens, B, T, D, eps, y,
+                    nullptr, y_dtype, LN_NO_DROP, (hipStream_t)stream};
+  return ln_forward(c, LN_PLAIN);
 }
 
 extern "C" int vo_layernorm_dual(const void* x, int x_dtype, const void* res, int res_dtype, const float* gamma,
                                  const float* beta, const int32_t* lens, int B, int T, int D, float eps, void* y,
                                  void* y16, void* stream) {
-  VO_CHECK_ARG(x && gamma && beta && y && y16, "layernorm_dual: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm_dual: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0, "layernorm_dual: empty");
+  VO_CHECK_ARG(y16, "layernorm_dual: null pointer");
   VO_CHECK_ARG(y16 != y && y16 != x && y16 != res, "layernorm_dual: y16 must not alias x, res or y");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!res) res_dtype = x_dtype;
-  if (x_dtype == VO_F32 && res_dtype == VO_F32)
-    return ln_launch<float, float, float, true>(x, res, gamma, beta, lens, B, T, D, eps, y, st, y16);
-  if (x_dtype == VO_BF16 && res_dtype == VO_BF16)
-    return ln_launch<bf16_t, bf16_t, float, true>(x, res, gamma, beta, lens, B, T, D, eps, y, st, y16);
-  if (x_dtype == VO_BF16 && res_dtype == VO_F32)  // round 6: bf16 sublayer output + fp32 residual stream (training)
-    return ln_launch<bf16_t, float, float, true>(x, res, gamma, beta, lens, B, T, D, eps, y, st, y16);
-  vo_set_error("layernorm_dual: unsupported dtype combination (fp32 y; fp32 / fp32, bf16 / bf16 or bf16 / fp32 x / res)");
-  return VO_ERR_INVALID;
+  const LnFwdCall c{"layernorm_dual", x, res, x_dtype, res ? res_dtype : x_dtype, gamma, beta, lens, B, T, D, eps, y,
+                    y16, VO_F32, LN_NO_DROP, (hipStream_t)stream};
+  return ln_forward(c, LN_DUAL);
 }
 
 extern "C" int64_t vo_layernorm_bwd_workspace_size(int B, int T, int D) {
-  const int64_t rows = (int64_t)B * T;
-  return ((rows + LN_BWD_NW * LN_BWD_RPW - 1) / (LN_BWD_NW * LN_BWD_RPW)) * 2 * D * (int64_t)sizeof(float);
+  return (((int64_t)B * T + LN_BWD_NW * LN_BWD_RPW - 1) / (LN_BWD_NW * LN_BWD_RPW)) * 2 * D * (int64_t)sizeof(float);
 }
 
 extern "C" int vo_layernorm_bwd(const void* x, const void* res, int x_dtype, const void* gy, int gy_dtype,
                                 const float* gamma, const int32_t* lens, int B, int T, int D, float eps, void* gh,
                                 float* dgamma, float* dbeta, void* workspace, void* stream) {
-  VO_CHECK_ARG(x && gy && gamma && gh && dgamma && dbeta && workspace, "layernorm_bwd: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm_bwd: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0, "layernorm_bwd: empty");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* ws = (float*)workspace;
-#define VO_LNB(TX, TG) return ln_bwd_launch<TX, TG>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st)
-  if (x_dtype == VO_BF16 && gy_dtype == VO_BF16) VO_LNB(bf16_t, bf16_t);
-  if (x_dtype == VO_BF16 && gy_dtype == VO_F32) VO_LNB(bf16_t, float);
-  if (x_dtype == VO_F32 && gy_dtype == VO_F32) VO_LNB(float, float);
-  if (x_dtype == VO_F32 && gy_dtype == VO_BF16) VO_LNB(float, bf16_t);
-#undef VO_LNB
-  vo_set_error("layernorm_bwd: unsupported dtype combination");
-  return VO_ERR_INVALID;
+  const LnBwdCall c{"layernorm_bwd", x, res, gy, nullptr, x_dtype, x_dtype, gy_dtype, gamma, lens, B, T, D, eps, gh,
+                    nullptr, dgamma, dbeta, (float*)workspace, LN_NO_DROP, (hipStream_t)stream};
+  return ln_backward(c, LN_BWD);
 }
 
 extern "C" int vo_layernorm_bwd_ex(const void* x, int x_dtype, const void* res, int res_dtype, const void* gy,
                                    int gy_dtype, const void* gy2, const float* gamma, const int32_t* lens, int B,
                                    int T, int D, float eps, void* gh, float* gh32, float* dgamma, float* dbeta,
                                    void* workspace, void* stream) {
-  VO_CHECK_ARG(x && gy && gamma && gh && dgamma && dbeta && workspace, "layernorm_bwd_ex: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm_bwd_ex: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0, "layernorm_bwd_ex: empty");
   VO_CHECK_ARG(gh32 == nullptr || ((const void*)gh32 != x && (const void*)gh32 != gh), "layernorm_bwd_ex: gh32 aliases");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* ws = (float*)workspace;
-  if (!res) res_dtype = x_dtype;
-  if (x_dtype == VO_BF16 && res_dtype == VO_F32 && gy_dtype == VO_F32)
-    return ln_bwd_launch<bf16_t, float, float>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st, gy2,
-                                               gh32);
-  if (x_dtype == VO_BF16 && res_dtype == VO_F32 && gy_dtype == VO_BF16)
-    return ln_bwd_launch<bf16_t, bf16_t, float>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st,
-                                                gy2, gh32);
-  if (x_dtype == res_dtype && gy2 == nullptr && gh32 == nullptr)
-    return vo_layernorm_bwd(x, res, x_dtype, gy, gy_dtype, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, workspace,
-                            stream);
-  vo_set_error("layernorm_bwd_ex: unsupported dtype combination (bf16 x with fp32 res, or equal x / res without gy2 / gh32)");
-  return VO_ERR_INVALID;
+  const LnBwdCall c{"layernorm_bwd_ex", x, res, gy, gy2, x_dtype, res ? res_dtype : x_dtype, gy_dtype, gamma, lens, B,
+                    T, D, eps, gh, gh32, dgamma, dbeta, (float*)workspace, LN_NO_DROP, (hipStream_t)stream};
+  return ln_backward(c, LN_BWD_EX);
 }
 
 // ---- round 6: the training FFT blocks' dropout fused into their LayerNorms (x = the sublayer output before its
 // dropout).  Forward: y = LN(dropout(x) + res) (+ its bf16 copy y16 when y is fp32 and y16 != NULL).  Backward:
 // gh = d/dx (through the mask), gres = d/dres (both 0 on pad rows), the dropout mask recomputed from (seed, salt).
 static LnDrop ln_drop(float p, const int64_t* seed, unsigned salt) {
-  LnDrop d;
-  d.seed = seed;
-  d.salt = salt;
-  d.thr = (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0);
-  d.scale = 1.f / (1.f - p);
-  return d;
+  return LnDrop{seed, salt, (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0), 1.f / (1.f - p)};
 }
 
 extern "C" int vo_layernorm_drop(const void* x, int x_dtype, const void* res, int res_dtype, const float* gamma,
                                  const float* beta, const int32_t* lens, int B, int T, int D, float eps, void* y,
                                  int y_dtype, void* y16, float p, const int64_t* seed, unsigned salt, void* stream) {
-  VO_CHECK_ARG(x && res && gamma && beta && y && seed, "layernorm_drop: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm_drop: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0 && (int64_t)B * T * D < (1LL << 32), "layernorm_drop: empty or > 2^32 elements");
+  VO_CHECK_ARG(res && seed, "layernorm_drop: null pointer");
   VO_CHECK_ARG(p >= 0.f && p < 1.f, "layernorm_drop: p = %g outside [0, 1)", p);
   VO_CHECK_ARG(y16 == nullptr || (y_dtype == VO_F32 && y16 != y && y16 != x && y16 != res),
                "layernorm_drop: y16 needs an fp32 y and its own buffer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const LnDrop dr = ln_drop(p, seed, salt);
-  if (y16) {
-    if (x_dtype == VO_BF16 && res_dtype == VO_F32)
-      return ln_launch<bf16_t, float, float, true>(x, res, gamma, beta, lens, B, T, D, eps, y, st, y16, dr);
-    if (x_dtype == VO_F32 && res_dtype == VO_F32)
-      return ln_launch<float, float, float, true>(x, res, gamma, beta, lens, B, T, D, eps, y, st, y16, dr);
-  } else {
-    if (x_dtype == VO_F32 && res_dtype == VO_F32 && y_dtype == VO_F32)
-      return ln_launch<float, float, float>(x, res, gamma, beta, lens, B, T, D, eps, y, st, nullptr, dr);
-    if (x_dtype == VO_BF16 && res_dtype == VO_BF16 && y_dtype == VO_BF16)
-      return ln_launch<bf16_t, bf16_t, bf16_t>(x, res, gamma, beta, lens, B, T, D, eps, y, st, nullptr, dr);
-    if (x_dtype == VO_BF16 && res_dtype == VO_F32 && y_dtype == VO_F32)
-      return ln_launch<bf16_t, float, float>(x, res, gamma, beta, lens, B, T, D, eps, y, st, nullptr, dr);
-  }
-  vo_set_error("layernorm_drop: unsupported dtype combination");
-  return VO_ERR_INVALID;
+  const LnFwdCall c{"layernorm_drop", x, res, x_dtype, res_dtype, gamma, beta, lens, B, T, D, eps, y, y16, y_dtype,
+                    ln_drop(p, seed, salt), (hipStream_t)stream};
+  return ln_forward(c, LN_DROP);
 }
 
 extern "C" int vo_layernorm_bwd_drop(const void* x, int x_dtype, const void* res, int res_dtype, const void* gy,
                                      int gy_dtype, const void* gy2, const float* gamma, const int32_t* lens, int B,
                                      int T, int D, float eps, float p, const int64_t* seed, unsigned salt, void* gh,
                                      void* gres, float* dgamma, float* dbeta, void* workspace, void* stream) {
-  VO_CHECK_ARG(x && res && gy && gamma && gh && gres && dgamma && dbeta && workspace && seed,
-               "layernorm_bwd_drop: null pointer");
-  VO_CHECK_ARG(D == 256 || D == 512, "layernorm_bwd_drop: D=%d unsupported (256 or 512)", D);
-  VO_CHECK_ARG(B > 0 && T > 0 && (int64_t)B * T * D < (1LL << 32), "layernorm_bwd_drop: empty or > 2^32 elements");
+  VO_CHECK_ARG(res && gres && seed, "layernorm_bwd_drop: null pointer");
   VO_CHECK_ARG(p >= 0.f && p < 1.f, "layernorm_bwd_drop: p = %g outside [0, 1)", p);
   VO_CHECK_ARG(gres != gh && gres != x && gh != x, "layernorm_bwd_drop: outputs alias");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* ws = (float*)workspace;
-  const LnDrop dr = ln_drop(p, seed, salt);
-  if (x_dtype == VO_BF16 && res_dtype == VO_F32 && gy_dtype == VO_F32)
-    return ln_bwd_launch<bf16_t, float, float>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st, gy2,
-                                               gres, dr);
-  if (x_dtype == VO_BF16 && res_dtype == VO_F32 && gy_dtype == VO_BF16)
-    return ln_bwd_launch<bf16_t, bf16_t, float>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st, gy2,
-                                                gres, dr);
-  if (x_dtype == VO_F32 && res_dtype == VO_F32 && gy_dtype == VO_F32 && gy2 == nullptr)
-    return ln_bwd_launch<float, float, float>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st, nullptr,
-                                              gres, dr);
-  if (x_dtype == VO_BF16 && res_dtype == VO_BF16 && gy_dtype == VO_BF16 && gy2 == nullptr)
-    return ln_bwd_launch<bf16_t, bf16_t, bf16_t>(x, res, gy, gamma, lens, B, T, D, eps, gh, dgamma, dbeta, ws, st,
-                                                 nullptr, gres, dr);
-  vo_set_error("layernorm_bwd_drop: unsupported dtype combination");
-  return VO_ERR_INVALID;
+  const LnBwdCall c{"layernorm_bwd_drop", x, res, gy, gy2, x_dtype, res_dtype, gy_dtype, gamma, lens, B, T, D, eps, gh,
+                    gres, dgamma, dbeta, (float*)workspace, ln_drop(p, seed, salt), (hipStream_t)stream};
+  return ln_backward(c, LN_BWD_DROP);
 }

@@ -6,6 +6,8 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/vonoma.h"
 
 typedef unsigned short bf16_t;
@@ -153,6 +155,37 @@ __device__ __forceinline__ void load4(const float* p, float (&v)[4]) {
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
 }
 
+// One 16-byte vector of a lane, V = 8 bf16 / 4 fp32 elements (the vectorised BatchNorm kernels, vo_dropout)
+template <typename TX> struct BnVec;
+template <> struct BnVec<float> {
+  static constexpr int V = 4;
+  __device__ static __forceinline__ void load(const float* p, float (&v)[4]) {
+    const float4 u = *reinterpret_cast<const float4*>(p);
+    v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
+  }
+  __device__ static __forceinline__ void store(float* p, const float (&v)[4]) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+template <> struct BnVec<bf16_t> {
+  static constexpr int V = 8;
+  __device__ static __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[2 * i] = __uint_as_float(w[i] << 16);
+      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+  }
+  __device__ static __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
+    uint32_t w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = pk_bf16(v[2 * i], v[2 * i + 1]);
+    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+};
+
 // ---------------------------------------------------------------- MFMA fragments
 // A fragment holds A[row = lane&15][k = 8*(lane>>4) + j], B holds B[k = 8*(lane>>4)+j][col = lane&15]
 // (j = 0..7).  For bf16 that is exactly one v_mfma_f32_16x16x32_bf16.  For f32 the same
@@ -286,3 +319,36 @@ extern "C" int vo_tune_get(const char* key);
     }                                                            \
     return VO_OK;                                                \
   } while (0)
+
+// ---------------------------------------------------------------- host: runtime dtype / flag -> template argument
+// A launcher names its instantiations once, inside a generic lambda: with_dtype(dtype, who, f) calls f(tag) with
+// decltype(tag)::type = float / bf16_t and ::id = VO_F32 / VO_BF16, with_dtypes the same for a pair, with_bool
+// f(std::true_type / std::false_type).  Any other dtype value: VO_ERR_INVALID, the error naming `who`.  The caller
+// leaves the combinations it does not ship out with `if constexpr`, so nothing else is instantiated.
+namespace vo {
+
+template <typename T, int ID>
+struct DtypeTag {
+  using type = T;
+  static constexpr int id = ID;
+};
+
+template <class F>
+int with_dtype(int dtype, const char* who, F f) {
+  if (dtype == VO_F32) return f(DtypeTag<float, VO_F32>{});
+  if (dtype == VO_BF16) return f(DtypeTag<bf16_t, VO_BF16>{});
+  vo_set_error("%s: unsupported dtype %d", who, dtype);
+  return VO_ERR_INVALID;
+}
+
+template <class F>
+int with_dtypes(int dtype_a, int dtype_b, const char* who, F f) {
+  return with_dtype(dtype_a, who, [&](auto a) { return with_dtype(dtype_b, who, [&](auto b) { return f(a, b); }); });
+}
+
+template <class F>
+int with_bool(bool v, F f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
+}  // namespace vo

@@ -268,6 +268,40 @@ def pack_conv_weight(w, dtype, g=None, row_scale=None, transposed_stride=None):
 
 # ----------------------------------------------------------------------------- layer norm
 
+def _ln_fwd(name, x, res, y_dtype, with_bf16, out=None):
+    """What the forward wrappers share: x and res contiguous and of one shape; y (``out`` if given) and, with_bf16,
+    its bf16 copy.  Returns (y, y16 or None)."""
+    _contig(x, "x")
+    if res is not None:
+        _contig(res, "res")
+        if res.shape != x.shape:
+            raise ValueError(f"{name}: res shape mismatch")
+    y = out if out is not None else torch.empty(x.shape, dtype=y_dtype, device=x.device)
+    return y, torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if with_bf16 else None
+
+
+def _ln_bwd(name, x, gy, res, gy2=None, gres_dtype=None):
+    """What the backward wrappers share, before any launch: x, gy, res and gy2 contiguous, gy and res of x's shape,
+    gy2 bf16 of x's shape (the kernels read it as bf16: there is no dtype argument).  Allocates and returns
+    (gh, gres or None, dgamma, dbeta, workspace)."""
+    B, T, D = x.shape
+    _contig(x, "x")
+    for t, n in ((gy, "gy"), (res, "res"), (gy2, "gy2")):
+        if t is None:
+            continue
+        _contig(t, n)
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: {n} must have x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if gy2 is not None and gy2.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: gy2 must be bf16, got {gy2.dtype}")
+    gh = torch.empty_like(x)
+    gres = None if gres_dtype is None else torch.empty(x.shape, dtype=gres_dtype, device=x.device)
+    dg = torch.empty(D, dtype=torch.float32, device=x.device)
+    db = torch.empty(D, dtype=torch.float32, device=x.device)
+    nws = int(_lib.lib().vo_layernorm_bwd_workspace_size(B, T, D)) // 4
+    return gh, gres, dg, db, torch.empty(nws, dtype=torch.float32, device=x.device)
+
+
 def layernorm(x, gamma, beta, res=None, lens=None, out=None, out_dtype=None, eps=1e-5, with_bf16=False):
     """y = LN(x + res) * gamma + beta, rows t >= lens[b] zeroed.  x: (B, T, D).  ``with_bf16``
     (fp32 y only): returns (y, y16), y16 the bf16 copy of y written in the same pass
@@ -275,47 +309,30 @@ def layernorm(x, gamma, beta, res=None, lens=None, out=None, out_dtype=None, eps
     if x.dim() == 2:
         x = x.unsqueeze(0)
     B, T, D = x.shape
-    _contig(x, "x")
-    if res is not None:
-        _contig(res, "res")
-        if res.shape != x.shape:
-            raise ValueError("layernorm: res shape mismatch")
-    out = out if out is not None else torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
+    out, out16 = _ln_fwd("layernorm", x, res, out_dtype or x.dtype, with_bf16, out)
+    rdt = vo_dtype(res) if res is not None else vo_dtype(x)
     if with_bf16:
         if out.dtype != torch.float32:
             raise ValueError("layernorm: with_bf16 needs an fp32 output")
-        out16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
         _lib.check(_lib.lib().vo_layernorm_dual(
-            _ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res) if res is not None else vo_dtype(x),
-            _ptr(gamma), _ptr(beta), _ptr(lens), B, T, D, eps, _ptr(out), _ptr(out16), _stream(x)),
-            "vo_layernorm_dual")
+            _ptr(x), vo_dtype(x), _ptr(res), rdt, _ptr(gamma), _ptr(beta), _ptr(lens), B, T, D, eps, _ptr(out),
+            _ptr(out16), _stream(x)), "vo_layernorm_dual")
         return out, out16
     _lib.check(_lib.lib().vo_layernorm(
-        _ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res) if res is not None else vo_dtype(x),
-        _ptr(gamma), _ptr(beta), _ptr(lens), B, T, D, eps, _ptr(out), vo_dtype(out), _stream(x)),
-        "vo_layernorm")
+        _ptr(x), vo_dtype(x), _ptr(res), rdt, _ptr(gamma), _ptr(beta), _ptr(lens), B, T, D, eps, _ptr(out),
+        vo_dtype(out), _stream(x)), "vo_layernorm")
     return out
 
 
 def layernorm_bwd(x, gy, gamma, res=None, lens=None, eps=1e-5):
     """Backward of ``layernorm``: (gh, dgamma, dbeta); gh = dL/d(x + res) in x's dtype."""
     B, T, D = x.shape
-    _contig(x, "x")
-    _contig(gy, "gy")
-    if res is not None:
-        _contig(res, "res")
-        if res.shape != x.shape or res.dtype != x.dtype:
-            raise ValueError("layernorm_bwd: res must match x in shape and dtype")
-    if gy.shape != x.shape:
-        raise ValueError("layernorm_bwd: gy shape mismatch")
-    L = _lib.lib()
-    gh = torch.empty_like(x)
-    dg = torch.empty(D, dtype=torch.float32, device=x.device)
-    db = torch.empty(D, dtype=torch.float32, device=x.device)
-    ws = torch.empty(int(L.vo_layernorm_bwd_workspace_size(B, T, D)) // 4, dtype=torch.float32, device=x.device)
-    _lib.check(L.vo_layernorm_bwd(_ptr(x), _ptr(res), vo_dtype(x), _ptr(gy), vo_dtype(gy), _ptr(gamma), _ptr(lens),
-                                  B, T, D, eps, _ptr(gh), _ptr(dg), _ptr(db), _ptr(ws), _stream(x)),
-               "vo_layernorm_bwd")
+    if res is not None and res.dtype != x.dtype:
+        raise ValueError("layernorm_bwd: res must match x in shape and dtype")
+    gh, _, dg, db, ws = _ln_bwd("layernorm_bwd", x, gy, res)
+    _lib.check(_lib.lib().vo_layernorm_bwd(
+        _ptr(x), _ptr(res), vo_dtype(x), _ptr(gy), vo_dtype(gy), _ptr(gamma), _ptr(lens), B, T, D, eps, _ptr(gh),
+        _ptr(dg), _ptr(db), _ptr(ws), _stream(x)), "vo_layernorm_bwd")
     return gh, dg, db
 
 
@@ -325,23 +342,12 @@ def layernorm_bwd_ex(x, gy, gamma, res, lens=None, gy2=None, eps=1e-5):
     (bf16, optional) that of the y16 copy -- added in the kernel.  Returns (gh in x's dtype, gh32 =
     the same gradient in fp32 for res, dgamma, dbeta) (vo_layernorm_bwd_ex)."""
     B, T, D = x.shape
-    for t, n in ((x, "x"), (gy, "gy"), (res, "res")):
-        _contig(t, n)
-    if x.dtype != torch.bfloat16 or res.dtype != torch.float32 or res.shape != x.shape or gy.shape != x.shape:
+    if x.dtype != torch.bfloat16 or res.dtype != torch.float32:
         raise ValueError("layernorm_bwd_ex: bf16 x, fp32 res, gy of x's shape")
-    if gy2 is not None:
-        _contig(gy2, "gy2")
-        if gy2.dtype != torch.bfloat16 or gy2.shape != x.shape:
-            raise ValueError("layernorm_bwd_ex: gy2 must be bf16 of x's shape")
-    L = _lib.lib()
-    gh = torch.empty_like(x)
-    gh32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    dg = torch.empty(D, dtype=torch.float32, device=x.device)
-    db = torch.empty(D, dtype=torch.float32, device=x.device)
-    ws = torch.empty(int(L.vo_layernorm_bwd_workspace_size(B, T, D)) // 4, dtype=torch.float32, device=x.device)
-    _lib.check(L.vo_layernorm_bwd_ex(_ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res), _ptr(gy), vo_dtype(gy),
-                                     _ptr(gy2), _ptr(gamma), _ptr(lens), B, T, D, eps, _ptr(gh), _ptr(gh32), _ptr(dg),
-                                     _ptr(db), _ptr(ws), _stream(x)), "vo_layernorm_bwd_ex")
+    gh, gh32, dg, db, ws = _ln_bwd("layernorm_bwd_ex", x, gy, res, gy2, torch.float32)
+    _lib.check(_lib.lib().vo_layernorm_bwd_ex(
+        _ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res), _ptr(gy), vo_dtype(gy), _ptr(gy2), _ptr(gamma), _ptr(lens),
+        B, T, D, eps, _ptr(gh), _ptr(gh32), _ptr(dg), _ptr(db), _ptr(ws), _stream(x)), "vo_layernorm_bwd_ex")
     return gh, gh32, dg, db
 
 
@@ -349,12 +355,7 @@ def layernorm_drop(x, gamma, beta, res, p, seed, salt, lens=None, with_bf16=Fals
     """y = LN(dropout_p(x) + res) * gamma + beta, pad rows zeroed (vo_layernorm_drop): the dropout mask is
     vo_dropout's for the same (seed, salt) on x.  y in res's dtype; with_bf16 (fp32 y): returns (y, y16)."""
     B, T, D = x.shape
-    for t, n in ((x, "x"), (res, "res")):
-        _contig(t, n)
-    if res.shape != x.shape:
-        raise ValueError("layernorm_drop: res shape mismatch")
-    y = torch.empty(x.shape, dtype=res.dtype, device=x.device)
-    y16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if with_bf16 else None
+    y, y16 = _ln_fwd("layernorm_drop", x, res, res.dtype, with_bf16)
     _lib.check(_lib.lib().vo_layernorm_drop(
         _ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res), _ptr(gamma), _ptr(beta), _ptr(lens), B, T, D, eps, _ptr(y),
         vo_dtype(y), _ptr(y16), float(p), _ptr(seed), int(salt), _stream(x)), "vo_layernorm_drop")
@@ -365,20 +366,11 @@ def layernorm_bwd_drop(x, gy, gamma, res, p, seed, salt, lens=None, gy2=None, ep
     """Backward of ``layernorm_drop``: (gh = dL/dx through the mask in x's dtype, gres = dL/dres in res's dtype,
     dgamma, dbeta); gy2 (bf16, optional): the gradient of the y16 copy, added in the kernel."""
     B, T, D = x.shape
-    for t, n in ((x, "x"), (gy, "gy"), (res, "res")):
-        _contig(t, n)
-    if gy2 is not None:
-        _contig(gy2, "gy2")
-    L = _lib.lib()
-    gh = torch.empty_like(x)
-    gres = torch.empty_like(res)
-    dg = torch.empty(D, dtype=torch.float32, device=x.device)
-    db = torch.empty(D, dtype=torch.float32, device=x.device)
-    ws = torch.empty(int(L.vo_layernorm_bwd_workspace_size(B, T, D)) // 4, dtype=torch.float32, device=x.device)
-    _lib.check(L.vo_layernorm_bwd_drop(_ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res), _ptr(gy), vo_dtype(gy),
-                                       _ptr(gy2), _ptr(gamma), _ptr(lens), B, T, D, eps, float(p), _ptr(seed), int(salt),
-                                       _ptr(gh), _ptr(gres), _ptr(dg), _ptr(db), _ptr(ws), _stream(x)),
-               "vo_layernorm_bwd_drop")
+    gh, gres, dg, db, ws = _ln_bwd("layernorm_bwd_drop", x, gy, res, gy2, res.dtype)
+    _lib.check(_lib.lib().vo_layernorm_bwd_drop(
+        _ptr(x), vo_dtype(x), _ptr(res), vo_dtype(res), _ptr(gy), vo_dtype(gy), _ptr(gy2), _ptr(gamma), _ptr(lens),
+        B, T, D, eps, float(p), _ptr(seed), int(salt), _ptr(gh), _ptr(gres), _ptr(dg), _ptr(db), _ptr(ws),
+        _stream(x)), "vo_layernorm_bwd_drop")
     return gh, gres, dg, db
 
 
