@@ -893,6 +893,45 @@ int vo_augment_batch(const vo_corpus* c, const int32_t* plan, int B, int T_src, 
                      float* energies, float* kurtosises, float* durations, float* images, int32_t* status,
                      void* stream);
 
+/* Energy / kurtosis statistics over the augmented population and the normalisation of the packed corpus (additive;
+ * DESIGN.md section 15).  Replaces the "feature normalization" pass of Preprocessor.build_from_path
+ * (scripts/preprocessor/preprocessor.py:113-144) with its _remove_outlier (:647-660) and _normalize (:624-645), and
+ * the energy pass of scripts/preprocessor/augmenter.py:330-398, none of which can run until every variant is a file.
+ *
+ * vo_corpus_stats: feature VO_STATS_ENERGY reads ch_energy, VO_STATS_KURTOSIS ch_kurtosis (VO_ERR_INVALID when the
+ * corpus has no such array).  Row b of plan (n_rows, 5), as for vo_augment_batch, stands for the array
+ * v[j] = x[sigma(j mod n')], j < L = n' r, in fp64 (m_mel plays no part beyond its sign).  Per row, as
+ * _remove_outlier: p25, p75 = np.percentile(v, 25 / 75) (method "linear": h = (L - 1) q on the sorted array,
+ * t = h - floor(h), a + (b - a) t for t < 0.5 and b - (b - a) (1 - t) otherwise, every operation rounded once),
+ * lower = p25 - 1.5 (p75 - p25), upper = p75 + 1.5 (p75 - p25); v[j] is kept iff lower < v[j] < upper, both strict:
+ * a row whose quartiles coincide (L = 1, all values equal) keeps nothing.  Then, as StandardScaler and _normalize,
+ * out (6 doubles, device memory) =
+ *   [0] the number of kept values of all rows, [1] their mean, [2] their population standard deviation (ddof 0;
+ *   1.0 where it is zero, and mean 0, std 1 when nothing was kept at all), [3], [4] the smallest and largest raw
+ *   value of the utterances that an accepted row names, kept or not (+inf, -inf when no row was accepted),
+ *   [5] the number of rows that kept at least one value.
+ * (x - mean) / std is monotone, so the min and max of stats.json are ([3] - [1]) / [2] and ([4] - [1]) / [2].
+ * A row is refused on the device by vo_augment_batch's rules in their order, without its caps: VO_AUG_BAD_ROW, then
+ * VO_STATS_CHARS_OVER for L > VO_STATS_MAX_CHARS (never truncated); a refused row contributes nothing, and its code
+ * goes to status[b] (status (n_rows) int32, or NULL).  Non-finite values are the caller's responsibility: a row
+ * that contains a NaN keeps nothing, as numpy's comparisons give, and nothing is promised about [3] and [4] then.
+ * workspace: vo_corpus_stats_workspace_size(n_rows) bytes of device memory, 8-byte aligned, written in full.
+ * Two launches (one workgroup per row, then one that folds the rows' (count, mean, M2) in a fixed order); no atomics,
+ * so two calls give the same bits.  Allocates nothing, never synchronises, reads nothing on the host, plan included:
+ * graph-capturable, and a plan rewritten in place is what a replay reads.
+ *
+ * vo_corpus_normalize: values[i] = (float)(((double)values[i] - stats[1]) / stats[2]) in place for i < n, stats
+ * being the out of vo_corpus_stats in device memory, read on the device: stream-ordered behind that call with no
+ * host round trip.  Equal to numpy's float64 (x - mean) / std followed by a cast to float32, bit for bit. */
+#define VO_STATS_ENERGY 0
+#define VO_STATS_KURTOSIS 1
+#define VO_STATS_MAX_CHARS 4096
+#define VO_STATS_CHARS_OVER 4
+int64_t vo_corpus_stats_workspace_size(int n_rows);
+int vo_corpus_stats(const vo_corpus* c, const int32_t* plan, int n_rows, int feature, void* workspace,
+                    int64_t workspace_bytes, double* out, int32_t* status, void* stream);
+int vo_corpus_normalize(float* values, int64_t n, const double* stats, void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Multi-tensor Adam (decoupled = 0: L2 weight decay on the gradient) / AdamW (decoupled = 1) step over
  * nt fp32 tensors (tables of device pointers and element counts, host memory), torch's

@@ -12,7 +12,10 @@
   path it replaces: the variants' files materialised in a temporary directory, read through Dataset.__getitem__,
   collate_fn and to_device.  Bytes per second are the batch's output bytes over the launch time.
 
-    python tools/bench_aux.py [glyph] [features] [augment] [--out FILE]     (all three by default)
+* corpus statistics (vo_corpus_stats): the energy statistics of the reference's feature normalisation over every row
+  of that corpus's variant plan, against numpy over the materialised arrays.
+
+    python tools/bench_aux.py [glyph] [features] [augment] [stats] [--out FILE]     (all four by default)
     rocprofv3 --kernel-trace --stats ... -- python tools/bench_aux.py augment --kernels 200   (launches only)
 """
 import json
@@ -124,22 +127,15 @@ def features():
                              "kind": "port", "sample": f"{n} utterances, oracle/mel.char_features torch-CPU"}}
 
 
-def augment(kernels=0):
+def _aug_bases():
+    """The synthetic corpus of the augment and stats modes -> (rng, configs, bases): 120 utterances of ICASSP-like
+    sizes."""
     import copy
-    import ctypes
-    import shutil
-    import statistics
-    import tempfile
-    from pathlib import Path
-    from PIL import Image
     import augment_check as C
     from helpers import DATA, configs
-    from visual_onoma_to_wave_amd import _lib, ops
-    from visual_onoma_to_wave_amd.dataset import Dataset, DeviceCorpus
-    from visual_onoma_to_wave_amd.utils.tools import to_device
     rng = np.random.default_rng(14)
     pc, mc, tc = copy.deepcopy(configs())
-    cfg, B, U, H, cell, dev = pc["augmentation"], 48, 120, 24, 102, torch.device("cuda")
+    U, H, cell = 120, 24, 102
     sym = C.symbol_ids()
     chars, labels = list(sym), sorted(json.load(open(os.path.join(DATA, "audiotype.json"))))
     bases = []
@@ -156,6 +152,24 @@ def augment(kernels=0):
                       "energy": rng.standard_normal(n), "kurtosis": None, "duration": dur,
                       "image": (rng.integers(0, 256, (H, int(width.sum()))).astype(np.uint8), width),
                       "event_image_feature": None})
+    return rng, (pc, mc, tc), bases
+
+
+def augment(kernels=0):
+    import ctypes
+    import shutil
+    import statistics
+    import tempfile
+    from pathlib import Path
+    from PIL import Image
+    import augment_check as C
+    from helpers import DATA
+    from visual_onoma_to_wave_amd import _lib, ops
+    from visual_onoma_to_wave_amd.dataset import Dataset, DeviceCorpus
+    from visual_onoma_to_wave_amd.utils.tools import to_device
+    rng, (pc, mc, tc), bases = _aug_bases()
+    cfg, B, U, H, cell, dev = pc["augmentation"], 48, len(bases), 24, 102, torch.device("cuda")
+    sym = C.symbol_ids()
     corpus = DeviceCorpus.from_arrays(bases, cell, pc["visual_text"]["stride"], dev)
     names, plan = corpus.variants(cfg)
     rows = np.sort(rng.choice(len(names), B, replace=False))
@@ -240,12 +254,75 @@ def augment(kernels=0):
                          "bytes_per_launch": out_bytes}}
 
 
+def stats():
+    """vo_corpus_stats over the whole augmented corpus of the augment mode (its 120 utterances, every row of
+    ``corpus.variants``) against the host path it replaces: numpy over the materialised arrays, np.percentile, the
+    filter, mean and std."""
+    import ctypes
+    import statistics
+    import corpus_stats_check as S
+    from visual_onoma_to_wave_amd import _lib, ops
+    from visual_onoma_to_wave_amd.dataset import DeviceCorpus
+    _, (pc, _, _), bases = _aug_bases()
+    dev = torch.device("cuda")
+    corpus = DeviceCorpus.from_arrays(bases, 102, pc["visual_text"]["stride"], dev)
+    names, plan = corpus.variants(pc["augmentation"])
+    plan_d = torch.from_numpy(plan).to(dev)
+    out, status = ops.corpus_stats(corpus.struct, plan_d, "energy")
+    ws = torch.empty(int(_lib.lib().vo_corpus_stats_workspace_size(len(plan))), dtype=torch.uint8, device=dev)
+    P = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    c_args = (ctypes.byref(corpus.struct), P(plan_d), len(plan), _lib.STATS_ENERGY, P(ws), ws.numel(), P(out),
+              P(status), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    fn = _lib.lib().vo_corpus_stats
+
+    def launch():  # the two launches alone, through the C ABI
+        fn(*c_args)
+    values = [u["energy"].astype(np.float32) for u in bases]
+    arrays = [S.row_array(values[r[0]], r) for r in plan.tolist()]  # the variants materialised once, outside the timing
+
+    def host():
+        kept = [S.keep(v) for v in arrays]
+        flat = np.concatenate(kept)
+        mean = float(flat.mean())
+        return len(flat), mean, float(np.sqrt(np.mean((flat - mean) ** 2))), min(float(v.min()) for v in arrays), \
+            max(float(v.max()) for v in arrays)
+    want, got = host(), out.cpu().numpy()
+    assert got[0] == want[0] and got[3] == want[3] and got[4] == want[4] and not bool(status.any())
+    assert abs(got[1] - want[1]) <= want[0] * 2.0 ** -52 * (abs(want[1]) + want[2])
+    assert abs(got[2] - want[2]) <= want[0] * 2.0 ** -52 * want[2]
+    t_host, t_call, t_launch = [], [], []
+    for _ in range(5):  # the two paths alternate
+        t0 = time.perf_counter()
+        for _ in range(3):
+            host()
+        t_host.append((time.perf_counter() - t0) / 3)
+        t_call.append(timed(lambda: ops.corpus_stats(corpus.struct, plan_d, "energy", out=out, status=status,
+                                                     workspace=ws), 2000))
+        t_launch.append(timed(launch, 5000))
+    med = statistics.median
+    spread = lambda v: [round(min(v) * 1e6, 2), round(max(v) * 1e6, 2)]  # noqa: E731
+    return {"metric": "energy statistics over the augmented corpus from a device plan (preprocessor.py:113-144, "
+                      "DESIGN.md 15)", "unit": "calls/s", "value": round(1 / med(t_launch), 1),
+            "config": {"corpus_utterances": len(bases), "plan_rows": len(plan), "kept_values": int(want[0]),
+                       "characters_in_all_rows": int(sum(len(v) for v in arrays)), "windows": 5},
+            "device_path": {"vo_corpus_stats_us": round(med(t_launch) * 1e6, 2),
+                            "vo_corpus_stats_us_min_max": spread(t_launch),
+                            "ops.corpus_stats_us": round(med(t_call) * 1e6, 2),
+                            "ops.corpus_stats_us_min_max": spread(t_call),
+                            "note": "back-to-back calls (two launches each), device events"},
+            "host_path": {"stats_us": round(med(t_host) * 1e6, 1), "stats_us_min_max": spread(t_host),
+                          "note": "numpy over the materialised float64 arrays (built outside the timing): two "
+                                  "np.percentile and the filter per array, mean and std of the concatenation, min / max"},
+            "speedup_launches_vs_host": round(med(t_host) / med(t_launch), 1)}
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     out = args.pop(args.index("--out") + 1) if "--out" in args else None
     kernels = int(args.pop(args.index("--kernels") + 1)) if "--kernels" in args else 0
     args = [a for a in args if a not in ("--out", "--kernels")]
-    which = {"glyph": glyph, "features": features, "augment": (lambda: augment(kernels)) if kernels else augment}
+    which = {"glyph": glyph, "features": features, "augment": (lambda: augment(kernels)) if kernels else augment,
+             "stats": stats}
     lines = [json.dumps(which[k]()) for k in (args or list(which))]
     print("\n".join(lines))
     if out:

@@ -104,6 +104,9 @@ class Corpus(ctypes.Structure):
 
 
 AUG_OK, AUG_BAD_ROW, AUG_CHARS_OVER, AUG_FRAMES_OVER = 0, 1, 2, 3
+# vo_corpus_stats: the features, the longest row it takes and the status of a longer one
+STATS_ENERGY, STATS_KURTOSIS = 0, 1
+STATS_MAX_CHARS, STATS_CHARS_OVER = 4096, 4
 
 _SIGNATURES = {
     "vo_last_error": (ctypes.c_char_p, []),
@@ -280,6 +283,10 @@ _SIGNATURES = {
     "vo_glyph_stretch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vo_augment_batch": (c_int, [ctypes.POINTER(Corpus), c_void_p] + [c_int] * 7 + [c_void_p] * 11),
+    "vo_corpus_stats_workspace_size": (c_int64, [c_int]),
+    "vo_corpus_stats": (c_int, [ctypes.POINTER(Corpus), c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_void_p]),
+    "vo_corpus_normalize": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION

@@ -99,6 +99,7 @@ static const char* const kSymbols[] = {
     "vo_stft_mel_lens", "vo_stft_mel_frames",
     "vo_glyph_stretch_table_size", "vo_glyph_stretch_table", "vo_glyph_stretch",
     "vo_augment_batch",
+    "vo_corpus_stats_workspace_size", "vo_corpus_stats", "vo_corpus_normalize",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

@@ -383,6 +383,7 @@ class DeviceCorpus:
         self.struct = _lib.Corpus(U=len(self.texts), n_mels=self.n_mels, strip_h=self.height,
                                   **{k: None if t is None else t.data_ptr() for k, t in self.tensors.items()})
         self.last_status = None
+        self.normalized = False
         return self
 
     @classmethod
@@ -413,6 +414,85 @@ class DeviceCorpus:
                 names.append(f"{self.names[u]}{suffix}")
                 rows.append((u, pos, m, mm, r))
         return names, np.asarray(rows, np.int32)
+
+    def _stats_plan(self, plan, cfg):
+        """The plan of ``stats`` / ``normalize_`` on the device: a device tensor as it is (never read back), a host plan
+        through ``check_plan``'s range rules without caps, None -> ``variants(cfg)`` or the base rows."""
+        import torch
+        from .preprocessor import augment as AU
+        if torch.is_tensor(plan) and plan.is_cuda:
+            return plan
+        if plan is None:
+            plan = self.variants(cfg)[1] if cfg is not None else [(u, 0, 0, 0, 1) for u in range(len(self))]
+        p, _, _ = AU.check_plan(plan.numpy() if torch.is_tensor(plan) else plan, self.n_chars, self.n_frames,
+                                self.durations)
+        return torch.from_numpy(p).to(self.device, non_blocking=True)
+
+    def _stats_device(self, plan_d):
+        """feature -> the (6,) float64 ``out`` of ``ops.corpus_stats`` on the device, for the features the corpus has."""
+        from . import ops
+        outs = {}
+        for k in ("energy", "kurtosis"):
+            if self.tensors["ch_" + k] is not None:
+                outs[k], self.last_status = ops.corpus_stats(self.struct, plan_d, k)
+        if not outs:
+            raise ValueError("DeviceCorpus: the corpus was packed without energy and kurtosis")
+        return outs
+
+    @staticmethod
+    def _stats_host(outs):
+        """``stats.json``'s [min, max, mean, std] per feature: one device-to-host copy each."""
+        res = {}
+        for k, o in outs.items():
+            _, mean, std, lo, hi, _ = (np.float64(v) for v in o.cpu().numpy())
+            if lo > hi:
+                raise ValueError(f"DeviceCorpus: no plan row was accepted for the {k} statistics (last_status has the "
+                                 "reasons)")
+            res[k] = [float((lo - mean) / std), float((hi - mean) / std), float(mean), float(std)]
+        return res
+
+    def stats(self, plan=None, cfg=None):
+        """``stats.json`` of the corpus augmented by ``plan`` -> {"energy": [min, max, mean, std], "kurtosis": [...]}
+        (the features the corpus has), as the reference's ``build_from_path`` computes them over every file it wrote
+        (scripts/preprocessor/preprocessor.py:113-144): per row the interquartile outlier rule,
+        mean and population std over what all rows keep, min and max of the normalised values of every character.  No
+        variant is materialised.  ``plan``: rows ``src, pos, m, m_mel, r``; None: ``variants(cfg)[1]`` with ``cfg``
+        (the ``augmentation:`` block), the base utterances alone without.  A host plan is checked first (ValueError
+        naming the row); a device plan is never read back.  A row longer than ``_lib.STATS_MAX_CHARS`` characters is
+        refused on the device and contributes nothing: ``self.last_status`` has the rows' codes.  On a corpus that
+        ``normalize_`` has already normalised these are the statistics of the normalised values."""
+        return self._stats_host(self._stats_device(self._stats_plan(plan, cfg)))
+
+    def normalize_(self, stats=None, plan=None, cfg=None):
+        """Z-normalise ``ch_energy`` / ``ch_kurtosis`` in place, ``(x - mean) / std`` in float64 rounded to float32 (the
+        reference's ``_normalize`` followed by ``to_device``'s ``.float()``), and return the stats dict.  ``stats``:
+        that of ``stats()`` or a ``stats.json``; None: computed from ``plan`` / ``cfg`` as ``stats`` does, and then mean
+        and std go from the statistics kernel to the normalising one on the device.  ``batch`` afterwards gives the
+        normalised values.  A second call raises ValueError: normalising twice is silent corruption."""
+        import torch
+        from . import ops
+        if self.normalized:
+            raise ValueError("DeviceCorpus.normalize_: the corpus is already normalised")
+        have = [k for k in ("energy", "kurtosis") if self.tensors["ch_" + k] is not None]
+        if stats is None:
+            outs = self._stats_device(self._stats_plan(plan, cfg))
+            stats = self._stats_host(outs)  # before anything is written: raises when no row was accepted
+        else:
+            if plan is not None or cfg is not None:
+                raise ValueError("DeviceCorpus.normalize_: give stats, or plan / cfg to compute them, not both")
+            outs = {}
+            for k in have:
+                if k not in stats or len(stats[k]) != 4:
+                    raise ValueError(f"DeviceCorpus.normalize_: stats has no [min, max, mean, std] for {k}")
+                mean, std = float(stats[k][2]), float(stats[k][3])
+                if not (np.isfinite(mean) and np.isfinite(std) and std > 0):
+                    raise ValueError(f"DeviceCorpus.normalize_: {k} mean {mean}, std {std} (finite, std > 0)")
+                outs[k] = torch.tensor([0.0, mean, std, 0.0, 0.0, 0.0], dtype=torch.float64).to(self.device)
+            stats = {k: [float(v) for v in stats[k]] for k in have}
+        for k in have:
+            ops.corpus_normalize_(self.tensors["ch_" + k], outs[k])
+        self.normalized = True
+        return stats
 
     def batch(self, plan, max_src_len=None, max_mel_len=None, out=None, names=None):
         """The batch of ``plan`` -> (ids, audiotypes, texts, src_lens, max_src_len, mels, mel_lens, max_mel_len,

@@ -1685,6 +1685,70 @@ def augment_batch(corpus, plan, T_src, T_mel, H, cell, margin, W_out=None, out=N
     return out
 
 
+STATS_FEATURES = {"energy": _lib.STATS_ENERGY, "kurtosis": _lib.STATS_KURTOSIS}
+
+
+def corpus_stats(corpus, plan, feature, out=None, status=None, workspace=None):
+    """The reference's energy / kurtosis statistics over the variants of ``plan`` without the variants (include/vonoma.h,
+    vo_corpus_stats).  ``corpus``: a ``_lib.Corpus`` of device pointers (``dataset.DeviceCorpus``
+    owns one), ``plan`` (n_rows, 5) int32 on the GPU, rows ``src, pos, m, m_mel, r``, ``feature`` "energy" or "kurtosis"
+    (or ``_lib.STATS_*``) -> (out, status): out (6,) float64 = kept count, mean, std, raw min, raw max, rows that kept
+    a value; status (n_rows,) int32 (``_lib.AUG_BAD_ROW`` or ``_lib.STATS_CHARS_OVER`` for a row that was refused and
+    contributed nothing).  The plan is never read on the host (``DeviceCorpus.stats`` checks a host plan first).  Two
+    launches on the current stream, no atomics, graph-capturable.  ``out`` / ``status`` / ``workspace`` (uint8,
+    ``vo_corpus_stats_workspace_size(n_rows)`` bytes or more): tensors of an earlier call, written in full."""
+    if not (torch.is_tensor(plan) and plan.is_cuda and plan.dtype == torch.int32 and plan.dim() == 2
+            and plan.shape[1] == 5 and plan.shape[0] >= 1):
+        raise ValueError("corpus_stats: plan must be an int32 (n_rows, 5) tensor on the GPU with n_rows >= 1")
+    _contig(plan, "plan")
+    f = STATS_FEATURES.get(feature, feature)
+    if f not in STATS_FEATURES.values():
+        raise ValueError(f"corpus_stats: feature must be one of {tuple(STATS_FEATURES)}, got {feature!r}")
+    if not (corpus.ch_energy if f == _lib.STATS_ENERGY else corpus.ch_kurtosis):
+        raise ValueError(f"corpus_stats: the corpus was packed without {('energy', 'kurtosis')[f]}")
+    n_rows = plan.shape[0]
+    need = int(_lib.lib().vo_corpus_stats_workspace_size(n_rows))
+    spec = {"out": ((6,), torch.float64), "status": ((n_rows,), torch.int32)}
+    given = {"out": out, "status": status}
+    for k, (shape, dt) in spec.items():
+        t = given[k]
+        if t is None:
+            given[k] = torch.empty(shape, dtype=dt, device=plan.device)
+        elif not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or t.device != plan.device:
+            raise ValueError(f"corpus_stats: {k} must be {dt} {shape} on {plan.device}, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else t}")
+        else:
+            _contig(t, k)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=plan.device)
+    elif (not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+          or workspace.numel() < need or workspace.device != plan.device):
+        raise ValueError(f"corpus_stats: workspace must be uint8 ({need},) or longer on {plan.device}")
+    else:
+        _contig(workspace, "workspace")
+    _lib.check(_lib.lib().vo_corpus_stats(ctypes.byref(corpus), _ptr(plan), n_rows, f, _ptr(workspace),
+                                          workspace.numel(), _ptr(given["out"]), _ptr(given["status"]), _stream(plan)),
+               "vo_corpus_stats")
+    return given["out"], given["status"]
+
+
+def corpus_normalize_(values, stats):
+    """``values`` (fp32, any shape, contiguous) <- (float)(((double)values - stats[1]) / stats[2]) in place, ``stats`` the
+    (6,) float64 ``out`` of ``corpus_stats`` on the same device, read there: stream-ordered behind that call without a
+    host round trip (vo_corpus_normalize; one launch on the current stream, graph-capturable).  numpy's float64
+    ``(x - mean) / std`` followed by ``.astype(float32)``, bit for bit."""
+    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.numel() >= 1):
+        raise ValueError("corpus_normalize_: values must be a non-empty fp32 tensor on the GPU")
+    if not (torch.is_tensor(stats) and stats.dtype == torch.float64 and tuple(stats.shape) == (6,)
+            and stats.device == values.device):
+        raise ValueError(f"corpus_normalize_: stats must be float64 (6,) on {values.device} (corpus_stats's out)")
+    _contig(values, "values")
+    _contig(stats, "stats")
+    _lib.check(_lib.lib().vo_corpus_normalize(_ptr(values), values.numel(), _ptr(stats), _stream(values)),
+               "vo_corpus_normalize")
+    return values
+
+
 # ----------------------------------------------------------------------------- offline feature extraction
 
 def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):

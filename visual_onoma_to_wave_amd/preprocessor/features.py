@@ -88,10 +88,29 @@ class FeatureExtractor:
         return res
 
 
-def normalize_features(arrays):
+def iqr_inliers(values):
+    """``Preprocessor._remove_outlier`` (preprocessor.py:647-660): the values strictly inside the fences 1.5
+    interquartile ranges below the 25th and above the 75th percentile (``np.percentile``'s default method).  An
+    array whose quartiles coincide keeps nothing."""
+    values = np.array(values)
+    p25, p75 = np.percentile(values, 25), np.percentile(values, 75)
+    lower, upper = p25 - 1.5 * (p75 - p25), p75 + 1.5 * (p75 - p25)
+    return values[np.logical_and(values > lower, values < upper)]
+
+
+def normalize_features(arrays, remove_outlier=False):
     """StandardScaler.partial_fit over every value + _normalize: returns (normalised arrays,
-    mean, std, min, max) with the population std (ddof 0) StandardScaler uses."""
-    flat = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in arrays])
+    mean, std, min, max) with the population std (ddof 0) StandardScaler uses.
+    ``remove_outlier``: mean and std are taken over what ``iqr_inliers`` keeps of each array (an array that
+    keeps nothing is skipped), as ``build_from_path`` does (:117-125); every value is still normalised, and min and
+    max are over all of them.  The device form over an augmented corpus: ``DeviceCorpus.stats`` (DESIGN.md section
+    15)."""
+    fit = arrays
+    if remove_outlier:
+        fit = [iqr_inliers(np.asarray(a, np.float64).reshape(-1)) for a in arrays]
+        if not sum(len(a) for a in fit):
+            raise ValueError("normalize_features: the outlier rule keeps no value of any array")
+    flat = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in fit])
     mean = float(flat.mean())
     std = float(np.sqrt(np.mean((flat - mean) ** 2)))
     if std == 0.0:
