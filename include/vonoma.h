@@ -932,6 +932,57 @@ int vo_corpus_stats(const vo_corpus* c, const int32_t* plan, int n_rows, int fea
                     int64_t workspace_bytes, double* out, int32_t* status, void* stream);
 int vo_corpus_normalize(float* values, int64_t n, const double* stats, void* stream);
 
+/* HiFi-GAN training batches (additive): aligned (mel, audio) segments cut on the device from
+ * the packed corpus and the base utterances' waveforms beside it, and the random draw of their rows.  The rules are
+ * this project's own (the reference trains no vocoder); they follow the fine-tuning branch of HiFi-GAN's MelDataset:
+ * the mel from the corpus, the audio cropped at mel_start * hop.
+ *
+ * vo_wave_corpus: the waveforms of the U utterances of a vo_corpus, in its order, packed flat in device memory.
+ * Utterance u has N = n_samples[u] >= 1 samples at sample_off[u] of wav; every sample_off[u] is a multiple of 8 (the
+ * gaps are padding nobody reads) and sample_off[U] is the packed length, so that with hop % 8 == 0 a segment starts
+ * on a 16-byte boundary of int16 samples and a 32-byte one of fp32.  wav is int16 (is_int16 != 0; PCM as the files
+ * hold it) or fp32.
+ *
+ * vo_segment_batch: plan (B, 2) int32 in device memory, row b = src, start (in frames).  With F frames and N samples
+ * of utterance src, an accepted row writes
+ *   y[b, i] = wav[sample_off[src] + start hop + i] for start hop + i < N, else 0.0f: an fp32 sample bit for bit (no
+ *     clipping), an int16 sample s as (float)s / max_wav_value, one IEEE float32 division;
+ *   x[b, f, :] = mel[frame_off[src] + start + f, :] for start + f < F, else mel_pad;
+ *   frames[b] = min(fps, F - start), status[b] = VO_SEG_OK.
+ * A row is refused on the device, never raised, when src is outside [0, U), start < 0 or start > max(F - fps, 0):
+ * status[b] = VO_SEG_BAD_ROW, y all 0.0f, x all mel_pad, frames[b] = 0; the other rows are unaffected.  Outputs y
+ * (B, fps hop) fp32, x (B, fps, n_mels) fp32 (channels-last: what the generator's training forward reads), frames (B)
+ * int32, status (B) int32; every element of every output is written.  VO_ERR_INVALID, nothing launched: a null
+ * pointer, w->U != c->U, B outside [1, 65535], fps < 1, hop < 1, fps hop or fps n_mels at or above 2^31.  start hop
+ * and every offset are formed in 64 bits.  Samples move as 16-byte vectors when hop % 8 == 0 and wav and y are
+ * 16-byte aligned, frames when n_mels % 4 == 0 and mel and x are; element by element otherwise.
+ *
+ * vo_segment_plan: the draw.  order (n_order) int32, an epoch's utterance order (the host shuffles it and rewrites it
+ * in place); counter, one int64 in device memory >= 0, the number of rows drawn so far.  Row b of plan (B, 2) is drawn
+ * from k = counter + b: src = order[k mod n_order]; (src, 0) when src is outside [0, U) (vo_segment_batch refuses it);
+ * otherwise start = (uint64(w) span) >> 32 with span = F - fps + 1 for F > fps, else 1 (at most 2^31), and w word 0 of
+ * Philox4x32-10 (Salmon et al. 2011: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85) of the
+ * counter words (k lo, k hi, 0, 0) under the key (seed lo, seed hi).  Then counter <- counter + B: a replay of a
+ * captured call draws the next B rows by itself.  One workgroup; no atomics.  VO_ERR_INVALID: a null pointer,
+ * n_order < 1, B outside [1, 65535], fps < 1.
+ *
+ * Both are one launch each, allocate nothing, never synchronise and read nothing on the host: graph-capturable, and
+ * a plan, an order or a counter rewritten in place is what a replay reads. */
+#define VO_SEG_OK 0
+#define VO_SEG_BAD_ROW 1
+typedef struct vo_wave_corpus {
+  int32_t U;
+  const int64_t* sample_off;  /* (U + 1), in samples; multiples of 8 */
+  const int64_t* n_samples;   /* (U) */
+  const void* wav;            /* (sample_off[U]) int16 or fp32 */
+  int32_t is_int16;
+  float max_wav_value;
+} vo_wave_corpus;
+int vo_segment_batch(const vo_corpus* c, const vo_wave_corpus* w, const int32_t* plan, int B, int fps, int hop,
+                     float mel_pad, float* y, float* x, int32_t* frames, int32_t* status, void* stream);
+int vo_segment_plan(const vo_corpus* c, const int32_t* order, int n_order, int64_t* counter, uint64_t seed, int B,
+                    int fps, int32_t* plan, void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Multi-tensor Adam (decoupled = 0: L2 weight decay on the gradient) / AdamW (decoupled = 1) step over
  * nt fp32 tensors (tables of device pointers and element counts, host memory), torch's

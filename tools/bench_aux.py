@@ -15,7 +15,12 @@
 * corpus statistics (vo_corpus_stats): the energy statistics of the reference's feature normalisation over every row
   of that corpus's variant plan, against numpy over the materialised arrays.
 
-    python tools/bench_aux.py [glyph] [features] [augment] [stats] [--out FILE]     (all four by default)
+* vocoder training batch (vo_segment_plan + vo_segment_batch, hifigan.data.SegmentSampler): 16 segments of 8192
+  samples and their mel frames drawn and cut on the device from that corpus with int16 waveforms attached, against
+  numpy crops of the same rows and their upload.  ``segments-c5`` (only when named): the C5 training step replayed
+  with the batch drawn inside the graph against the replay over static tensors.
+
+    python tools/bench_aux.py [glyph] [features] [augment] [stats] [segments] [--out FILE]   (these five by default)
     rocprofv3 --kernel-trace --stats ... -- python tools/bench_aux.py augment --kernels 200   (launches only)
 """
 import json
@@ -27,7 +32,7 @@ import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "tests")):
+for p in (REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "tests", "golden")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -316,14 +321,133 @@ def stats():
             "speedup_launches_vs_host": round(med(t_host) / med(t_launch), 1)}
 
 
+def _seg_corpus(dev):
+    """The synthetic corpus of the augment mode with int16 waveforms of F * hop samples attached -> (corpus, waves)."""
+    from visual_onoma_to_wave_amd.dataset import DeviceCorpus
+    rng, (pc, _, _), bases = _aug_bases()
+    hop = 256
+    wavs = [rng.integers(-8000, 8001, u["mel"].shape[0] * hop).astype(np.int16) for u in bases]
+    corpus = DeviceCorpus.from_arrays(bases, 102, pc["visual_text"]["stride"], dev).attach_waves(wavs, hop)
+    return corpus, bases, wavs
+
+
+def segments():
+    """A HiFi-GAN training batch (16 segments of 8192 samples and their 32 mel frames) drawn and cut on the device
+    (vo_segment_plan + vo_segment_batch, hifigan.data.SegmentSampler) against the host path it
+    replaces: numpy crops of the same rows, torch.from_numpy, .to(device), synchronise."""
+    import ctypes
+    import statistics
+    from visual_onoma_to_wave_amd import _lib
+    from visual_onoma_to_wave_amd.hifigan import SegmentSampler
+    dev = torch.device("cuda")
+    corpus, bases, wavs = _seg_corpus(dev)
+    B, seg, hop = 16, 8192, 256
+    fps = seg // hop
+    s = SegmentSampler(corpus, seg, hop, B, seed=16)
+    x, y = s.draw()
+    rows = s.plan.cpu().tolist()
+    mels = [u["mel"] for u in bases]
+
+    def host():
+        hx, hy = np.zeros((B, fps, 80), np.float32), np.zeros((B, seg), np.float32)
+        for b, (src, start) in enumerate(rows):
+            m = mels[src][start:start + fps]
+            a = wavs[src][start * hop:start * hop + seg]
+            hx[b, :len(m)] = m
+            hy[b, :len(a)] = a.astype(np.float32) / np.float32(32768.0)
+        out = torch.from_numpy(hx).to(dev), torch.from_numpy(hy).to(dev)
+        torch.cuda.synchronize()
+        return out
+    hx, hy = host()
+    assert torch.equal(hx, x) and torch.equal(hy, y) and not bool(s.status.any())
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib = _lib.lib()
+    plan_args = (ctypes.byref(corpus.struct), P(s.order), s.order.shape[0], P(s.counter), s.seed, B, fps, P(s.plan), st)
+    batch_args = (ctypes.byref(corpus.struct), ctypes.byref(corpus.waves), P(s.plan), B, fps, hop, 0.0, P(y), P(x),
+                  P(s.frames), P(s.status), st)
+
+    def launch():  # the two launches alone, through the C ABI
+        lib.vo_segment_plan(*plan_args)
+        lib.vo_segment_batch(*batch_args)
+    t_host, t_call, t_launch = [], [], []
+    for _ in range(5):  # the two paths alternate
+        t0 = time.perf_counter()
+        for _ in range(200):
+            host()
+        t_host.append((time.perf_counter() - t0) / 200)
+        t_call.append(timed(s.draw, 2000))
+        t_launch.append(timed(launch, 5000))
+    med = statistics.median
+    spread = lambda v: [round(min(v) * 1e6, 2), round(max(v) * 1e6, 2)]  # noqa: E731
+    out_bytes = x.numel() * 4 + y.numel() * 4
+    assert med(t_call) <= med(t_host), (med(t_call), med(t_host))  # the device path is not slower than the host's
+    return {"metric": "HiFi-GAN training batch drawn and cut on the device (DESIGN.md 16)", "unit": "batches/s",
+            "value": round(1 / med(t_call), 1),
+            "config": {"batch": B, "segment_size": seg, "hop": hop, "n_mels": 80, "corpus_utterances": len(bases),
+                       "waveforms": "int16, F * hop samples", "output_bytes": out_bytes, "windows": 5},
+            "device_path": {"sampler.draw_us": round(med(t_call) * 1e6, 2), "sampler.draw_us_min_max": spread(t_call),
+                            "launches_us": round(med(t_launch) * 1e6, 2), "launches_us_min_max": spread(t_launch),
+                            "note": "back-to-back calls (two launches each: the draw, the cut), device events; "
+                                    f"{out_bytes / 1e6:.2f} MB of output: launch latency bounds it, not bandwidth, so no "
+                                    "roofline fraction is quoted"},
+            "host_path": {"batch_us": round(med(t_host) * 1e6, 1), "batch_us_min_max": spread(t_host),
+                          "note": "numpy crops of the same 16 rows from arrays in memory, torch.from_numpy, .to(device), "
+                                  "synchronize, one process"},
+            "host_over_device": round(med(t_host) / med(t_call), 2)}
+
+
+def segments_c5():
+    """The C5 training step at the benchmark's shape (batch 16, segment 8192, bf16 compute) as one graph replay with
+    its batch drawn inside (``step_graphed(sampler=...)``) against the replay over static tensors plus their two
+    copies (``step_graphed(x, y)``): five windows each, the order rotated."""
+    import statistics
+    from helpers import hifigan_arrays, hifigan_h
+    from weights import load_into
+    from visual_onoma_to_wave_amd import hifigan
+    dev = torch.device("cuda")
+    corpus, _, _ = _seg_corpus(dev)
+    h = hifigan.AttrDict(hifigan_h())
+    B, seg, hop, steps = 16, h.segment_size, h.hop_size, 20
+    runs = {}
+    for kind in ("static", "sampler"):
+        g = hifigan.Generator(h)
+        load_into(g, hifigan_arrays())
+        torch.manual_seed(1234)
+        tr = hifigan.HifiGanTrainer(g.to(dev), h, device=dev, graphed=True).set_compute_dtype(torch.bfloat16)
+        s = hifigan.SegmentSampler(corpus, seg, hop, B, seed=5)
+        if kind == "sampler":
+            runs[kind] = lambda tr=tr, s=s: tr.step_graphed(sampler=s)
+        else:
+            x, y = (t.clone() for t in s.draw())
+            runs[kind] = lambda tr=tr, x=x, y=y: tr.step_graphed(x, y)
+        runs[kind]()  # warm-up steps and the capture
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    order = list(runs)
+    for i in range(5):
+        for k in order[i % 2:] + order[:i % 2]:
+            ms[k].append(timed(runs[k], steps) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"metric": "C5 step: graph replay with the batch drawn inside against static tensors", "unit": "ms/step",
+            "value": round(med["sampler"], 3),
+            "config": {"batch": B, "segment": seg, "dtype": "bf16", "steps_per_window": steps, "windows": 5,
+                       "order": "rotated from window to window"},
+            "ms_per_step": {k: [round(t, 3) for t in v] for k, v in ms.items()},
+            "median": {k: round(v, 3) for k, v in med.items()},
+            "sampler_minus_static_us": round((med["sampler"] - med["static"]) * 1e3, 1),
+            "note": "the sampler's replay holds two more launches (the draw, the cut) and no copies of x and y into "
+                    "the static buffers; the static path's two copies are outside its graph"}
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     out = args.pop(args.index("--out") + 1) if "--out" in args else None
     kernels = int(args.pop(args.index("--kernels") + 1)) if "--kernels" in args else 0
     args = [a for a in args if a not in ("--out", "--kernels")]
     which = {"glyph": glyph, "features": features, "augment": (lambda: augment(kernels)) if kernels else augment,
-             "stats": stats}
-    lines = [json.dumps(which[k]()) for k in (args or list(which))]
+             "stats": stats, "segments": segments, "segments-c5": segments_c5}
+    lines = [json.dumps(which[k]()) for k in (args or [k for k in which if k != "segments-c5"])]
     print("\n".join(lines))
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)

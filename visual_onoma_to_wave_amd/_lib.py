@@ -103,7 +103,14 @@ class Corpus(ctypes.Structure):
                                 "ch_dstart", "ch_width", "ch_col", "ch_energy", "ch_kurtosis", "mel", "px")]
 
 
+class WaveCorpus(ctypes.Structure):
+    """vo_wave_corpus (include/vonoma.h, vo_segment_batch)."""
+    _fields_ = [("U", ctypes.c_int32), ("sample_off", c_void_p), ("n_samples", c_void_p), ("wav", c_void_p),
+                ("is_int16", ctypes.c_int32), ("max_wav_value", ctypes.c_float)]
+
+
 AUG_OK, AUG_BAD_ROW, AUG_CHARS_OVER, AUG_FRAMES_OVER = 0, 1, 2, 3
+SEG_OK, SEG_BAD_ROW = 0, 1
 # vo_corpus_stats: the features, the longest row it takes and the status of a longer one
 STATS_ENERGY, STATS_KURTOSIS = 0, 1
 STATS_MAX_CHARS, STATS_CHARS_OVER = 4096, 4
@@ -287,6 +294,10 @@ _SIGNATURES = {
     "vo_corpus_stats": (c_int, [ctypes.POINTER(Corpus), c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p]),
     "vo_corpus_normalize": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "vo_segment_batch": (c_int, [ctypes.POINTER(Corpus), ctypes.POINTER(WaveCorpus), c_void_p, c_int, c_int, c_int,
+                                 c_float] + [c_void_p] * 5),
+    "vo_segment_plan": (c_int, [ctypes.POINTER(Corpus), c_void_p, c_int, c_void_p, ctypes.c_uint64, c_int, c_int,
+                                c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION

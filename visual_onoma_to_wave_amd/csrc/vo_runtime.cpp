@@ -100,6 +100,7 @@ static const char* const kSymbols[] = {
     "vo_glyph_stretch_table_size", "vo_glyph_stretch_table", "vo_glyph_stretch",
     "vo_augment_batch",
     "vo_corpus_stats_workspace_size", "vo_corpus_stats", "vo_corpus_normalize",
+    "vo_segment_batch", "vo_segment_plan",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

@@ -384,6 +384,56 @@ class DeviceCorpus:
                                   **{k: None if t is None else t.data_ptr() for k, t in self.tensors.items()})
         self.last_status = None
         self.normalized = False
+        self.waves = None
+        return self
+
+    def attach_waves(self, wavs, hop, max_wav_value=32768.0):
+        """The base utterances' waveforms beside their mels, for the vocoder's training batches
+        (``hifigan.data.SegmentSampler``): ``wavs`` is one 1-D array per utterance in corpus
+        order, all int16 (PCM as the files hold it, kept as int16 and divided by ``max_wav_value`` when a segment is
+        cut) or all floating point (kept as fp32, copied as they are).  Packed once, flat, every utterance at a sample
+        offset that is a multiple of 8.  ``hop``: the hop of the corpus's mels; utterance u of N samples and F frames
+        must have 1 + N // hop >= F, what ``FeatureExtractor.process`` requires of a waveform and its durations.
+        ValueError naming the utterance otherwise.  Sets ``self.waves`` (``_lib.WaveCorpus``) and returns self."""
+        import torch
+        from . import _lib
+        hop, max_wav_value = int(hop), float(max_wav_value)
+        if hop < 1:
+            raise ValueError(f"DeviceCorpus.attach_waves: hop must be >= 1, got {hop}")
+        if not (np.isfinite(max_wav_value) and max_wav_value > 0):
+            raise ValueError(f"DeviceCorpus.attach_waves: max_wav_value must be finite and > 0, got {max_wav_value}")
+        wavs = list(wavs)
+        if len(wavs) != len(self):
+            raise ValueError(f"DeviceCorpus.attach_waves: {len(wavs)} waveforms for {len(self)} utterances")
+        arrays, is_int16 = [], None
+        for i, a in enumerate(wavs):
+            who = f"DeviceCorpus.attach_waves: utterance {i} ({self.names[i]!r})"
+            a = np.asarray(a.cpu() if torch.is_tensor(a) else a)
+            if a.ndim != 1 or a.size < 1:
+                raise ValueError(f"{who}: the waveform has shape {a.shape} (1-D and non-empty)")
+            if a.dtype != np.int16 and a.dtype.kind != "f":
+                raise ValueError(f"{who}: the waveform is {a.dtype} (int16 or floating point)")
+            if is_int16 is None:
+                is_int16 = a.dtype == np.int16
+            if (a.dtype == np.int16) != is_int16:
+                raise ValueError(f"{who}: the waveform is {a.dtype}, the ones before it are "
+                                 f"{'int16' if is_int16 else 'floating point'} (all int16 or all floating point)")
+            if 1 + a.size // hop < self.n_frames[i]:
+                raise ValueError(f"{who}: {a.size} samples are 1 + N // hop = {1 + a.size // hop} frames at hop {hop}, "
+                                 f"the mel has {self.n_frames[i]}")
+            arrays.append(a)
+        dtype = np.int16 if is_int16 else np.float32
+        n = np.asarray([a.size for a in arrays], np.int64)
+        off = np.concatenate([[0], np.cumsum((n + 7) // 8 * 8)]).astype(np.int64)
+        flat = np.zeros(int(off[-1]), dtype)
+        for a, o in zip(arrays, off):
+            flat[o:o + a.size] = a
+        self.n_samples = [int(v) for v in n]
+        self.wave_hop = hop
+        self.wave_tensors = {k: torch.from_numpy(a).to(self.device)
+                             for k, a in (("sample_off", off), ("n_samples", n), ("wav", flat))}
+        self.waves = _lib.WaveCorpus(U=len(self), is_int16=int(is_int16), max_wav_value=max_wav_value,
+                                     **{k: t.data_ptr() for k, t in self.wave_tensors.items()})
         return self
 
     @classmethod

@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "HifiGanTrainer":
         from .train import HifiGanTrainer
         return HifiGanTrainer
+    if name in ("SegmentSampler", "segment_plan_host", "check_segment_plan"):
+        from . import data
+        return getattr(data, name)
     raise AttributeError(name)

@@ -62,7 +62,7 @@ class HifiGanTrainer:
         self.msd = (msd or MultiScaleDiscriminator()).to(device)
         self.h = h
         self.graphed = graphed
-        self._graph = None
+        self._graph = self._sampler = None
         if graphed:
             _check_graph_runtime()
         # capturable AdamW (device-tensor step counts and learning rates) is required for the graph
@@ -153,33 +153,59 @@ class HifiGanTrainer:
         return dict(disc=loss_disc_all.detach(), gen=loss_gen_all.detach(), mel=loss_mel.detach(),
                     fm=loss_fm.detach(), adv=loss_adv.detach(), **extra)
 
-    def step_graphed(self, x_mel_cl, y, warmup=3):
+    def step_graphed(self, x_mel_cl=None, y=None, warmup=3, sampler=None):
         """``step`` as one HIP-graph replay (captured on the first call, after ``warmup`` eager
         steps on a side stream whose updates are then undone).  Inputs are copied into the
         graph's static buffers; the returned loss tensors are the graph's (overwritten by the next
-        replay).  No host synchronisation."""
+        replay).  No host synchronisation.
+
+        ``sampler`` (a ``hifigan.data.SegmentSampler``) in place of the two tensors: the captured body
+        is ``sampler.draw`` into the static buffers followed by ``step``, so a replay is a whole
+        training step including its batch, drawn from the sampler's counter on the device.  The
+        warm-up draws are undone as well: the first replay draws the rows the sampler stood at
+        before the call.  Tensors together with a sampler, or tensors after a capture with a sampler
+        (or the other way round, or another sampler), are a ValueError."""
         from . import gan_ops
         if not self.graphed:
             raise RuntimeError("HifiGanTrainer: construct with graphed=True to replay steps as a HIP graph")
+        if (sampler is None) == (x_mel_cl is None and y is None) or (x_mel_cl is None) != (y is None):
+            raise ValueError("HifiGanTrainer.step_graphed: give x_mel_cl and y, or sampler, not both")
+        if self._graph is not None and sampler is not self._sampler:
+            raise ValueError("HifiGanTrainer.step_graphed: the step was captured "
+                             + ("with tensors as its batch" if self._sampler is None else "with a sampler as its batch")
+                             + "; it cannot change afterwards")
         if self._graph is None:
-            self._x, self._y = x_mel_cl.clone(), y.clone()
+            if sampler is None:
+                self._x, self._y = x_mel_cl.clone(), y.clone()
+                draw = lambda: None  # noqa: E731
+            else:
+                dev = sampler.counter.device
+                self._x = torch.zeros((sampler.batch, sampler.fps, sampler.n_mels), dtype=torch.float32, device=dev)
+                self._y = torch.zeros((sampler.batch, sampler.segment_size), dtype=torch.float32, device=dev)
+                at = sampler.position()
+                draw = lambda: sampler.draw(out=(self._x, self._y))  # noqa: E731
             snap = TrainState([self.generator, self.mpd, self.msd], [self.optim_g, self.optim_d])
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), _warmup_ctx([self.bk_g, self.bk_d]):
                 for _ in range(warmup):
+                    draw()
                     self.step(self._x, self._y)
             torch.cuda.current_stream().wait_stream(side)
             gan_ops.reset_pack_cache()
             graph = torch.cuda.CUDAGraph()
             with _capture_ctx([self.bk_g, self.bk_d]), torch.cuda.graph(graph):
+                draw()
                 self._out = self.step(self._x, self._y)
             snap.restore()
+            if sampler is not None:
+                sampler.seek(at)
             gan_ops.reset_pack_cache()
             _base.invalidate_packs(self.generator, self.mpd, self.msd)
-            self._graph = graph
-        self._x.copy_(x_mel_cl)
-        self._y.copy_(y)
+            self._graph, self._sampler = graph, sampler
+        if sampler is None:
+            self._x.copy_(x_mel_cl)
+            self._y.copy_(y)
         self._graph.replay()
         gan_ops.reset_pack_cache()  # replays move the parameters without bumping their versions
         _base.invalidate_packs(self.generator, self.mpd, self.msd)

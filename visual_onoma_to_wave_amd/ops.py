@@ -1749,6 +1749,85 @@ def corpus_normalize_(values, stats):
     return values
 
 
+SEGMENT_OUT = ("y", "x", "frames", "status")
+
+
+def _segment_sizes(who, B, fps):
+    B, fps = int(B), int(fps)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"{who}: B must be in [1, 65535], got {B}")
+    if fps < 1:
+        raise ValueError(f"{who}: fps must be >= 1, got {fps}")
+    return B, fps
+
+
+def segment_batch(corpus, waves, plan, fps, hop, mel_pad=0.0, out=None):
+    """Aligned (mel, audio) training segments of the vocoder from a packed corpus (``_lib.Corpus``), the waveforms
+    beside it (``_lib.WaveCorpus``; ``dataset.DeviceCorpus.attach_waves`` builds and owns one) and ``plan`` (B, 2)
+    int32 on the GPU, rows ``src, start`` with start in frames (include/vonoma.h states the rule) -> dict of
+    ``SEGMENT_OUT``: y (B, fps * hop) fp32, x (B, fps, n_mels) fp32 channels-last, frames (B,) int32, status (B,)
+    int32.  Past an utterance's end y is 0.0 and x is ``mel_pad``.  The plan is never read on the host: a row out of
+    range comes out as padding with ``_lib.SEG_BAD_ROW`` in ``status``.  vo_segment_batch: one launch on the current
+    stream, graph-capturable.  ``out``: such a dict, every tensor of it written in full."""
+    if not (torch.is_tensor(plan) and plan.is_cuda and plan.dtype == torch.int32 and plan.dim() == 2
+            and plan.shape[1] == 2):
+        raise ValueError("segment_batch: plan must be an int32 (B, 2) tensor on the GPU")
+    _contig(plan, "plan")
+    B, fps = _segment_sizes("segment_batch", plan.shape[0], fps)
+    hop, n_mels = int(hop), int(corpus.n_mels)
+    if hop < 1:
+        raise ValueError(f"segment_batch: hop must be >= 1, got {hop}")
+    if fps * hop >= 2 ** 31 or fps * n_mels >= 2 ** 31:
+        raise ValueError(f"segment_batch: a row of fps * hop = {fps * hop} samples or fps * n_mels = {fps * n_mels} "
+                         "values is at or above 2^31")
+    if int(waves.U) != int(corpus.U):
+        raise ValueError(f"segment_batch: the wave corpus has {int(waves.U)} utterances, the corpus {int(corpus.U)}")
+    spec = {"y": ((B, fps * hop), torch.float32), "x": ((B, fps, n_mels), torch.float32),
+            "frames": ((B,), torch.int32), "status": ((B,), torch.int32)}
+    if out is None:
+        out = {k: torch.empty(s[0], dtype=s[1], device=plan.device) for k, s in spec.items()}
+    for k, s in spec.items():
+        t = out.get(k)
+        if not torch.is_tensor(t) or t.dtype != s[1] or tuple(t.shape) != s[0] or t.device != plan.device:
+            raise ValueError(f"segment_batch: out[{k!r}] must be {s[1]} {s[0]} on {plan.device}, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else t}")
+        _contig(t, k)
+    _lib.check(_lib.lib().vo_segment_batch(ctypes.byref(corpus), ctypes.byref(waves), _ptr(plan), B, fps, hop,
+                                           float(mel_pad), *[_ptr(out[k]) for k in SEGMENT_OUT], _stream(plan)),
+               "vo_segment_batch")
+    return out
+
+
+def segment_plan(corpus, order, counter, seed, B, fps, plan=None):
+    """The next ``B`` rows of the vocoder's segment draw -> plan (B, 2) int32, rows ``src, start`` (vo_segment_plan,
+    include/vonoma.h): row b from k = counter + b, src = order[k mod len(order)], start uniform in [0, max(F - fps, 0)]
+    from Philox4x32-10 of k under ``seed``; then ``counter`` += B on the device.  ``order`` (n_order,) int32 and
+    ``counter`` (1,) int64 live on the GPU and are never read on the host: one launch on the current stream,
+    graph-capturable, and a replay draws the following rows.  ``hifigan.data.segment_plan_host`` is the same rule in
+    numpy.  ``plan``: the tensor of an earlier call, written in full."""
+    if not (torch.is_tensor(order) and order.is_cuda and order.dtype == torch.int32 and order.dim() == 1
+            and order.shape[0] >= 1):
+        raise ValueError("segment_plan: order must be a non-empty int32 (n_order,) tensor on the GPU")
+    if not (torch.is_tensor(counter) and counter.dtype == torch.int64 and counter.numel() == 1
+            and counter.device == order.device):
+        raise ValueError(f"segment_plan: counter must be one int64 on {order.device}")
+    _contig(order, "order")
+    B, fps = _segment_sizes("segment_plan", B, fps)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"segment_plan: seed must be in [0, 2^64), got {seed}")
+    if plan is None:
+        plan = torch.empty((B, 2), dtype=torch.int32, device=order.device)
+    elif (not torch.is_tensor(plan) or plan.dtype != torch.int32 or tuple(plan.shape) != (B, 2)
+          or plan.device != order.device):
+        raise ValueError(f"segment_plan: plan must be int32 ({B}, 2) on {order.device}")
+    else:
+        _contig(plan, "plan")
+    _lib.check(_lib.lib().vo_segment_plan(ctypes.byref(corpus), _ptr(order), order.shape[0], _ptr(counter), seed, B,
+                                          fps, _ptr(plan), _stream(order)), "vo_segment_plan")
+    return plan
+
+
 # ----------------------------------------------------------------------------- offline feature extraction
 
 def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):
