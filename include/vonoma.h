@@ -624,9 +624,11 @@ int vo_gan_reduce(int kind, const void* a, int lda, const void* b, int ldb, int6
 int vo_gan_reduce_grad(int kind, const void* a, int lda, const void* b, int ldb, int64_t rows,
                        int width, int dtype, const float* scale, void* ga, int ldg, void* stream);
 /* Many terms per launch (the C5 G step's feature-matching / adversarial terms, the D step's halves):
- * vo_gan_reduce_multi writes out[i] = sum_i * scale[i] (scale NULL: 1), each sum bit for bit
- * vo_gan_reduce's (workspace: vo_gan_reduce_multi_workspace_size(n) bytes); vo_gan_reduce_grad_multi
- * writes term i's gradient ga_i = scale[i] * d(sum_i)/da_i (ga, ldg per term).  scale: n device floats. */
+ * vo_gan_reduce_multi writes out[i] = sum_i * scale[i] (scale NULL: 1; workspace:
+ * vo_gan_reduce_multi_workspace_size(n) bytes); vo_gan_reduce_grad_multi writes term i's gradient
+ * ga_i = scale[i] * d(sum_i)/da_i (ga, ldg per term).  scale: n device floats.  vo_gan_reduce and
+ * vo_gan_reduce_grad run the same two kernels with a table of one term, and a term's blocks do not
+ * depend on the terms around it: sum_i and ga_i are the single-term results bit for bit. */
 typedef struct vo_gan_term {
   int kind; const void* a; int lda; const void* b; int ldb; int64_t rows; int width; void* ga; int ldg;
 } VoGanTerm;

@@ -289,208 +289,58 @@ __global__ void __launch_bounds__(256) avgpool_kernel(const float* __restrict__ 
   }
 }
 
-// reductions over a (rows x width) view with leading dimensions lda / ldb:
-//   0: sum |a - b|     1: sum (1 - a)^2     2: sum a^2
-template <typename TA>
-__global__ void __launch_bounds__(256) gan_reduce_kernel(int kind, const TA* __restrict__ a, int lda,
-                                                         const TA* __restrict__ b, int ldb, int64_t rows, int width,
-                                                         float* __restrict__ part) {
-  __shared__ float red[4];
-  const int64_t n = rows * width;
-  float s = 0.f;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / width;
-    const int c = (int)(i - r * width);
-    const float x = to_f32(a[r * lda + c]);
-    if (kind == 0) {
-      s += fabsf(x - to_f32(b[r * ldb + c]));
-    } else if (kind == 1) {
-      s += (1.f - x) * (1.f - x);
-    } else {
-      s += x * x;
-    }
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// *out += the block partials added in block order (one wave: lanes stride the blocks, a fixed tree)
-__global__ void __launch_bounds__(64) gan_reduce_final_kernel(const float* __restrict__ part, int n,
-                                                              float* __restrict__ out) {
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) s += part[i];
-  s = wave_sum(s);
-  if (threadIdx.x == 0) out[0] += s;
-}
-
-// gradient of scale * reduction wrt a (b held constant), written in a's layout
-template <typename TA>
-__global__ void __launch_bounds__(256) gan_reduce_grad_kernel(int kind, const TA* __restrict__ a, int lda,
-                                                              const TA* __restrict__ b, int ldb, int64_t rows,
-                                                              int width, const float* __restrict__ scale,
-                                                              TA* __restrict__ ga, int ldg) {
-  const int64_t n = rows * width;
-  const float s = *scale;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / width;
-    const int c = (int)(i - r * width);
-    const float x = to_f32(a[r * lda + c]);
-    float g;
-    if (kind == 0) {
-      const float d = x - to_f32(b[r * ldb + c]);
-      g = d > 0.f ? s : (d < 0.f ? -s : 0.f);
-    } else if (kind == 1) {
-      g = -2.f * (1.f - x) * s;
-    } else {
-      g = 2.f * x * s;
-    }
-    ga[r * ldg + c] = from_f32<TA>(g);
-  }
-}
-
 static int grid_for(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }
 
-// 8-element vector forms of the three kernels above (width and leading dimensions multiples of 8,
-// 16-byte aligned bases): one 16 / 32-byte load per operand per 8 elements, and the row / column
-// split of the flat index (a 64-bit division per ELEMENT in the scalar kernels, which made them
-// 10-30 us calls) per vector, or none at all when every operand is contiguous (FLAT)
+// The GAN reductions and the leaky-ReLU mask walk a (rows x width) view with leading dimensions in units of
+// V elements: V = 8 where the width and every leading dimension are multiples of 8 and the bases 16-byte
+// aligned (one 16 / 32-byte load per operand per unit), V = 1 otherwise.  RowMap splits a flat unit index into
+// row and column (a 64-bit division per unit: per ELEMENT at V = 1, which made those 10-30 us calls).
+template <int V>
 struct RowMap {
-  int64_t wv;  // vectors per row
-  __device__ __forceinline__ void at(int64_t v, int64_t* r, int* c) const {
-    *r = v / wv;
-    *c = (int)(v - *r * wv) * 8;
+  int64_t wv;  // units per row
+  __device__ __forceinline__ void at(int64_t u, int64_t* r, int* c) const {
+    *r = u / wv;
+    *c = (int)(u - *r * wv) * V;
   }
 };
-
-template <typename TA, bool FLAT>
-__global__ void __launch_bounds__(256) gan_reduce_v8_kernel(int kind, const TA* __restrict__ a, int lda,
-                                                            const TA* __restrict__ b, int ldb, int64_t rows,
-                                                            int width, float* __restrict__ part) {
-  __shared__ float red[4];
-  const RowMap rm{width / 8};
-  const int64_t nv = rows * rm.wv;
-  float s = 0.f;
-  for (int64_t v = blockIdx.x * 256 + threadIdx.x; v < nv; v += (int64_t)gridDim.x * 256) {
-    int64_t oa = v * 8, ob = v * 8;
-    if constexpr (!FLAT) {
-      int64_t r;
-      int c;
-      rm.at(v, &r, &c);
-      oa = r * lda + c;
-      ob = r * ldb + c;
-    }
-    float x[8];
-    load8(a + oa, x);
-    if (kind == 0) {
-      float y[8];
-      load8(b + ob, y);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += fabsf(x[e] - y[e]);
-    } else if (kind == 1) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += (1.f - x[e]) * (1.f - x[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += x[e] * x[e];
-    }
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+template <int V, typename T>
+__device__ __forceinline__ void load_v(const T* p, float (&v)[V]) {
+  if constexpr (V == 8) load8(p, v); else v[0] = to_f32(*p);
+}
+template <int V, typename T>
+__device__ __forceinline__ void store_v(T* p, const float (&v)[V]) {
+  if constexpr (V == 8) store8(p, v); else *p = from_f32<T>(v[0]);
 }
 
-template <typename TA, bool FLAT>
-__global__ void __launch_bounds__(256) gan_reduce_grad_v8_kernel(int kind, const TA* __restrict__ a, int lda,
-                                                                 const TA* __restrict__ b, int ldb, int64_t rows,
-                                                                 int width, const float* __restrict__ scale,
-                                                                 TA* __restrict__ ga, int ldg) {
-  const RowMap rm{width / 8};
-  const int64_t nv = rows * rm.wv;
-  const float sc = *scale;
-  for (int64_t v = blockIdx.x * 256 + threadIdx.x; v < nv; v += (int64_t)gridDim.x * 256) {
-    int64_t oa = v * 8, ob = v * 8, og = v * 8;
-    if constexpr (!FLAT) {
-      int64_t r;
-      int c;
-      rm.at(v, &r, &c);
-      oa = r * lda + c;
-      ob = r * ldb + c;
-      og = r * ldg + c;
-    }
-    float x[8], g[8];
-    load8(a + oa, x);
-    if (kind == 0) {
-      float y[8];
-      load8(b + ob, y);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float d = x[e] - y[e];
-        g[e] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
-      }
-    } else if (kind == 1) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = -2.f * (1.f - x[e]) * sc;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = 2.f * x[e] * sc;
-    }
-    store8(ga + og, g);
+// The loss terms, each formula stated here and nowhere else.  An element of term
+//   0: |x - y|     1: (1 - x)^2     2: x^2     (y: only kind 0 reads it)
+// and the gradient of s times it with respect to x (y held constant; 0 at a tie of kind 0).
+__device__ __forceinline__ float gan_value(int kind, float x, float y) {
+  if (kind == 0) return fabsf(x - y);
+  if (kind == 1) return (1.f - x) * (1.f - x);
+  return x * x;
+}
+__device__ __forceinline__ float gan_grad(int kind, float x, float y, float s) {
+  if (kind == 0) {
+    const float d = x - y;
+    return d > 0.f ? s : (d < 0.f ? -s : 0.f);
   }
+  if (kind == 1) return -2.f * (1.f - x) * s;
+  return 2.f * x * s;
+}
+// f(kind) with the kind a compile-time constant: a term's kind is tested once per unit, not once per element
+template <class F>
+__device__ __forceinline__ void with_kind(int kind, F f) {
+  if (kind == 0) f(std::integral_constant<int, 0>{});
+  else if (kind == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
 }
 
-// ADD 1: out = round(masked) + add[r, c] (then rounded): a residual's gradient summed in the same
-// pass -- bit for bit the masked tensor followed by autograd's add of the two gradients.
-// ADD 2: out = mask(round(g + add)): two gradients of the activation's output (the next conv's and a
-// feature-matching loss's) summed as autograd sums them, then masked
-template <typename TG, typename TR, bool FLAT, int ADD = 0>
-__global__ void __launch_bounds__(256) lrelu_mask_v8_kernel(const TG* __restrict__ g, int ldg,
-                                                            const TR* __restrict__ ref, int ldr, int64_t rows,
-                                                            int width, float slope, TG* __restrict__ out, int ldo,
-                                                            const TG* __restrict__ add = nullptr, int lda = 0) {
-  const RowMap rm{width / 8};
-  const int64_t nv = rows * rm.wv;
-  for (int64_t v = blockIdx.x * 256 + threadIdx.x; v < nv; v += (int64_t)gridDim.x * 256) {
-    int64_t og = v * 8, orf = v * 8, oo = v * 8, oa = v * 8;
-    if constexpr (!FLAT) {
-      int64_t r;
-      int c;
-      rm.at(v, &r, &c);
-      og = r * ldg + c;
-      orf = r * ldr + c;
-      oo = r * ldo + c;
-      oa = r * lda + c;
-    }
-    float x[8], q[8];
-    load8(g + og, x);
-    load8(ref + orf, q);
-    if constexpr (ADD == 2) {
-      float a[8];
-      load8(add + oa, a);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = to_f32(from_f32<TG>(x[e] + a[e]));
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = q[e] > 0.f ? x[e] : x[e] * slope;
-    if constexpr (ADD == 1) {
-      float a[8];
-      load8(add + oa, a);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = to_f32(from_f32<TG>(x[e])) + a[e];
-    }
-    store8(out + oo, x);
-  }
-}
-
-// Many loss terms per launch (the C5 G step's 54 feature-matching L1 terms and 8 adversarial ones,
-// the D step's 16 halves): term i's blocks are blk0[i] .. blk0[i + 1] - 1 of one grid, each doing what
-// block b of the single-term kernel's g_i-block grid does (same elements per thread, same sums), so
-// the partials, and the per-term sums of them added by one wave each, are those of vo_gan_reduce bit
-// for bit; the sums are written times the term's scale.  The gradient kernel likewise covers every
-// term's elements in one launch.  (Each term was a reduction, a final sum, and backward a gradient
-// launch: ~230 launches of 3-6 us per C5 step.)
+// Loss terms of one launch (the C5 G step's 54 feature-matching L1 terms and 8 adversarial ones, the D step's
+// 16 halves; each term was a reduction, a final sum, and backward a gradient launch: ~230 launches of 3-6 us
+// per C5 step): term i's blocks are blk0[i] .. blk0[i + 1] - 1 of one grid and stride the term's units by its
+// own block count g, so a term's partials do not depend on the terms around it.  The single-term entry points
+// run the same kernels with a one-term table.
 constexpr int GT_MAX = 32;
 struct GanTerm {
   const void* a; const void* b; void* ga;
@@ -503,65 +353,84 @@ struct GanArgs {
   int n;
 };
 
+// This thread's share of a term's sum: units bi * 256 + thread, then every gs-th, added in ascending order
+// into one accumulator (the sum's bits depend on it).  flat: every operand contiguous, no row split.
+template <typename TA, int V>
+__device__ __forceinline__ float gan_term_sum(const GanTerm& T, int64_t bi, int64_t gs) {
+  const TA* a = reinterpret_cast<const TA*>(T.a);
+  const TA* b = reinterpret_cast<const TA*>(T.b);
+  const RowMap<V> rm{T.width / V};
+  const int64_t nu = T.rows * rm.wv;
+  const bool flat = T.lda == T.width && (!b || T.ldb == T.width);
+  float s = 0.f;
+  for (int64_t u = bi * 256 + threadIdx.x; u < nu; u += gs) {
+    int64_t oa = u * V, ob = u * V;
+    if (!flat) {
+      int64_t r;
+      int c;
+      rm.at(u, &r, &c);
+      oa = r * T.lda + c;
+      ob = r * T.ldb + c;
+    }
+    float x[V], y[V] = {};
+    load_v<V>(a + oa, x);
+    if (T.kind == 0) load_v<V>(b + ob, y);
+    with_kind(T.kind, [&](auto kind) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) s += gan_value(kind, x[e], y[e]);
+    });
+  }
+  return s;
+}
+
+// The same units of the term's gradient, sc * d(sum)/da, written in ga's layout
+template <typename TA, int V>
+__device__ __forceinline__ void gan_term_grad(const GanTerm& T, int64_t bi, int64_t gs, float sc) {
+  const TA* a = reinterpret_cast<const TA*>(T.a);
+  const TA* b = reinterpret_cast<const TA*>(T.b);
+  TA* ga = reinterpret_cast<TA*>(T.ga);
+  const RowMap<V> rm{T.width / V};
+  const int64_t nu = T.rows * rm.wv;
+  for (int64_t u = bi * 256 + threadIdx.x; u < nu; u += gs) {
+    int64_t r;
+    int c;
+    rm.at(u, &r, &c);
+    float x[V], y[V] = {}, g[V];
+    load_v<V>(a + r * T.lda + c, x);
+    if (T.kind == 0) load_v<V>(b + r * T.ldb + c, y);
+    with_kind(T.kind, [&](auto kind) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) g[e] = gan_grad(kind, x[e], y[e], sc);
+    });
+    store_v<V>(ga + r * T.ldg + c, g);
+  }
+}
+
+// part[block] = the block's sum: at most 512 partials per term (workspace: 512 floats per term), added in
+// block order by one wave (deterministic; the grid-stride loop keeps the loads coalesced)
 template <typename TA>
 __global__ void __launch_bounds__(256) gan_multi_reduce_kernel(GanArgs A, float* __restrict__ part) {
   __shared__ float red[4];
   const int li = table_find(A.blk0, A.n, blockIdx.x);
   const GanTerm& T = A.t[li];
   const int64_t bi = blockIdx.x - A.blk0[li], gs = (int64_t)T.g * 256;
-  const TA* a = reinterpret_cast<const TA*>(T.a);
-  const TA* b = reinterpret_cast<const TA*>(T.b);
-  float s = 0.f;
-  if (T.v8) {
-    const RowMap rm{T.width / 8};
-    const int64_t nv = T.rows * rm.wv;
-    const bool flat = T.lda == T.width && (!b || T.ldb == T.width);
-    for (int64_t v = bi * 256 + threadIdx.x; v < nv; v += gs) {
-      int64_t oa = v * 8, ob = v * 8;
-      if (!flat) {
-        int64_t r;
-        int c;
-        rm.at(v, &r, &c);
-        oa = r * T.lda + c;
-        ob = r * T.ldb + c;
-      }
-      float x[8];
-      load8(a + oa, x);
-      if (T.kind == 0) {
-        float y[8];
-        load8(b + ob, y);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += fabsf(x[e] - y[e]);
-      } else if (T.kind == 1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += (1.f - x[e]) * (1.f - x[e]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += x[e] * x[e];
-      }
-    }
-  } else {
-    const int64_t n = T.rows * T.width;
-    for (int64_t i = bi * 256 + threadIdx.x; i < n; i += gs) {
-      const int64_t r = i / T.width;
-      const int c = (int)(i - r * T.width);
-      const float x = to_f32(a[r * T.lda + c]);
-      if (T.kind == 0) {
-        s += fabsf(x - to_f32(b[r * T.ldb + c]));
-      } else if (T.kind == 1) {
-        s += (1.f - x) * (1.f - x);
-      } else {
-        s += x * x;
-      }
-    }
-  }
+  float s = T.v8 ? gan_term_sum<TA, 8>(T, bi, gs) : gan_term_sum<TA, 1>(T, bi, gs);
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-// one wave per term: its partials added as gan_reduce_final_kernel adds them, times the term's scale
+// vo_gan_reduce: *out += the block partials added in block order (one wave: lanes stride the blocks, a fixed tree)
+__global__ void __launch_bounds__(64) gan_reduce_final_kernel(const float* __restrict__ part, int n,
+                                                              float* __restrict__ out) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) s += part[i];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) out[0] += s;
+}
+
+// vo_gan_reduce_multi: one wave per term, its partials added in the same order, written times the term's scale
 __global__ void __launch_bounds__(64) gan_multi_final_kernel(GanArgs A, const float* __restrict__ part,
                                                              const float* __restrict__ scale, float* __restrict__ out) {
   const int li = blockIdx.x;
@@ -577,74 +446,57 @@ __global__ void __launch_bounds__(256) gan_multi_grad_kernel(GanArgs A, const fl
   const int li = table_find(A.blk0, A.n, blockIdx.x);
   const GanTerm& T = A.t[li];
   const int64_t bi = blockIdx.x - A.blk0[li], gs = (int64_t)(A.blk0[li + 1] - A.blk0[li]) * 256;
-  const TA* a = reinterpret_cast<const TA*>(T.a);
-  const TA* b = reinterpret_cast<const TA*>(T.b);
-  TA* ga = reinterpret_cast<TA*>(T.ga);
   const float sc = scale[li];
-  if (T.v8) {
-    const RowMap rm{T.width / 8};
-    const int64_t nv = T.rows * rm.wv;
-    for (int64_t v = bi * 256 + threadIdx.x; v < nv; v += gs) {
-      int64_t r;
-      int c;
-      rm.at(v, &r, &c);
-      float x[8], g[8];
-      load8(a + r * T.lda + c, x);
-      if (T.kind == 0) {
-        float y[8];
-        load8(b + r * T.ldb + c, y);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = x[e] - y[e];
-          g[e] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
-        }
-      } else if (T.kind == 1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = -2.f * (1.f - x[e]) * sc;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = 2.f * x[e] * sc;
-      }
-      store8(ga + r * T.ldg + c, g);
-    }
-  } else {
-    const int64_t n = T.rows * T.width;
-    for (int64_t i = bi * 256 + threadIdx.x; i < n; i += gs) {
-      const int64_t r = i / T.width;
-      const int c = (int)(i - r * T.width);
-      const float x = to_f32(a[r * T.lda + c]);
-      float g;
-      if (T.kind == 0) {
-        const float d = x - to_f32(b[r * T.ldb + c]);
-        g = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
-      } else if (T.kind == 1) {
-        g = -2.f * (1.f - x) * sc;
-      } else {
-        g = 2.f * x * sc;
-      }
-      ga[r * T.ldg + c] = from_f32<TA>(g);
-    }
-  }
+  if (T.v8) gan_term_grad<TA, 8>(T, bi, gs, sc); else gan_term_grad<TA, 1>(T, bi, gs, sc);
 }
 
 static bool v8_ok(const void* p, int64_t ld) { return p == nullptr || (((uintptr_t)p & 15) == 0 && ld % 8 == 0); }
-// vo_pack_dgrad_phase and the GAN reductions read every dtype value but VO_BF16 as fp32
+// vo_pack_dgrad_phase, the GAN reductions and the input transforms read every dtype value but VO_BF16 as fp32
 static int bf16_else_f32(int dtype) { return dtype == VO_BF16 ? VO_BF16 : VO_F32; }
 
-
-// leaky-ReLU backward mask: out = g * (ref > 0 ? 1 : slope) over a (rows x width) view with
-// leading dimensions (out may alias g).  ref = the activation's input or its output (same sign
-// for slope > 0).  One launch instead of PyTorch's compare / where / cast / mul chain.
-template <typename TG, typename TR>
+// leaky-ReLU backward mask: out = g * (ref > 0 ? 1 : slope) over a (rows x width) view with leading dimensions
+// (out may alias g), in units of V elements; FLAT: no row is padded, no row split.  ref = the activation's input
+// or its output (same sign for slope > 0).  One launch instead of PyTorch's compare / where / cast / mul chain.
+// ADD 1: out = round(masked) + add[r, c] (then rounded): a residual's gradient summed in the same
+// pass -- bit for bit the masked tensor followed by autograd's add of the two gradients.
+// ADD 2: out = mask(round(g + add)): two gradients of the activation's output (the next conv's and a
+// feature-matching loss's) summed as autograd sums them, then masked
+template <typename TG, typename TR, int V, bool FLAT, int ADD = 0>
 __global__ void __launch_bounds__(256) lrelu_mask_kernel(const TG* __restrict__ g, int ldg, const TR* __restrict__ ref,
                                                          int ldr, int64_t rows, int width, float slope,
-                                                         TG* __restrict__ out, int ldo) {
-  const int64_t n = rows * width;
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / width;
-    const int c = (int)(i - r * width);
-    const float v = to_f32(g[r * ldg + c]);
-    out[r * ldo + c] = from_f32<TG>(to_f32(ref[r * ldr + c]) > 0.f ? v : v * slope);
+                                                         TG* __restrict__ out, int ldo,
+                                                         const TG* __restrict__ add = nullptr, int lda = 0) {
+  const RowMap<V> rm{width / V};
+  const int64_t nu = rows * rm.wv;
+  for (int64_t u = blockIdx.x * 256 + threadIdx.x; u < nu; u += (int64_t)gridDim.x * 256) {
+    int64_t og = u * V, orf = u * V, oo = u * V, oa = u * V;
+    if constexpr (!FLAT) {
+      int64_t r;
+      int c;
+      rm.at(u, &r, &c);
+      og = r * ldg + c;
+      orf = r * ldr + c;
+      oo = r * ldo + c;
+      oa = r * lda + c;
+    }
+    float x[V], q[V];
+    load_v<V>(g + og, x);
+    load_v<V>(ref + orf, q);
+    if constexpr (ADD == 2) {
+      float a[V];
+      load_v<V>(add + oa, a);
+#pragma unroll
+      for (int e = 0; e < V; ++e) x[e] = to_f32(from_f32<TG>(x[e] + a[e]));
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) x[e] = q[e] > 0.f ? x[e] : x[e] * slope;
+    if constexpr (ADD == 1) {
+      float a[V];
+      load_v<V>(add + oa, a);
+#pragma unroll
+      for (int e = 0; e < V; ++e) x[e] = to_f32(from_f32<TG>(x[e])) + a[e];
+    }
+    store_v<V>(out + oo, x);
   }
 }
 
@@ -859,11 +711,10 @@ extern "C" int vo_seq_remap2(int n, const VoRemapJob* jobs, int row_bytes, int d
   if (units == 0) return VO_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 g((unsigned)grid_for(units), (unsigned)n);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(seq_remap2_kernel<1>, g, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(seq_remap2_kernel<2>, g, dim3(256), 0, st, a);
-  VO_RETURN_LAUNCH();
+  return with_dtype(dtype, "seq_remap2", [&](auto t) {
+    hipLaunchKernelGGL(seq_remap2_kernel<decltype(t)::id == VO_BF16 ? 1 : 2>, g, dim3(256), 0, st, a);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_period_fold(const float* wav, int B, int T, int P, void* out, int dtype, void* stream) {
@@ -872,21 +723,21 @@ extern "C" int vo_period_fold(const float* wav, int B, int T, int P, void* out, 
   const int H = (T + P - 1) / P;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(grid_for((int64_t)P * H), B);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(period_fold_kernel<bf16_t>, grid, dim3(256), 0, st, wav, T, P, H, (bf16_t*)out);
-  else
-    hipLaunchKernelGGL(period_fold_kernel<float>, grid, dim3(256), 0, st, wav, T, P, H, (float*)out);
-  VO_RETURN_LAUNCH();
+  return with_dtype(bf16_else_f32(dtype), "period_fold", [&](auto td) {
+    using TD = typename decltype(td)::type;
+    hipLaunchKernelGGL(period_fold_kernel<TD>, grid, dim3(256), 0, st, wav, T, P, H, (TD*)out);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_wav_cl8(const float* wav, int64_t n, void* out, int dtype, void* stream) {
   VO_CHECK_ARG(wav && out && n > 0, "wav_cl8: bad arguments");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(wav_cl8_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, wav, n, (bf16_t*)out);
-  else
-    hipLaunchKernelGGL(wav_cl8_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, wav, n, (float*)out);
-  VO_RETURN_LAUNCH();
+  return with_dtype(bf16_else_f32(dtype), "wav_cl8", [&](auto td) {
+    using TD = typename decltype(td)::type;
+    hipLaunchKernelGGL(wav_cl8_kernel<TD>, dim3(grid_for(n)), dim3(256), 0, st, wav, n, (TD*)out);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_avgpool_wav(const float* x, int B, int T, float* y, void* stream) {
@@ -897,33 +748,8 @@ extern "C" int vo_avgpool_wav(const float* x, int B, int T, float* y, void* stre
   VO_RETURN_LAUNCH();
 }
 
-extern "C" int vo_gan_reduce(int kind, const void* a, int lda, const void* b, int ldb, int64_t rows, int width,
-                             int dtype, float* out, float* workspace, void* stream) {
-  VO_CHECK_ARG(a && out && workspace && kind >= 0 && kind <= 2 && (kind != 0 || b), "gan_reduce: bad arguments");
-  VO_CHECK_ARG(rows > 0 && width > 0 && lda >= width && (kind != 0 || ldb >= width), "gan_reduce: bad shape");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // at most 512 block partials (workspace: 512 floats), added in order by one wave (deterministic;
-  // the grid-stride loop keeps the loads coalesced)
-  const bool v8 = width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb);
-  const bool flat = lda == width && (!b || ldb == width);
-  const int g = std::min(grid_for(rows * (v8 ? width / 8 : width)), 512);
-  return with_dtype(bf16_else_f32(dtype), "gan_reduce", [&](auto ta) {
-    using TA = typename decltype(ta)::type;
-    if (v8)
-      with_bool(flat, [&](auto fl) {
-        hipLaunchKernelGGL((gan_reduce_v8_kernel<TA, decltype(fl)::value>), dim3(g), dim3(256), 0, st, kind,
-                           (const TA*)a, lda, (const TA*)b, ldb, rows, width, workspace);
-        return 0;
-      });
-    else
-      hipLaunchKernelGGL(gan_reduce_kernel<TA>, dim3(g), dim3(256), 0, st, kind, (const TA*)a, lda, (const TA*)b, ldb,
-                         rows, width, workspace);
-    hipLaunchKernelGGL(gan_reduce_final_kernel, dim3(1), dim3(64), 0, st, workspace, g, out);
-    VO_RETURN_LAUNCH();
-  });
-}
-
-// the term table of one launch: the block grid of each term as the single-term entry points size it
+// The term table of one launch.  A term's units are 8-element vectors where its rows allow (v8), else elements;
+// its grid is grid_for(units) blocks, the reduction's capped at its 512 partials.
 static int gan_multi_args(const VoGanTerm* terms, int n, bool grad, GanArgs* A, int* blocks) {
   int total = 0;
   for (int i = 0; i < n; ++i) {
@@ -957,59 +783,73 @@ extern "C" int vo_gan_reduce_multi(int n, const VoGanTerm* terms, int dtype, con
   VO_CHECK_ARG(n >= 0 && (n == 0 || (terms && out && workspace)) && (dtype == VO_BF16 || dtype == VO_F32),
                "gan_reduce_multi: bad arguments");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int i0 = 0; i0 < n; i0 += GT_MAX) {
-    GanArgs A;
-    int blocks;
-    const int m = std::min(GT_MAX, n - i0);
-    const int rc = gan_multi_args(terms + i0, m, false, &A, &blocks);
-    if (rc != VO_OK) return rc;
-    if (dtype == VO_BF16)
-      hipLaunchKernelGGL(gan_multi_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, A, workspace);
-    else
-      hipLaunchKernelGGL(gan_multi_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, A, workspace);
-    hipLaunchKernelGGL(gan_multi_final_kernel, dim3(m), dim3(64), 0, st, A, workspace, scale ? scale + i0 : nullptr,
-                       out + i0);
-  }
-  VO_RETURN_LAUNCH();
+  return with_dtype(dtype, "gan_reduce_multi", [&](auto ta) {
+    for (int i0 = 0; i0 < n; i0 += GT_MAX) {
+      GanArgs A;
+      int blocks;
+      const int m = std::min(GT_MAX, n - i0);
+      const int rc = gan_multi_args(terms + i0, m, false, &A, &blocks);
+      if (rc != VO_OK) return rc;
+      hipLaunchKernelGGL(gan_multi_reduce_kernel<typename decltype(ta)::type>, dim3(blocks), dim3(256), 0, st, A,
+                         workspace);
+      hipLaunchKernelGGL(gan_multi_final_kernel, dim3(m), dim3(64), 0, st, A, workspace, scale ? scale + i0 : nullptr,
+                         out + i0);
+    }
+    VO_RETURN_LAUNCH();
+  });
+}
+
+// One term: vo_gan_reduce_multi's reduction over a one-term table, its partials then added into *out
+extern "C" int vo_gan_reduce(int kind, const void* a, int lda, const void* b, int ldb, int64_t rows, int width,
+                             int dtype, float* out, float* workspace, void* stream) {
+  VO_CHECK_ARG(a && out && workspace && kind >= 0 && kind <= 2 && (kind != 0 || b), "gan_reduce: bad arguments");
+  VO_CHECK_ARG(rows > 0 && width > 0 && lda >= width && (kind != 0 || ldb >= width), "gan_reduce: bad shape");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const VoGanTerm term{kind, a, lda, b, ldb, rows, width, nullptr, 0};
+  GanArgs A;
+  int blocks;
+  const int rc = gan_multi_args(&term, 1, false, &A, &blocks);
+  if (rc != VO_OK) return rc;
+  return with_dtype(bf16_else_f32(dtype), "gan_reduce", [&](auto ta) {
+    hipLaunchKernelGGL(gan_multi_reduce_kernel<typename decltype(ta)::type>, dim3(blocks), dim3(256), 0, st, A,
+                       workspace);
+    hipLaunchKernelGGL(gan_reduce_final_kernel, dim3(1), dim3(64), 0, st, workspace, blocks, out);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_gan_reduce_grad_multi(int n, const VoGanTerm* terms, int dtype, const float* scale, void* stream) {
   VO_CHECK_ARG(n >= 0 && (n == 0 || (terms && scale)) && (dtype == VO_BF16 || dtype == VO_F32),
                "gan_reduce_grad_multi: bad arguments");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int i0 = 0; i0 < n; i0 += GT_MAX) {
-    GanArgs A;
-    int blocks;
-    const int m = std::min(GT_MAX, n - i0);
-    const int rc = gan_multi_args(terms + i0, m, true, &A, &blocks);
-    if (rc != VO_OK) return rc;
-    if (dtype == VO_BF16)
-      hipLaunchKernelGGL(gan_multi_grad_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, A, scale + i0);
-    else
-      hipLaunchKernelGGL(gan_multi_grad_kernel<float>, dim3(blocks), dim3(256), 0, st, A, scale + i0);
-  }
-  VO_RETURN_LAUNCH();
+  return with_dtype(dtype, "gan_reduce_grad_multi", [&](auto ta) {
+    for (int i0 = 0; i0 < n; i0 += GT_MAX) {
+      GanArgs A;
+      int blocks;
+      const int m = std::min(GT_MAX, n - i0);
+      const int rc = gan_multi_args(terms + i0, m, true, &A, &blocks);
+      if (rc != VO_OK) return rc;
+      hipLaunchKernelGGL(gan_multi_grad_kernel<typename decltype(ta)::type>, dim3(blocks), dim3(256), 0, st, A,
+                         scale + i0);
+    }
+    VO_RETURN_LAUNCH();
+  });
 }
 
+// One term: vo_gan_reduce_grad_multi's kernel over a one-term table
 extern "C" int vo_gan_reduce_grad(int kind, const void* a, int lda, const void* b, int ldb, int64_t rows, int width,
                                   int dtype, const float* scale, void* ga, int ldg, void* stream) {
   VO_CHECK_ARG(a && ga && scale && kind >= 0 && kind <= 2 && (kind != 0 || b), "gan_reduce_grad: bad arguments");
-  VO_CHECK_ARG(rows > 0 && width > 0 && lda >= width && ldg >= width, "gan_reduce_grad: bad shape");
+  VO_CHECK_ARG(rows > 0 && width > 0 && lda >= width && (kind != 0 || ldb >= width) && ldg >= width,
+               "gan_reduce_grad: bad shape");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool v8 = width % 8 == 0 && v8_ok(a, lda) && v8_ok(b, ldb) && v8_ok(ga, ldg);
-  const bool flat = lda == width && (!b || ldb == width) && ldg == width;
-  const int g = grid_for(rows * (v8 ? width / 8 : width));
+  const VoGanTerm term{kind, a, lda, b, ldb, rows, width, ga, ldg};
+  GanArgs A;
+  int blocks;
+  const int rc = gan_multi_args(&term, 1, true, &A, &blocks);
+  if (rc != VO_OK) return rc;
   return with_dtype(bf16_else_f32(dtype), "gan_reduce_grad", [&](auto ta) {
-    using TA = typename decltype(ta)::type;
-    if (v8)
-      with_bool(flat, [&](auto fl) {
-        hipLaunchKernelGGL((gan_reduce_grad_v8_kernel<TA, decltype(fl)::value>), dim3(g), dim3(256), 0, st, kind,
-                           (const TA*)a, lda, (const TA*)b, ldb, rows, width, scale, (TA*)ga, ldg);
-        return 0;
-      });
-    else
-      hipLaunchKernelGGL(gan_reduce_grad_kernel<TA>, dim3(g), dim3(256), 0, st, kind, (const TA*)a, lda, (const TA*)b,
-                         ldb, rows, width, scale, (TA*)ga, ldg);
+    hipLaunchKernelGGL(gan_multi_grad_kernel<typename decltype(ta)::type>, dim3(blocks), dim3(256), 0, st, A, scale);
     VO_RETURN_LAUNCH();
   });
 }
@@ -1027,22 +867,22 @@ static int lrelu_mask_launch(const char* who, const void* g, int ldg, int g_dtyp
   return with_dtypes(g_dtype, ref_dtype, who, [&](auto tg, auto tr) {
     using TG = typename decltype(tg)::type;
     using TR = typename decltype(tr)::type;
-    auto v8_form = [&](auto fl, auto mode) {
-      hipLaunchKernelGGL((lrelu_mask_v8_kernel<TG, TR, decltype(fl)::value, decltype(mode)::value>), dim3(gr),
-                         dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref, ldr, rows, width, slope, (TG*)out, ldo,
-                         (const TG*)add, lda);
+    using std::integral_constant;
+    auto form = [&](auto v, auto fl, auto mode) {
+      hipLaunchKernelGGL((lrelu_mask_kernel<TG, TR, decltype(v)::value, decltype(fl)::value, decltype(mode)::value>),
+                         dim3(gr), dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref, ldr, rows, width, slope,
+                         (TG*)out, ldo, (const TG*)add, lda);
       return 0;
     };
-    using std::integral_constant;
+    const integral_constant<int, 8> vec;
     if (!v8)
-      hipLaunchKernelGGL((lrelu_mask_kernel<TG, TR>), dim3(gr), dim3(256), 0, st, (const TG*)g, ldg, (const TR*)ref,
-                         ldr, rows, width, slope, (TG*)out, ldo);
+      form(integral_constant<int, 1>{}, std::false_type{}, integral_constant<int, 0>{});
     else if (!add)
-      with_bool(flat, [&](auto fl) { return v8_form(fl, integral_constant<int, 0>{}); });
+      with_bool(flat, [&](auto fl) { return form(vec, fl, integral_constant<int, 0>{}); });
     else if (presum)
-      v8_form(std::false_type{}, integral_constant<int, 2>{});
+      form(vec, std::false_type{}, integral_constant<int, 2>{});
     else
-      v8_form(std::false_type{}, integral_constant<int, 1>{});
+      form(vec, std::false_type{}, integral_constant<int, 1>{});
     VO_RETURN_LAUNCH();
   });
 }
@@ -1083,23 +923,21 @@ extern "C" int vo_period_fold_bwd(const void* g, int dtype, int B, int T, int P,
   VO_CHECK_ARG(g && gwav && B > 0 && P >= 1 && T > P, "period_fold_bwd: bad arguments");
   const int H = (T + P - 1) / P;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(period_fold_bwd_kernel<bf16_t>, dim3(grid_for(T), B), dim3(256), 0, st, (const bf16_t*)g, T, P,
-                       H, gwav);
-  else
-    hipLaunchKernelGGL(period_fold_bwd_kernel<float>, dim3(grid_for(T), B), dim3(256), 0, st, (const float*)g, T, P, H,
-                       gwav);
-  VO_RETURN_LAUNCH();
+  return with_dtype(bf16_else_f32(dtype), "period_fold_bwd", [&](auto tg) {
+    using TG = typename decltype(tg)::type;
+    hipLaunchKernelGGL(period_fold_bwd_kernel<TG>, dim3(grid_for(T), B), dim3(256), 0, st, (const TG*)g, T, P, H, gwav);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_wav_cl8_bwd(const void* g, int dtype, int64_t n, float* gwav, void* stream) {
   VO_CHECK_ARG(g && gwav && n > 0, "wav_cl8_bwd: bad arguments");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VO_BF16)
-    hipLaunchKernelGGL(wav_cl8_bwd_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16_t*)g, n, gwav);
-  else
-    hipLaunchKernelGGL(wav_cl8_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)g, n, gwav);
-  VO_RETURN_LAUNCH();
+  return with_dtype(bf16_else_f32(dtype), "wav_cl8_bwd", [&](auto tg) {
+    using TG = typename decltype(tg)::type;
+    hipLaunchKernelGGL(wav_cl8_bwd_kernel<TG>, dim3(grid_for(n)), dim3(256), 0, st, (const TG*)g, n, gwav);
+    VO_RETURN_LAUNCH();
+  });
 }
 
 extern "C" int vo_avgpool_wav_bwd(const float* g, int B, int T, float* gx, void* stream) {

@@ -1517,7 +1517,8 @@ def _gan_terms(kinds, As, Bs, outs=None):
 
 def gan_reduce_multi(kinds, As, Bs, scale=None):
     """[gan_reduce(kinds[i], As[i], Bs[i])] * scale as one (n,) fp32 vector in one launch pair
-    (vo_gan_reduce_multi; each sum bit for bit gan_reduce's).  ``scale``: (n,) fp32 device vector."""
+    (vo_gan_reduce_multi; gan_reduce runs the same kernel with a table of one term, so each sum is
+    gan_reduce's bit for bit).  ``scale``: (n,) fp32 device vector."""
     n = len(kinds)
     arr, keep = _gan_terms(kinds, As, Bs)
     out = torch.empty(n, dtype=torch.float32, device=As[0].device)
@@ -1531,8 +1532,8 @@ def gan_reduce_multi(kinds, As, Bs, scale=None):
 
 
 def gan_reduce_grad_multi(kinds, As, Bs, scale, outs=None):
-    """[gan_reduce_grad(kinds[i], As[i], Bs[i], scale[i])] in one launch (vo_gan_reduce_grad_multi);
-    ``outs``: contiguous tensors to write them into (default: new tensors shaped like As)."""
+    """[gan_reduce_grad(kinds[i], As[i], Bs[i], scale[i])] in one launch (vo_gan_reduce_grad_multi, the kernel
+    gan_reduce_grad runs with a table of one term); ``outs``: contiguous tensors to write them into (default: new tensors shaped like As)."""
     if outs is None:
         outs = [torch.empty(a.shape, dtype=a.dtype, device=a.device) for a in As]
     arr, keep = _gan_terms(kinds, As, Bs, outs)
