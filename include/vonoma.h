@@ -985,6 +985,45 @@ int vo_segment_batch(const vo_corpus* c, const vo_wave_corpus* w, const int32_t*
 int vo_segment_plan(const vo_corpus* c, const int32_t* order, int n_order, int64_t* counter, uint64_t seed, int B,
                     int fps, int32_t* plan, void* stream);
 
+/* Sample-rate conversion (additive): band-limited interpolation with a Kaiser-windowed sinc,
+ * in front of the mel front end (the reference's librosa.load(path, sr=22050), scripts/preprocessor/preprocessor.py:385,
+ * and its wav[int(sr * start):], :391) and behind the vocoder.  The rule is this project's own:
+ *   constants   Z = 64 zero crossings, ROLLOFF = 0.9475937167399596, BETA = 14.769656459379492;
+ *   geometry    g = gcd(sr_in, sr_out), O = sr_in / g, M = sr_out / g; c = min(O, M) ROLLOFF / O; W = ceil(Z / c) the
+ *               half width in input samples; T = 2 W + 1 taps.  48000 -> 22050: O, M, W, T = 320, 147, 148, 297;
+ *               22050 -> 48000: 147, 320, 68, 137;
+ *   supported   O, M <= 1024, O / M <= 8, sr_in != sr_out.  Every other pair is refused with a message naming the
+ *               reduced pair and the limits; no nearby ratio is ever run in its place;
+ *   table       (M, T) fp32 row-major, computed in double and rounded once: with t = c (j - W - r / M),
+ *               h[r][j] = c sinc(t) I0(BETA sqrt(1 - (t / Z)^2)) / I0(BETA) for |t| < Z, else 0; sinc(t) = sin(pi t) /
+ *               (pi t), sinc(0) = 1;
+ *   output n    of a row x of n_b samples (x[k] = 0 outside [0, n_b)): q = (n O) div M, r = (n O) mod M in 64 bits,
+ *               res[n] = sum_j h[r][j] x[q - W + j] in fp32, j ascending in one fused multiply-add chain;
+ *   length      L_b = ceil(n_b M / O), in 64 bits.
+ *
+ * Host only, like vo_conv1d_plan (no HIP call, no GPU needed): vo_resample_geometry gives O, M, W of two rates
+ * (VO_ERR_INVALID for a refused pair or a rate < 1), vo_resample_len gives L of n samples (0 for n <= 0), and
+ * vo_resample_table fills the M T coefficients of a reduced pair into host memory.
+ *
+ * vo_resample: x (B, N) with row stride N, fp32 or int16 (x_is_int16; a sample s is read as (float)s / max_wav_value,
+ * one IEEE division, as vo_segment_batch reads it); lens (B) device int32 or NULL (every row is N): n_b =
+ * clamp(lens[b], 0, N), and no sample at or past n_b is read; skip (B) device int32 or NULL (0): output samples
+ * dropped from the front, clamped on the device to [0, L_b]; table: the device copy of vo_resample_table(O, M).  With
+ * m_b = clamp(L_b - skip_b, 0, N_out): y[b, i] = res_b[i + skip_b] for i < m_b and 0.0f (int16 0) for m_b <= i <
+ * N_out -- every element of y (B, N_out) is written -- and out_lens[b] = m_b (NULL: not wanted).  y is fp32, or int16
+ * (y_is_int16) stored by the rule of vo_conv_post_pcm16: clamp(trunc(v pcm_scale)), NaN -> 0.  An output's bits
+ * depend on its row's n_b samples, on n and on the table alone: not on the batch, the tile, skip, N, N_out or the
+ * element types.  One launch, allocates nothing, never synchronises, reads nothing on the host: graph-capturable, and
+ * a replay follows x, lens and skip rewritten in place.  VO_ERR_INVALID, nothing launched: a null x, y or table; B
+ * outside [1, 65535]; N < 1 or N_out < 1 (or N_out within 256 of 2^31); an (O, M) the geometry refuses or that is not
+ * reduced; max_wav_value (int16 input) or pcm_scale (int16 output) not finite and positive. */
+int vo_resample_geometry(int64_t sr_in, int64_t sr_out, int32_t* O, int32_t* M, int32_t* W);
+int64_t vo_resample_len(int64_t n, int O, int M);
+int vo_resample_table(int O, int M, float* host_out);
+int vo_resample(const void* x, int x_is_int16, float max_wav_value, int B, int N, const int32_t* lens,
+                const int32_t* skip, const float* table, int O, int M, void* y, int y_is_int16, float pcm_scale,
+                int N_out, int32_t* out_lens, void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Multi-tensor Adam (decoupled = 0: L2 weight decay on the gradient) / AdamW (decoupled = 1) step over
  * nt fp32 tensors (tables of device pointers and element counts, host memory), torch's

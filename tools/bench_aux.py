@@ -20,7 +20,10 @@
   numpy crops of the same rows and their upload.  ``segments-c5`` (only when named): the C5 training step replayed
   with the batch drawn inside the graph against the replay over static tensors.
 
-    python tools/bench_aux.py [glyph] [features] [augment] [stats] [segments] [--out FILE]   (these five by default)
+* sample-rate conversion (vo_resample): 64 rows of 2 s of int16 PCM at 48 kHz -> fp32 at 22.05 kHz in one launch,
+  the achieved fp32 rate beside the vector peak and the byte bound, and the upload of the same batch for scale.
+
+    python tools/bench_aux.py [glyph] [features] [augment] [stats] [segments] [resample] [--out FILE]   (these six by default)
     rocprofv3 --kernel-trace --stats ... -- python tools/bench_aux.py augment --kernels 200   (launches only)
 """
 import json
@@ -37,6 +40,7 @@ for p in (REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "tests", "golden
         sys.path.insert(0, p)
 
 HBM_PEAK_GBS = 8000.0
+FP32_VECTOR_PEAK_TFLOPS = 157.3  # the spec figure: packed FMA on every lane; a scalar-FMA loop can reach half of it
 
 
 def timed(fn, n):
@@ -440,13 +444,63 @@ def segments_c5():
                     "the static buffers; the static path's two copies are outside its graph"}
 
 
+def resample():
+    """vo_resample at the corpus ingestion shape: B = 64 rows of 2 s at 48000 -> 22050, int16
+    in, fp32 out.  Device events over back-to-back launches, five windows, at least 0.5 s of work in all."""
+    import statistics
+    from visual_onoma_to_wave_amd import ops
+    dev = torch.device("cuda")
+    B, N, sr_in, sr_out = 64, 96000, 48000, 22050
+    O, M, W = ops.resample_geometry(sr_in, sr_out)
+    T = 2 * W + 1
+    rng = np.random.default_rng(17)
+    host = torch.from_numpy(rng.integers(-16384, 16385, (B, N)).astype(np.int16))
+    pinned = host.pin_memory()
+    x = host.to(dev)
+    L = ops.resample_len(N, O, M)
+    out = torch.empty((B, L), dtype=torch.float32, device=dev)
+    run = lambda: ops.resample(x, sr_in, sr_out, out=out)  # noqa: E731
+    run()
+    torch.cuda.synchronize()
+    t1 = timed(run, 20)
+    n = max(20, int(0.12 / t1) + 1)  # 0.12 s a window: 0.6 s of work in all
+    t_call = [timed(run, n) for _ in range(5)]
+    stage = torch.empty_like(x)
+
+    def upload():
+        stage.copy_(pinned, non_blocking=True)
+    t_up = [timed(upload, 50) for _ in range(5)]
+    med = statistics.median
+    t = med(t_call)
+    flops = 2.0 * T * B * L
+    table_bytes = M * T * 4
+    moved = B * N * 2 + B * L * 4 + table_bytes
+    tf = flops / t / 1e12
+    return {"metric": "sample-rate conversion 48000 -> 22050 on the device (DESIGN.md 17)", "unit": "us/call",
+            "value": round(t * 1e6, 1),
+            "config": {"rows": B, "samples_in": N, "samples_out": L, "taps": T, "input": "int16", "output": "fp32",
+                       "calls_per_window": n, "windows": 5},
+            "call_us_min_max": [round(min(t_call) * 1e6, 1), round(max(t_call) * 1e6, 1)],
+            "fp32": {"tflops": round(tf, 2), "vector_peak_tflops": FP32_VECTOR_PEAK_TFLOPS,
+                     "fraction_of_peak": round(tf / FP32_VECTOR_PEAK_TFLOPS, 4),
+                     "bound_us": round(flops / (FP32_VECTOR_PEAK_TFLOPS * 1e12) * 1e6, 1)},
+            "bytes": {"algorithmic": moved, "bound_us": round(moved / (HBM_PEAK_GBS * 1e9) * 1e6, 2),
+                      "note": "int16 in + fp32 out + the table once, at the HBM peak"},
+            "bounded_by": "fp32" if flops / (FP32_VECTOR_PEAK_TFLOPS * 1e12) > moved / (HBM_PEAK_GBS * 1e9)
+            else "bytes",
+            "seconds_of_audio_per_second": round(B * N / sr_in / t, 1),
+            "upload": {"pinned_h2d_us": round(med(t_up) * 1e6, 1),
+                       "us_min_max": [round(min(t_up) * 1e6, 1), round(max(t_up) * 1e6, 1)],
+                       "note": "the same (64, 96000) int16 batch from pinned host memory, for scale"}}
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     out = args.pop(args.index("--out") + 1) if "--out" in args else None
     kernels = int(args.pop(args.index("--kernels") + 1)) if "--kernels" in args else 0
     args = [a for a in args if a not in ("--out", "--kernels")]
     which = {"glyph": glyph, "features": features, "augment": (lambda: augment(kernels)) if kernels else augment,
-             "stats": stats, "segments": segments, "segments-c5": segments_c5}
+             "stats": stats, "segments": segments, "resample": resample, "segments-c5": segments_c5}
     lines = [json.dumps(which[k]()) for k in (args or [k for k in which if k != "segments-c5"])]
     print("\n".join(lines))
     if out:

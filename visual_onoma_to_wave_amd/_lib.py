@@ -298,6 +298,11 @@ _SIGNATURES = {
                                  c_float] + [c_void_p] * 5),
     "vo_segment_plan": (c_int, [ctypes.POINTER(Corpus), c_void_p, c_int, c_void_p, ctypes.c_uint64, c_int, c_int,
                                 c_void_p, c_void_p]),
+    "vo_resample_geometry": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "vo_resample_len": (c_int64, [c_int64, c_int, c_int]),
+    "vo_resample_table": (c_int, [c_int, c_int, c_void_p]),
+    "vo_resample": (c_int, [c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                            c_void_p, c_int, c_float, c_int, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION

@@ -82,6 +82,52 @@ def pad_waves(wavs):
     return torch.from_numpy(out), torch.from_numpy(lens)
 
 
+def read_wav(path):
+    """A PCM ``.wav`` file -> (samples, rate), with the standard library's ``wave``.  16-bit mono comes back as the
+    file holds it, int16 (N,); several channels are averaged in float32 on the host (librosa's ``mono=True``: the
+    samples / 32768, then the mean), a float32 (N,) array.  Any other sample width is a ValueError naming the file."""
+    import wave
+    with wave.open(str(path), "rb") as f:
+        width, channels, rate, n = f.getsampwidth(), f.getnchannels(), f.getframerate(), f.getnframes()
+        if width != 2:
+            raise ValueError(f"read_wav: {path}: {8 * width}-bit samples (16-bit PCM only)")
+        data = np.frombuffer(f.readframes(n), dtype="<i2").astype(np.int16, copy=False)
+    if channels == 1:
+        return data.copy(), rate
+    frames = data[:data.size // channels * channels].reshape(-1, channels)
+    return (frames.astype(np.float32) / np.float32(32768.0)).mean(axis=1, dtype=np.float32), rate
+
+
+def resample_length(n, sr_in, sr_out):
+    """The samples ``n`` samples at ``sr_in`` become at ``sr_out``: ceil(n M / O) of the reduced rates (n itself
+    for equal rates)."""
+    if int(sr_in) == int(sr_out):
+        return int(n)
+    O, M, _ = ops.resample_geometry(sr_in, sr_out)
+    return ops.resample_len(n, O, M)
+
+
+class Resample:
+    """Sample-rate conversion on HIP (``ops.resample``: a Kaiser-windowed sinc of 64 zero crossings, the parameters
+    torchaudio documents for ``sinc_interp_kaiser`` as resampy's ``kaiser_best``).  The rates are checked here: a
+    ratio the library does not run is a ValueError at construction."""
+
+    def __init__(self, sr_in, sr_out):
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.geometry = None if self.sr_in == self.sr_out else ops.resample_geometry(self.sr_in, self.sr_out)
+
+    def __call__(self, wav, lengths=None, skip=None):
+        """wav (N,) or (B, N), fp32 or int16 (read as s / 32768), on the GPU -> (wav, lengths) at ``sr_out``: fp32
+        (N',) / (B, N') with N' = resample_length(N) and the device int32 sample counts of the rows, zeros past
+        them.  ``lengths`` / ``skip`` (output samples dropped from the front): as ``ops.resample`` takes them.
+        With equal rates the input comes back untouched, with ``lengths`` as given."""
+        if self.geometry is None:
+            return wav, lengths
+        squeeze = wav.dim() == 1
+        y, n = ops.resample(wav.reshape(1, -1) if squeeze else wav, self.sr_in, self.sr_out, lens=lengths, skip=skip)
+        return (y[0], n[0]) if squeeze else (y, n)
+
+
 class MelSpectrogram:
     """Spectrogram(n_fft, win_length, hop, power=1, center=True) -> MelScale -> log, on HIP."""
 

@@ -101,6 +101,7 @@ static const char* const kSymbols[] = {
     "vo_augment_batch",
     "vo_corpus_stats_workspace_size", "vo_corpus_stats", "vo_corpus_normalize",
     "vo_segment_batch", "vo_segment_plan",
+    "vo_resample_geometry", "vo_resample_len", "vo_resample_table", "vo_resample",
 };
 
 extern "C" int vo_num_symbols(void) { return (int)(sizeof(kSymbols) / sizeof(kSymbols[0])); }

@@ -18,28 +18,6 @@ namespace vo {
 
 constexpr int CP_ROWS = 256;
 
-// How a conv_post kernel stores a sample, by the output element type TY.  float: the value itself (the struct is
-// empty, so the fp32 instantiations are the kernels they were).  int16_t: q = (int16) clamp(trunc(v * scale), -32768,
-// 32767), the product in fp32 -- the host's (wav * max_wav_value).astype("int16") for values in range.  Deliberate
-// deviation: tanhf gives exactly +-1.0f for large inputs and 1.0f * 32768 is outside int16, where the host cast is
-// undefined (it wraps to -32768, a click); this stores 32767.  NaN stores 0.  Element stores only: a row of y is
-// 2-byte aligned when T is odd.
-template <typename TY>
-struct PostStore;
-template <>
-struct PostStore<float> {
-  __device__ float operator()(float v) const { return v; }
-};
-template <>
-struct PostStore<int16_t> {
-  float scale;
-  __device__ int16_t operator()(float v) const {
-    const float p = v * scale;
-    // fminf / fmaxf return the non-NaN operand, so a NaN is caught first; both bounds are exact in fp32
-    return (p != p) ? (int16_t)0 : (int16_t)(int)truncf(fminf(fmaxf(p, -32768.f), 32767.f));
-  }
-};
-
 // CC > 0: compile-time channel count (HiFi-GAN V1: 32) -- the staging loads are then issued
 // as one batch (a runtime-trip loop serialises one HBM round trip per iteration); CC = 0:
 // any C (multiple of 8).

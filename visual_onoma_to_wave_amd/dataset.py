@@ -387,16 +387,26 @@ class DeviceCorpus:
         self.waves = None
         return self
 
-    def attach_waves(self, wavs, hop, max_wav_value=32768.0):
+    def attach_waves(self, wavs, hop, max_wav_value=32768.0, sr=None, target_sr=None, start=None):
         """The base utterances' waveforms beside their mels, for the vocoder's training batches
         (``hifigan.data.SegmentSampler``): ``wavs`` is one 1-D array per utterance in corpus
         order, all int16 (PCM as the files hold it, kept as int16 and divided by ``max_wav_value`` when a segment is
         cut) or all floating point (kept as fp32, copied as they are).  Packed once, flat, every utterance at a sample
         offset that is a multiple of 8.  ``hop``: the hop of the corpus's mels; utterance u of N samples and F frames
         must have 1 + N // hop >= F, what ``FeatureExtractor.process`` requires of a waveform and its durations.
-        ValueError naming the utterance otherwise.  Sets ``self.waves`` (``_lib.WaveCorpus``) and returns self."""
+        ValueError naming the utterance otherwise.  Sets ``self.waves`` (``_lib.WaveCorpus``) and returns self.
+
+        ``sr`` (an int, or one per utterance): the rate the arrays are at, with ``target_sr`` the rate of the corpus's
+        mels.  Where the two differ the waveforms are resampled on the device (``ops.resample``, one launch per source
+        rate) and the corpus holds fp32, whatever came in; ``start`` (seconds, one per
+        utterance) drops the first ``int(target_sr * start)`` resampled samples, as ``FeatureExtractor.process``
+        does.  The frame check then uses the resampled, trimmed length.  Without ``sr`` the call is what it was."""
         import torch
         from . import _lib
+        if sr is None and (target_sr is not None or start is not None):
+            raise ValueError("DeviceCorpus.attach_waves: target_sr and start go with sr, the rate of the arrays")
+        if sr is not None and target_sr is None:
+            raise ValueError("DeviceCorpus.attach_waves: sr needs target_sr, the rate of the corpus's mels")
         hop, max_wav_value = int(hop), float(max_wav_value)
         if hop < 1:
             raise ValueError(f"DeviceCorpus.attach_waves: hop must be >= 1, got {hop}")
@@ -418,23 +428,73 @@ class DeviceCorpus:
             if (a.dtype == np.int16) != is_int16:
                 raise ValueError(f"{who}: the waveform is {a.dtype}, the ones before it are "
                                  f"{'int16' if is_int16 else 'floating point'} (all int16 or all floating point)")
-            if 1 + a.size // hop < self.n_frames[i]:
-                raise ValueError(f"{who}: {a.size} samples are 1 + N // hop = {1 + a.size // hop} frames at hop {hop}, "
-                                 f"the mel has {self.n_frames[i]}")
             arrays.append(a)
+        if sr is not None:
+            arrays = self._resampled(arrays, is_int16, max_wav_value, sr, int(target_sr), start)
+            is_int16 = is_int16 and not torch.is_tensor(arrays[0])
+        for i, a in enumerate(arrays):
+            size = a.numel() if torch.is_tensor(a) else a.size
+            if size < 1 or 1 + size // hop < self.n_frames[i]:
+                raise ValueError(f"DeviceCorpus.attach_waves: utterance {i} ({self.names[i]!r}): {size} samples are "
+                                 f"1 + N // hop = {1 + size // hop} frames at hop {hop}, the mel has "
+                                 f"{self.n_frames[i]}")
         dtype = np.int16 if is_int16 else np.float32
-        n = np.asarray([a.size for a in arrays], np.int64)
+        n = np.asarray([a.numel() if torch.is_tensor(a) else a.size for a in arrays], np.int64)
         off = np.concatenate([[0], np.cumsum((n + 7) // 8 * 8)]).astype(np.int64)
-        flat = np.zeros(int(off[-1]), dtype)
-        for a, o in zip(arrays, off):
-            flat[o:o + a.size] = a
+        if torch.is_tensor(arrays[0]):  # resampled: fp32 rows on the device already
+            flat = torch.zeros(int(off[-1]), dtype=torch.float32, device=self.device)
+            for a, o in zip(arrays, off):
+                flat[o:o + a.numel()] = a
+        else:
+            flat = np.zeros(int(off[-1]), dtype)
+            for a, o in zip(arrays, off):
+                flat[o:o + a.size] = a
+            flat = torch.from_numpy(flat).to(self.device)
         self.n_samples = [int(v) for v in n]
         self.wave_hop = hop
-        self.wave_tensors = {k: torch.from_numpy(a).to(self.device)
-                             for k, a in (("sample_off", off), ("n_samples", n), ("wav", flat))}
+        self.wave_tensors = {"sample_off": torch.from_numpy(off).to(self.device),
+                             "n_samples": torch.from_numpy(n).to(self.device), "wav": flat}
         self.waves = _lib.WaveCorpus(U=len(self), is_int16=int(is_int16), max_wav_value=max_wav_value,
                                      **{k: t.data_ptr() for k, t in self.wave_tensors.items()})
         return self
+
+    def _resampled(self, arrays, is_int16, max_wav_value, sr, target_sr, start):
+        """``attach_waves`` with ``sr``: the validated host arrays -> one fp32 device row per utterance at
+        ``target_sr``, or the arrays themselves when every rate already is ``target_sr`` and nothing is trimmed.  The
+        lengths are computed on the host (``ops.resample_len``): nothing is read back."""
+        import torch
+        from . import ops
+        U = len(arrays)
+        rates = [int(sr)] * U if np.ndim(sr) == 0 else [int(r) for r in sr]
+        starts = [0.0] * U if start is None else [float(v) for v in start]
+        if len(rates) != U or len(starts) != U:
+            raise ValueError(f"DeviceCorpus.attach_waves: {U} utterances, {len(rates)} rates, {len(starts)} start "
+                             "times")
+        if any(not (v >= 0.0 and v < float("inf")) for v in starts):
+            raise ValueError(f"DeviceCorpus.attach_waves: start times must be finite and >= 0, got {starts}")
+        skips = [int(target_sr * v) for v in starts]
+        if all(r == target_sr for r in rates) and not any(skips):
+            return arrays
+        geo = {r: ops.resample_geometry(r, target_sr) for r in set(rates) - {target_sr}}  # refusals first
+        rows = [None] * U
+        for rate in sorted(set(rates)):
+            idx = [i for i, r in enumerate(rates) if r == rate]
+            if rate == target_sr:  # trimmed on the host, read as the kernel reads them
+                for i in idx:
+                    a = arrays[i][skips[i]:]
+                    a = a.astype(np.float32) / np.float32(max_wav_value) if is_int16 else a.astype(np.float32)
+                    rows[i] = torch.from_numpy(a).to(self.device)
+                continue
+            x = np.zeros((len(idx), max(arrays[i].size for i in idx)), np.int16 if is_int16 else np.float32)
+            for k, i in enumerate(idx):
+                x[k, :arrays[i].size] = arrays[i]
+            y, _ = ops.resample(torch.from_numpy(x).to(self.device), rate, target_sr,
+                                lens=[arrays[i].size for i in idx], skip=[skips[i] for i in idx],
+                                max_wav_value=max_wav_value if is_int16 else None)
+            for k, i in enumerate(idx):
+                L = max(ops.resample_len(arrays[i].size, *geo[rate][:2]) - skips[i], 0)
+                rows[i] = y[k, :L]
+        return rows
 
     @classmethod
     def from_dataset(cls, ds, indices=None, base_only=True, device="cuda"):

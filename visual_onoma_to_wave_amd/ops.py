@@ -1829,6 +1829,112 @@ def segment_plan(corpus, order, counter, seed, B, fps, plan=None):
     return plan
 
 
+# ----------------------------------------------------------------------------- sample-rate conversion
+
+RESAMPLE_TILE = 256  # the outputs one workgroup of resample_kernel writes (RS_TILE, csrc/resample.hip)
+_RESAMPLE_TABLES = {}
+
+
+def resample_geometry(sr_in, sr_out):
+    """(O, M, W) of a conversion from ``sr_in`` to ``sr_out`` (vo_resample_geometry, host only): the reduced rates
+    and the filter's half width in input samples; T = 2 W + 1 taps.  ValueError, with the library's message naming
+    the reduced pair and the limits, for equal rates, a rate < 1, O or M above 1024 and O / M above 8."""
+    L = _lib.lib()
+    O, M, W = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    if L.vo_resample_geometry(int(sr_in), int(sr_out), ctypes.byref(O), ctypes.byref(M), ctypes.byref(W)) != 0:
+        raise ValueError(L.vo_last_error().decode(errors="replace"))
+    return O.value, M.value, W.value
+
+
+def resample_len(n, O, M):
+    """ceil(n M / O): the samples ``n`` input samples become (vo_resample_len, host only)."""
+    return int(_lib.lib().vo_resample_len(int(n), int(O), int(M)))
+
+
+def resample_table(O, M, device=None):
+    """The (M, 2 W + 1) fp32 coefficients of the reduced pair (vo_resample_table: double, rounded once).  With
+    ``device`` the copy on that device, built once and cached; without, a new host tensor."""
+    if device is not None:
+        key = (O, M, str(torch.device(device)))
+        if key not in _RESAMPLE_TABLES:
+            _RESAMPLE_TABLES[key] = resample_table(O, M).to(device)
+        return _RESAMPLE_TABLES[key]
+    W = resample_geometry(O, M)[2]  # refuses what the library does not run; (O, M) must already be reduced
+    t = torch.empty((M, 2 * W + 1), dtype=torch.float32)
+    _lib.check(_lib.lib().vo_resample_table(O, M, ctypes.c_void_p(t.data_ptr())), "vo_resample_table")
+    return t
+
+
+def _resample_rows(v, B, hi, ref, name):
+    """``lens`` / ``skip`` of ``resample`` -> contiguous int32 (B,) on ``ref``'s device.  A device tensor (int32 /
+    int64) is converted on the device and never read on the host (the kernel clamps it); a host sequence is
+    validated here: B integers in [0, hi]."""
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        if v.dtype not in (torch.int32, torch.int64) or v.shape != (B,):
+            raise ValueError(f"resample: {name} must be an int32 / int64 tensor of shape ({B},), got {v.dtype} "
+                             f"{tuple(v.shape)}")
+        if v.device != ref.device:
+            raise ValueError(f"resample: {name} is on {v.device}, the waveform on {ref.device}")
+        return v.to(torch.int32).contiguous()
+    host = [int(a) for a in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+    if len(host) != B or any(a < 0 or a > hi for a in host):
+        raise ValueError(f"resample: {name} must be {B} sample counts in [0, {hi}], got {host}")
+    return torch.tensor(host, dtype=torch.int32).to(ref.device)
+
+
+def resample(x, sr_in, sr_out, lens=None, skip=None, max_wav_value=None, pcm_scale=None, out=None,
+             out_capacity=None):
+    """Sample-rate conversion of a ragged batch in one launch (vo_resample; include/vonoma.h states the rule: a
+    Kaiser-windowed sinc of 64 zero crossings): x (B, N) fp32, or int16 read as s / ``max_wav_value`` (32768.0 by
+    default), at ``sr_in`` -> (y, out_lens) at ``sr_out``.  Row b holds ``lens[b]`` samples (None: N) and loses its
+    first ``skip[b]`` output samples (None: 0; clamped to the row's length).  y is (B, N_out) with N_out =
+    ``out_capacity``, or ``out``'s, or resample_len(N): fp32, or int16 with ``pcm_scale`` (the store of
+    ``Generator.run(pcm_scale=...)``); row b holds out_lens[b] = clamp(ceil(lens[b] M / O) - skip[b], 0, N_out)
+    samples, then zeros.  out_lens is int32 (B,) on the device.  ``lens`` and ``skip``: int32 / int64 device
+    tensors, never read on the host (the call is graph-capturable and a replay follows them, and x, changed in
+    place), or host sequences, which are validated.  Equal rates are a ValueError: there is nothing to launch."""
+    if not (torch.is_tensor(x) and x.dim() == 2 and x.dtype in (torch.float32, torch.int16)):
+        raise ValueError("resample: x must be an fp32 or int16 (B, N) tensor, got "
+                         f"{(x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__}")
+    st = _stream(x)
+    _contig(x, "x")
+    O, M, _ = resample_geometry(sr_in, sr_out)
+    B, N = x.shape
+    if not 1 <= B <= 65535 or N < 1:
+        raise ValueError(f"resample: x is {(B, N)}: B must be in [1, 65535] and N >= 1")
+    is16 = x.dtype == torch.int16
+    if max_wav_value is not None and not is16:
+        raise ValueError("resample: max_wav_value belongs to int16 input, x is fp32")
+    mwv = 32768.0 if max_wav_value is None else float(max_wav_value)
+    if not (0.0 < mwv < float("inf")):
+        raise ValueError(f"resample: max_wav_value must be finite and positive, got {max_wav_value}")
+    if pcm_scale is not None and not (0.0 < float(pcm_scale) < float("inf")):
+        raise ValueError(f"resample: pcm_scale must be finite and positive, got {pcm_scale}")
+    y_dtype = torch.float32 if pcm_scale is None else torch.int16
+    if out_capacity is not None:
+        N_out = int(out_capacity)
+    elif out is not None:
+        N_out = out.shape[1] if out.dim() == 2 else -1
+    else:
+        N_out = resample_len(N, O, M)
+    if not 1 <= N_out < 2 ** 31 - RESAMPLE_TILE:
+        raise ValueError(f"resample: the output capacity must be in [1, 2^31 - {RESAMPLE_TILE}), got {N_out}")
+    if out is None:
+        out = torch.empty((B, N_out), dtype=y_dtype, device=x.device)
+    elif tuple(out.shape) != (B, N_out) or out.dtype != y_dtype or out.device != x.device:
+        raise ValueError(f"resample: out must be {y_dtype} {(B, N_out)} on {x.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    _contig(out, "out")
+    lens32 = None if lens is None else _resample_rows(lens, B, N, x, "lens")
+    skip32 = None if skip is None else _resample_rows(skip, B, 2 ** 31 - 1, x, "skip")
+    table = resample_table(O, M, x.device)
+    out_lens = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().vo_resample(_ptr(x), int(is16), mwv, B, N, _ptr(lens32), _ptr(skip32), _ptr(table), O, M,
+                                      _ptr(out), int(pcm_scale is not None), float(pcm_scale or 0.0), N_out,
+                                      _ptr(out_lens), st), "vo_resample")
+    return out, out_lens
+
+
 # ----------------------------------------------------------------------------- offline feature extraction
 
 def spec_features(wav, window, fb, n_fft=1024, hop=256, log_floor=1e-5):

@@ -84,8 +84,11 @@ class SynthesisResult:
     the next call of the same ``GraphedSynthesis`` (which overwrites it in stream order) -- clone, or take ``wavs()``,
     before calling again.
 
-    wav        (n, max_mel_len * hop): int16 with ``pcm_scale``, fp32 without; exactly 0 past each utterance's end
-    samples    (n,) int64: min(mel_len, max_mel_len) * hop, computed inside the graph
+    wav        (n, max_mel_len * hop): int16 with ``pcm_scale``, fp32 without; exactly 0 past each utterance's end.
+               At the vocoder's rate (``rate``, 22050 Hz for the shipped HiFi-GAN); with ``out_rate`` at that rate,
+               (n, resample_length(max_mel_len * hop, rate, out_rate))
+    samples    (n,) int64: min(mel_len, max_mel_len) * hop, computed inside the graph; with ``out_rate`` the
+               resampled counts, ceil(that M / O) (vo_resample's out_lens)
     mel_len    (n,) int64: the length regulator's uncropped frame counts
     truncated  (n,) bool: mel_len > max_mel_len -- the utterance was cropped at the capacity (as the reference's
                pad(output, max_len) crops it); re-run it in a larger bucket
@@ -128,6 +131,12 @@ class GraphedSynthesis:
     place and glyphs edited in place in ``atlas.glyphs_d``.  Without ``atlas`` nothing of this exists: the same
     arguments, the same graph.
 
+    ``out_rate`` (delivery at another sample rate than the vocoder's ``rate``): the vocoder
+    runs to fp32 and the captured body ends in one ``vo_resample`` launch from the fp32 waveform and ``samples``
+    (cast to int32 inside the graph), which writes int16 with ``pcm_scale`` and fp32 without.  A ratio the library
+    does not run is a ValueError here.  With ``out_rate=None`` (or equal to ``rate``) the object captures exactly
+    the launches it captures without the argument.
+
     The model and the vocoder must be in eval mode (RuntimeError otherwise); the call runs under ``no_grad``.
 
     Capture: on a side stream after ``warmup`` eager runs (they build the weight packs, the vocoder's side streams
@@ -140,7 +149,7 @@ class GraphedSynthesis:
     goes up by one: a replay never synthesises with weights the modules no longer hold."""
 
     def __init__(self, model, vocoder, batch, max_src_len, max_mel_len, pcm_scale=None, use_image=True, warmup=2,
-                 atlas=None):
+                 atlas=None, out_rate=None, rate=22050):
         from .train import _check_graph_runtime
         _check_graph_runtime("GraphedSynthesis (HIP-graph replay)")
         batch, max_src_len, max_mel_len = int(batch), int(max_src_len), int(max_mel_len)
@@ -162,6 +171,11 @@ class GraphedSynthesis:
         self.batch, self.max_src_len, self.max_mel_len = batch, max_src_len, max_mel_len
         self.pcm_scale = None if pcm_scale is None else float(pcm_scale)
         self.use_image, self.warmup = bool(use_image), int(warmup)
+        self.rate = int(rate)
+        self.out_rate = None if out_rate is None or int(out_rate) == self.rate else int(out_rate)
+        if self.out_rate is not None:
+            from . import ops
+            ops.resample_geometry(self.rate, self.out_rate)  # ValueError for a ratio the library does not run
         self.device = next(vocoder.parameters()).device
         self.hop = 1
         for u in vocoder.h.upsample_rates:
@@ -245,9 +259,15 @@ class GraphedSynthesis:
                               W_out=i.images.shape[3], out=i.images)
         out = self.model(i.audiotypes, i.texts, i.src_lens, self.max_src_len, None, None, self.max_mel_len, None,
                          None, None, i.images, None, self.use_image, e_control=i.e_control, d_control=i.d_control)
-        wav = self.vocoder.run(out[1], out[9], self.pcm_scale)
         mel_len = out[9]
         samples = torch.clamp(mel_len, max=self.max_mel_len) * self.hop
+        if self.out_rate is None:
+            wav = self.vocoder.run(out[1], out[9], self.pcm_scale)
+        else:
+            from . import ops
+            wav, samples = ops.resample(self.vocoder.run(out[1], out[9], None), self.rate, self.out_rate,
+                                        lens=samples.to(torch.int32), pcm_scale=self.pcm_scale)
+            samples = samples.to(torch.int64)
         return out, wav, samples, mel_len > self.max_mel_len
 
     def _capture(self):
