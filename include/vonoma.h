@@ -50,8 +50,10 @@ const char* vo_last_error(void);
  * at load time.  2 (round 4): vo_bucket_embed gained n_table (before n), vo_conv1d_desc gained
  * ymask / ymask_slope at its end -- a version-1 binding would pass shifted arguments or leave the
  * new fields uninitialised.  3: vo_conv1d_desc gained lens / lens_scale at its end (a version-2 binding would
- * leave them uninitialised), and the vo_*_lens entries below. */
-#define VO_ABI_VERSION 3
+ * leave them uninitialised), and the vo_*_lens entries below.  4: vo_conv1d_wgrad and vo_conv1d_wgrad_grouped,
+ * forwarding wrappers of vo_conv1d_wgrad_bias without a caller, are gone (a version-3 binding would look them
+ * up). */
+#define VO_ABI_VERSION 4
 int vo_version(void);
 /* number of entry points and their names (used by the loader test) */
 int vo_num_symbols(void);
@@ -652,24 +654,19 @@ int vo_gan_reduce_grad_multi(int n, const VoGanTerm* terms, int dtype, const flo
  * vo_colsum: out[c] = sum_r x[r*ld + c] (bias gradient; block partials in workspace,
  * vo_colsum_workspace_size bytes, added in order). */
 int64_t vo_conv1d_wgrad_workspace_size(int B, int T_A, int M, int N, int K, int groups);
-int vo_conv1d_wgrad(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M,
-                    int N, int K, int S, int dil, int pad, int pre_a, int pre_b, float slope,
-                    int dtype, float* dw, float* workspace, void* stream);
-/* Grouped conv (groups > 1): M = C_out / groups and N = C_in / groups per group, lda >= groups*M,
- * ldb >= groups*N; group g reads A columns [g*M, (g+1)*M), B columns [g*N, (g+1)*N) and writes
+/* The one entry (ABI 4 dropped the forwarding wrappers vo_conv1d_wgrad and vo_conv1d_wgrad_grouped: groups = 1
+ * and db = NULL here).  Grouped conv (groups > 1): M = C_out / groups and N = C_in / groups per group,
+ * lda >= groups*M, ldb >= groups*N; group g reads A columns [g*M, (g+1)*M), B columns [g*N, (g+1)*N) and writes
  * rows [g*M, (g+1)*M) of dw laid out (groups*M, N, K).  Replaces MIOpen's grouped weight pass of
- * the multi-scale discriminator (HiFi-GAN V1 MSD). */
-int vo_conv1d_wgrad_grouped(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B,
-                            int M, int N, int K, int S, int dil, int pad, int groups, int pre_a,
-                            int pre_b, float slope, int dtype, float* dw, float* workspace, void* stream);
-/* vo_conv1d_wgrad_grouped + the bias gradient in the same launch: db[g*M + m] = sum over all
+ * the multi-scale discriminator (HiFi-GAN V1 MSD).
+ * db non-NULL: the bias gradient in the same launch, db[g*M + m] = sum over all
  * A rows of A[.., g*M + m] (the conv form, A = dY; pre_a must be 0), summed by the tap-0
  * workgroups as they stage A (saves the separate vo_colsum launch). */
 int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B,
                          int M, int N, int K, int S, int dil, int pad, int groups, int pre_a,
                          int pre_b, float slope, int dtype, float* dw, float* db, float* workspace,
                          void* stream);
-/* Which kernel this thread's last vo_conv1d_wgrad[_grouped|_bias] call launched (host bookkeeping, zeroed at the
+/* Which kernel this thread's last vo_conv1d_wgrad_bias call launched (host bookkeeping, zeroed at the
  * call's entry: a rejected call reads as zeros).  Copies min(n, VO_CONV1D_WGRAD_LAUNCH_FIELDS) fields into rec
  * and returns that count (0 for a null rec).  Fields, in order: ROUTE (1 per-tap kernel, 2 multi-tap kernel,
  * 3 K = 1 kernel), TM (output tile: 64 / 32 or 64 / 128), KG (taps per run; 0 off the multi-tap route), SW (its

@@ -591,7 +591,7 @@ def test_trainer_graphed_matches_eager():
     (2, 1000, 32, 32, 11, 5, 1, 25, 0.1), (3, 517, 256, 256, 3, 1, 1, 1, 0.1), (2, 300, 80, 512, 7, 1, 1, 3, None),
     (4, 2731, 32, 128, 5, 1, 3, 2, None), (2, 777, 1024, 256, 1, 1, 1, 0, None), (1, 5, 64, 64, 7, 3, 1, 9, 0.1)])
 def test_conv1d_wgrad_vs_torch(B, T, Ci, Co, K, dil, s, pad, pre, dt, tol):
-    """vo_conv1d_wgrad (dense conv: A = dY, B = pre(x)) against torch's conv1d weight gradient."""
+    """vo_conv1d_wgrad_bias (dense conv: A = dY, B = pre(x)) against torch's conv1d weight gradient."""
     from visual_onoma_to_wave_amd import ops
     g = torch.Generator().manual_seed(T + K + Ci)
     x = torch.randn(B, T, Ci, generator=g).to(dt).float()
@@ -678,7 +678,7 @@ def _multitap_vs_per_tap(B, T, Ci, Co, K, dil, g, bias, kg, routes):
     (2, 1000, 128, 128, 41, 2, 4, 20), (2, 777, 128, 256, 41, 4, 16, 20), (3, 300, 256, 512, 41, 4, 16, 20),
     (2, 64, 1024, 1024, 41, 1, 16, 20), (2, 13, 512, 1024, 41, 4, 16, 20), (1, 5, 64, 64, 3, 1, 2, 1)])
 def test_grouped_conv1d_wgrad_vs_torch(B, T, Ci, Co, K, s, g, pad, dt, tol):
-    """vo_conv1d_wgrad_grouped (MSD grouped strided convs) against torch's grouped weight gradient."""
+    """vo_conv1d_wgrad_bias, grouped (MSD grouped strided convs) against torch's grouped weight gradient."""
     from visual_onoma_to_wave_amd import ops
     gen = torch.Generator().manual_seed(T + Co + g)
     x = torch.randn(B, T, Ci, generator=gen).to(dt).float()
@@ -695,7 +695,7 @@ def test_grouped_conv1d_wgrad_vs_torch(B, T, Ci, Co, K, s, g, pad, dt, tol):
 @pytest.mark.parametrize("dt,tol", [(torch.float32, 1e-5), (torch.bfloat16, 1e-2)])
 @pytest.mark.parametrize("Ci,Co,u,T", [(512, 256, 8, 32), (128, 64, 2, 1000), (64, 32, 2, 7)])
 def test_convtranspose_wgrad_vs_torch(Ci, Co, u, T, dt, tol):
-    """vo_conv1d_wgrad transposed form (A = lrelu(x), B = dY) against torch's ConvTranspose1d grad."""
+    """vo_conv1d_wgrad_bias, transposed form (A = lrelu(x), B = dY) against torch's ConvTranspose1d grad."""
     from visual_onoma_to_wave_amd import ops
     g = torch.Generator().manual_seed(Ci + T)
     K, p = 2 * u, u // 2

@@ -212,11 +212,6 @@ _SIGNATURES = {
                                  c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "vo_stft_mel_frames": (c_int, [c_int, c_int, c_int, c_int]),
     "vo_conv1d_wgrad_workspace_size": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "vo_conv1d_wgrad": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
-    "vo_conv1d_wgrad_grouped": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
-                                        c_void_p, c_void_p]),
     "vo_conv1d_wgrad_bias": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
@@ -305,7 +300,7 @@ _SIGNATURES = {
                             c_void_p, c_int, c_float, c_int, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 3  # include/vonoma.h VO_ABI_VERSION
+ABI_VERSION = 4  # include/vonoma.h VO_ABI_VERSION
 _lib = None
 
 

@@ -4,7 +4,7 @@ The forward of every op is the same HIP kernel the inference path runs.  Backwar
 
 * Conv1d / Linear input-gradient: HIP -- the conv kernel itself over dY with the weights
   re-packed taps-reversed / channels-swapped (``vo_pack_weight`` mode DGRAD);
-* Conv1d / Linear weight and bias gradients: HIP -- ``vo_conv1d_wgrad`` (MFMA, fragments
+* Conv1d / Linear weight and bias gradients: HIP -- ``vo_conv1d_wgrad_bias`` (MFMA, fragments
   read transposed from LDS) and ``vo_colsum``;
 * LayerNorm backward: HIP -- ``vo_layernorm_bwd`` (row-wise input gradient, deterministic
   gamma / beta column sums);
@@ -205,7 +205,7 @@ class Conv1dFn(torch.autograd.Function):
                             pad=(K - 1) * dil - pad, T_out=x.shape[1], out_dtype=x.dtype, compute_dtype=cdt)
         if ctx.needs_input_grad[1]:
             if x.dtype in (torch.float32, torch.bfloat16) and x.shape[-1] % 8 == 0 and w.shape[0] % 8 == 0:
-                # MFMA weight gradient over transposed LDS reads (vo_conv1d_wgrad), in the forward's
+                # MFMA weight gradient over transposed LDS reads (vo_conv1d_wgrad_bias), in the forward's
                 # compute dtype (an fp32 activation feeding a bf16 conv -- PostNet after its fp32
                 # BatchNorm -- was contracted in bf16 by the forward too)
                 fuse_b = want_b and gz.dtype == sd  # bias = column sums of the same dY (no cast)

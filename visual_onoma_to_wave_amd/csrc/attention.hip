@@ -194,9 +194,6 @@ __global__ void __launch_bounds__(256) attention2_kernel(const bf16_t* __restric
   constexpr int P = DK + 16;
   __shared__ __attribute__((aligned(16))) bf16_t kv_lds[2][2][KT * P];  // [buf][K | V][key][dk]
   typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-  typedef short v4s __attribute__((ext_vector_type(4)));
-  typedef short v8s __attribute__((ext_vector_type(8)));
-  typedef __attribute__((address_space(3))) v4s lds_v4s;
 
   const int D = H * DK;
   // the query tiles of one (b, h) read the same K / V: consecutive logical ids, one XCD's L2
@@ -320,11 +317,7 @@ __global__ void __launch_bounds__(256) attention2_kernel(const bf16_t* __restric
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const bf16_t* vb = V + (32 * ks + 4 * g + tq) * P + 16 * dt + 4 * tp;
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)vb);
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(vb + 16 * P));
-        Frag<bf16_t> vf;
-        vf.v = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        o[dt] = mfma(vf, pf, o[dt]);
+        o[dt] = mfma(tr_frag(vb, vb + 16 * P), pf, o[dt]);
       }
     }
     if (kt + 1 < n_tiles) stash(buf ^ 1);  // the other buffer was last read before the previous barrier

@@ -372,20 +372,13 @@ template <int DK>
 constexpr int AB2_P = DK + 16;
 
 typedef unsigned int ab_u4 __attribute__((ext_vector_type(4)));
-typedef short ab_v4s __attribute__((ext_vector_type(4)));
-typedef short ab_v8s __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) ab_v4s ab_lds_v4s;
 
 // A fragment of X^T (rows d = 16 dt + lane row, k = the 32 rows 32 ks .. of the row-major LDS tile X, in
 // the accumulator order above)
 template <int P>
 __device__ __forceinline__ Frag<bf16_t> ab_tr_frag(const bf16_t* X, int ks, int dt, int g, int tq, int tp) {
   const bf16_t* vb = X + (32 * ks + 4 * g + tq) * P + 16 * dt + 4 * tp;
-  const ab_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)vb);
-  const ab_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)(vb + 16 * P));
-  Frag<bf16_t> f;
-  f.v = __builtin_bit_cast(bf16x8, (ab_v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-  return f;
+  return tr_frag(vb, vb + 16 * P);
 }
 
 // B fragment from two accumulator tiles (k-step ks: tiles 2 ks, 2 ks + 1)

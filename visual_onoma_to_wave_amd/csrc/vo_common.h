@@ -200,6 +200,22 @@ template <> struct Frag<bf16_t> {
     for (int i = 0; i < 8; ++i) v[i] = (__bf16)0.0f;
   }
 };
+// Fragment by two transposed LDS reads (ds_read_b64_tr_b16, gfx950): each read delivers 4 rows of one channel per
+// lane, so a row-major (channels-last) LDS tile feeds the fragment's k = row index without a transpose pass.  Lane
+// 4 q + p of a 16-lane group names row q, channels 4 p .. 4 p + 3 of a 4-row block (8-byte aligned; every lane
+// active); lo fills elements 0..3, hi 4..7.  The callers differ only in where the two blocks lie.
+__device__ __forceinline__ Frag<bf16_t> tr_frag(const bf16_t* lo_p, const bf16_t* hi_p) {
+  typedef short v4s __attribute__((ext_vector_type(4)));
+  typedef short v8s __attribute__((ext_vector_type(8)));
+  typedef __attribute__((address_space(3))) v4s lds_v4s;
+  const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)lo_p);
+  const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)hi_p);
+  // whole-vector bit cast: per-element __bf16 inserts were mis-lowered by hipcc (only the low dword of each read
+  // survived)
+  Frag<bf16_t> f;
+  f.v = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  return f;
+}
 template <> struct Frag<float> {
   float v[8];
   __device__ __forceinline__ void load(const float* p) {

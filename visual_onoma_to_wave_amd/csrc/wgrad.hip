@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 #include "vo_common.h"
 
@@ -45,15 +46,12 @@ struct WgradArgs {
   int64_t n_w;  // groups * K * M * N
   int64_t n_tot;  // n_w + groups * M (with bias) or n_w: floats per split
   bool bias;  // bias gradient (column sums of A) fused into the tap-0 / n-tile-0 workgroups
-  int abl;  // timing ablation (wgrad_cfg 11): 2 = no loads
   int gpt;  // groups per tile (grouped convs with narrow groups, per-tap kernel): see wgrad_gpt
   float* dwf;  // per-tap kernel with one row split: dW (and db) written in their final layout, no reduce
   float* dbf;
 };
 // groups > 1 (grouped conv): grid z = group * K + tap; group g reads A columns [g M, (g+1) M)
 // and B columns [g N, (g+1) N) and writes block g of the (groups, K, M, N) result
-
-typedef short v4s __attribute__((ext_vector_type(4)));
 
 template <typename T> struct WgTile;
 template <> struct WgTile<bf16_t> { static constexpr int PITCH = 72; };  // 144-B rows: tr reads of 4 rows hit distinct banks
@@ -65,6 +63,51 @@ template <> struct WgTile<bx3_t> { static constexpr int PITCH = 72; };
 __device__ __forceinline__ uint32_t lrelu_pack(uint32_t w, float s) {
   const float lo = __uint_as_float(w << 16), hi = __uint_as_float(w & 0xffff0000u);
   return pk_bf16(lrelu_max(lo, s), lrelu_max(hi, s));
+}
+// leaky ReLU of a staged 16-byte vector: eight packed bf16, or four fp32 lanes
+__device__ __forceinline__ u32x4_t lrelu_bf16x8(u32x4_t x, float s) {
+  return u32x4_t{lrelu_pack(x.x, s), lrelu_pack(x.y, s), lrelu_pack(x.z, s), lrelu_pack(x.w, s)};
+}
+__device__ __forceinline__ u32x4_t lrelu_f32x4(u32x4_t x, float s) {
+  const float f[4] = {__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)};
+  return u32x4_t{__float_as_uint(fmaxf(f[0], f[0] * s)), __float_as_uint(fmaxf(f[1], f[1] * s)),
+                 __float_as_uint(fmaxf(f[2], f[2] * s)), __float_as_uint(fmaxf(f[3], f[3] * s))};
+}
+
+// staging slot s of thread tid (256 threads) in a tile of VPR vectors of EV elements per row: row r, column c
+struct WgSlot { int r, c; };
+template <int VPR, int EV>
+__device__ __forceinline__ WgSlot wg_slot(int tid, int s) {
+  const int v = tid + s * 256;
+  return WgSlot{v / VPR, (v % VPR) * EV};
+}
+
+// A wave's MI x MI accumulator tiles -> out(m, n, value) for every (m, n) inside M x N.  (m0, n0): the lane's
+// element 0 of tile (0, 0), i.e. the wave's origin + (4 (lane >> 4), lane & 15); element e is the next row, tile
+// (i, j) 16 rows / columns on.  The K = 1 and multi-tap kernels' epilogue.  Their lambdas capture the destination
+// by value: wgrad_k1_kernel then compiles to the same instructions as with the loop written out
+// (profiles/wgradplan/isa_parent_vs_tree.md)
+template <int MI, typename F>
+__device__ __forceinline__ void wg_epilogue(const f32x4 (&acc)[MI][MI], int m0, int n0, int M, int N, F&& out) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < MI; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int m = m0 + 16 * i + e, n = n0 + 16 * j;
+        if (m < M && n < N) out(m, n, acc[i][j][e]);
+      }
+}
+
+// Bias finish of the four waves: thread (wave w, column c = tid & 63) brings the column sum of its wave's 16 rows
+// of every staged chunk; out(m, the four sums added in wave order) for the first `cols` columns inside M
+template <typename F>
+__device__ __forceinline__ void wg_bias_finish(float bsum, int tid, int cols, int m0, int M, F&& out) {
+  __shared__ float bred[4][64];
+  bred[tid >> 6][tid & 63] = bsum;
+  __syncthreads();
+  if (tid < cols && m0 + tid < M) out(m0 + tid, bred[0][tid] + bred[1][tid] + bred[2][tid] + bred[3][tid]);
 }
 
 // 4 waves as 2 x 2, each a 32 x 32 sub-tile = 2 x 2 MFMA tiles
@@ -109,8 +152,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
   auto load_chunk = [&](int64_t r0) {
 #pragma unroll
     for (int s = 0; s < NV; ++s) {
-      const int v = tid + s * 256;
-      const int r = v / VPR, c = (v % VPR) * EV;
+      const auto [r, c] = wg_slot<VPR, EV>(tid, s);
       const int64_t q = r0 + r;
       const bool qok = q < r_end;
       const int64_t qq = qok ? q : r_begin;
@@ -118,12 +160,8 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
       const int tb = t * p.S + k * p.dil - p.pad;
       const bool bok = qok && tb >= 0 && tb < p.T_B;
       const int ma = min(m0 + c, Mv - EV), nb = min(n0 + c, Nv - EV);
-      if (p.abl & 2) {
-        va[s] = vb[s] = u32x4_t{(unsigned)tb, (unsigned)ma, 1u, 1u};
-      } else {
-        va[s] = *reinterpret_cast<const u32x4_t*>(A + ((int64_t)b * p.T_A + t) * p.lda + ma);
-        vb[s] = *reinterpret_cast<const u32x4_t*>(Bs + ((int64_t)b * p.T_B + min(max(tb, 0), p.T_B - 1)) * p.ldb + nb);
-      }
+      va[s] = *reinterpret_cast<const u32x4_t*>(A + ((int64_t)b * p.T_A + t) * p.lda + ma);
+      vb[s] = *reinterpret_cast<const u32x4_t*>(Bs + ((int64_t)b * p.T_B + min(max(tb, 0), p.T_B - 1)) * p.ldb + nb);
       if (!qok || m0 + c >= Mv) va[s] = u32x4_t{0u, 0u, 0u, 0u};
       if (!bok || n0 + c >= Nv) vb[s] = u32x4_t{0u, 0u, 0u, 0u};
     }
@@ -133,17 +171,18 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
     __syncthreads();  // previous chunk's fragment reads are done
 #pragma unroll
     for (int s = 0; s < NV; ++s) {
-      const int v = tid + s * 256;
-      const int r = v / VPR, c = (v % VPR) * EV;
+      const auto [r, c] = wg_slot<VPR, EV>(tid, s);
       u32x4_t x = va[s], y = vb[s];
+      if constexpr (sizeof(TC) == 2) {
+        if (p.pre_a) x = lrelu_bf16x8(x, p.slope);
+        if (p.pre_b) y = lrelu_bf16x8(y, p.slope);
+      } else {  // fp32 lanes, also ahead of the split
+        if (p.pre_a) x = lrelu_f32x4(x, p.slope);
+        if (p.pre_b) y = lrelu_f32x4(y, p.slope);
+      }
       if constexpr (std::is_same<TC, bx3_t>::value) {
-        float f[8] = {__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w),
-                      __uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(y.z), __uint_as_float(y.w)};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (p.pre_a) f[e] = fmaxf(f[e], f[e] * p.slope);
-          if (p.pre_b) f[4 + e] = fmaxf(f[4 + e], f[4 + e] * p.slope);
-        }
+        const float f[8] = {__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w),
+                            __uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(y.z), __uint_as_float(y.w)};
         uint4 hi, lo;  // (x.xy, x.zw, y.xy, y.zw) as bf16 pairs
         split8(f, hi, lo);
         bf16_t* ha = reinterpret_cast<bf16_t*>(sa);
@@ -152,24 +191,10 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
         *reinterpret_cast<uint2*>(ha + (WG_R + r) * P + c) = make_uint2(lo.x, lo.y);
         *reinterpret_cast<uint2*>(hb + r * P + c) = make_uint2(hi.z, hi.w);
         *reinterpret_cast<uint2*>(hb + (WG_R + r) * P + c) = make_uint2(lo.z, lo.w);
-        continue;
-      } else if constexpr (sizeof(TC) == 2) {
-        if (p.pre_a) x = u32x4_t{lrelu_pack(x.x, p.slope), lrelu_pack(x.y, p.slope), lrelu_pack(x.z, p.slope), lrelu_pack(x.w, p.slope)};
-        if (p.pre_b) y = u32x4_t{lrelu_pack(y.x, p.slope), lrelu_pack(y.y, p.slope), lrelu_pack(y.z, p.slope), lrelu_pack(y.w, p.slope)};
       } else {
-        if (p.pre_a) {
-          float f[4] = {__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)};
-          x = u32x4_t{__float_as_uint(fmaxf(f[0], f[0] * p.slope)), __float_as_uint(fmaxf(f[1], f[1] * p.slope)),
-                      __float_as_uint(fmaxf(f[2], f[2] * p.slope)), __float_as_uint(fmaxf(f[3], f[3] * p.slope))};
-        }
-        if (p.pre_b) {
-          float f[4] = {__uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(y.z), __uint_as_float(y.w)};
-          y = u32x4_t{__float_as_uint(fmaxf(f[0], f[0] * p.slope)), __float_as_uint(fmaxf(f[1], f[1] * p.slope)),
-                      __float_as_uint(fmaxf(f[2], f[2] * p.slope)), __float_as_uint(fmaxf(f[3], f[3] * p.slope))};
-        }
+        *reinterpret_cast<u32x4_t*>(sa + r * P + c) = x;
+        *reinterpret_cast<u32x4_t*>(sb + r * P + c) = y;
       }
-      *reinterpret_cast<u32x4_t*>(sa + r * P + c) = x;
-      *reinterpret_cast<u32x4_t*>(sb + r * P + c) = y;
     }
     __syncthreads();
     if (r0 + WG_R < r_end) load_chunk(r0 + WG_R);
@@ -195,16 +220,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
         const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
         auto frag = [&](const bf16_t* tile, int c0) {
           const bf16_t* base = tile + (kr + 8 * g + q) * P + c0 + 4 * pp;
-          typedef __attribute__((address_space(3))) v4s lds_v4s;
-          const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)base);
-          const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(base + 4 * P));
-          // whole-vector bit cast: per-element __bf16 inserts were mis-lowered by hipcc (only the
-          // low dword of each read survived)
-          typedef short v8s __attribute__((ext_vector_type(8)));
-          const v8s all = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          Frag<bf16_t> f;
-          f.v = __builtin_bit_cast(bf16x8, all);
-          return f;
+          return tr_frag(base, base + 4 * P);
         };
         const bf16_t* ta = reinterpret_cast<const bf16_t*>(sa);
         const bf16_t* tb = reinterpret_cast<const bf16_t*>(sb);
@@ -253,20 +269,18 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs p) {
     }
   }
 
-  if (do_bias) {
-    __shared__ float bred[4][64];
-    bred[tid >> 6][tid & 63] = bsum;
-    __syncthreads();
-    if (tid < 64 && m0 + tid < Mv) {
-      const float v = bred[0][tid] + bred[1][tid] + bred[2][tid] + bred[3][tid];
+  if (do_bias)
+    wg_bias_finish(bsum, tid, 64, m0, Mv, [&](int m, float v) {
       if (p.dbf)
-        p.dbf[(int64_t)grp * p.M + m0 + tid] = v;
+        p.dbf[(int64_t)grp * p.M + m] = v;
       else
-        p.part[(int64_t)blockIdx.x * p.n_tot + p.n_w + (int64_t)grp * p.M + m0 + tid] = v;
-    }
-  }
+        p.part[(int64_t)blockIdx.x * p.n_tot + p.n_w + (int64_t)grp * p.M + m] = v;
+    });
 
-  // ---- epilogue: D[m][n] (row = m: 4 (lane >> 4) + e, col = n: lane & 15) -> dW[k][m][n]
+  // ---- epilogue: D[m][n] (row = m: 4 (lane >> 4) + e, col = n: lane & 15) -> dW[k][m][n].  Not wg_epilogue: the
+  // group of a row must be found before the bounds test, where the compiler shares the divisions between the
+  // elements; inside wg_epilogue's bounds test every element repeats them (earlier_call in
+  // profiles/wgradplan/bench_parent_vs_tree.json)
   const int li = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -360,15 +374,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_k1_kernel(WgradArgs p) {
   const int g = lane >> 4, li = lane & 15, fq = li >> 2, fp = li & 3;
   auto frag = [&](const bf16_t* tile, int kr, int c0) {
     const int r = kr + 8 * g + fq, col = c0 + 4 * fp;
-    typedef __attribute__((address_space(3))) v4s lds_v4s;
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(tile + r * K1_T + k1_swz(r, col >> 3) * 8 + (col & 7)));
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_v4s*)(tile + (r + 4) * K1_T + k1_swz(r + 4, col >> 3) * 8 + (col & 7)));
-    typedef short v8s __attribute__((ext_vector_type(8)));
-    const v8s all = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    Frag<bf16_t> f;
-    f.v = __builtin_bit_cast(bf16x8, all);
-    return f;
+    return tr_frag(tile + r * K1_T + k1_swz(r, col >> 3) * 8 + (col & 7),
+                   tile + (r + 4) * K1_T + k1_swz(r + 4, col >> 3) * 8 + (col & 7));
   };
 
   const int nchunks = (int)((r_end - r_begin + K1_R - 1) / K1_R);
@@ -412,15 +419,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_k1_kernel(WgradArgs p) {
     }
   }
   float* dw = p.dwf ? p.dwf : p.part + (int64_t)blockIdx.x * p.n_tot;  // K = 1: (M, N) either way
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int m = m0 + wm + 16 * i + 4 * g + e, n = n0 + wn + 16 * j + li;
-        if (m < p.M && n < p.N) dw[(int64_t)m * p.N + n] = acc[i][j][e];
-      }
+  wg_epilogue<4>(acc, m0 + wm + 4 * g, n0 + wn + li, p.M, p.N,
+                 [dw, N = p.N](int m, int n, float v) { dw[(int64_t)m * N + n] = v; });
 }
 
 // Multi-tap weight gradient (round 3; stride-1 convs, bf16): the per-tap kernel above restages
@@ -497,15 +497,15 @@ __global__ void __launch_bounds__(256, 2) wgrad_mt_kernel(WgradArgs p, int chunk
     const int b = c / chunks_per_b, t0 = (c - b * chunks_per_b) * WM_R;
 #pragma unroll
     for (int s = 0; s < NVA; ++s) {
-      const int v = tid + s * 256, r = v / VPR, col = (v % VPR) * 8;
+      const auto [r, col] = wg_slot<VPR, 8>(tid, s);
       const int t = min(t0 + r, p.T_A - 1);
       va[s] = *reinterpret_cast<const u32x4_t*>(A + ((int64_t)b * p.T_A + t) * p.lda + min(m0 + col, p.M - 8));
     }
     const int tb0 = t0 * p.S - p.pad + k0 * p.dil;
 #pragma unroll
     for (int s = 0; s < NVB; ++s) {
-      const int v = tid + s * 256, w = min(v / VPR, WMW - 1), col = (v % VPR) * 8;
-      const int tb = min(max(tb0 + w, 0), p.T_B - 1);
+      const auto [w, col] = wg_slot<VPR, 8>(tid, s);
+      const int tb = min(max(tb0 + min(w, WMW - 1), 0), p.T_B - 1);
       vb[s] = *reinterpret_cast<const u32x4_t*>(Bs + ((int64_t)b * p.T_B + tb) * p.ldb + min(n0 + col, p.N - 8));
     }
   };
@@ -514,49 +514,37 @@ __global__ void __launch_bounds__(256, 2) wgrad_mt_kernel(WgradArgs p, int chunk
     (void)b;
 #pragma unroll
     for (int s = 0; s < NVA; ++s) {
-      const int v = tid + s * 256, r = v / VPR, col = (v % VPR) * 8;
+      const auto [r, col] = wg_slot<VPR, 8>(tid, s);
       u32x4_t x = va[s];
       if (t0 + r >= p.T_A || m0 + col >= p.M) x = u32x4_t{0u, 0u, 0u, 0u};
-      if (p.pre_a) x = u32x4_t{lrelu_pack(x.x, p.slope), lrelu_pack(x.y, p.slope), lrelu_pack(x.z, p.slope), lrelu_pack(x.w, p.slope)};
+      if (p.pre_a) x = lrelu_bf16x8(x, p.slope);
       *reinterpret_cast<u32x4_t*>(sa + r * P + col) = x;
     }
     const int tb0 = t0 * p.S - p.pad + k0 * p.dil;
 #pragma unroll
     for (int s = 0; s < NVB; ++s) {
-      const int v = tid + s * 256, w = v / VPR, col = (v % VPR) * 8;
+      const auto [w, col] = wg_slot<VPR, 8>(tid, s);
       if (w < WR) {  // uniform per 8-lane row group; rows past the window are never read
         u32x4_t y = vb[s];
         const int tb = tb0 + w;
         if (tb < 0 || tb >= p.T_B || n0 + col >= p.N) y = u32x4_t{0u, 0u, 0u, 0u};
-        if (p.pre_b) y = u32x4_t{lrelu_pack(y.x, p.slope), lrelu_pack(y.y, p.slope), lrelu_pack(y.z, p.slope), lrelu_pack(y.w, p.slope)};
+        if (p.pre_b) y = lrelu_bf16x8(y, p.slope);
         *reinterpret_cast<u32x4_t*>(sb + roff(w) + col) = y;
       }
     }
   };
 
   const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  typedef __attribute__((address_space(3))) v4s lds_v4s;
-  typedef short v8s __attribute__((ext_vector_type(8)));
   // fragment of 16 channels (c0 + li) x 8 rows (row0 + 8 g ..): two transposed 4-row reads
   auto frag = [&](const bf16_t* tile, int row0, int c0) {
     const bf16_t* base = tile + (row0 + 8 * g + q) * P + c0 + 4 * pp;
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)base);
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(base + 4 * P));
-    Frag<bf16_t> f;
-    f.v = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    return f;
+    return tr_frag(base, base + 4 * P);
   };
   // B fragment of A rows arow0 + 8 g .. (+ 8) for tap kk: window rows (A row) S + kk dil
   auto frag_b = [&](int arow0, int kk, int c0) {
     if constexpr (SW == 1) return frag(sb, arow0 + kk * p.dil, c0);
     const int r = arow0 + 8 * g + q;
-    const bf16_t* lo_p = sb + roff(r * p.S + kk * p.dil) + c0 + 4 * pp;
-    const bf16_t* hi_p = sb + roff((r + 4) * p.S + kk * p.dil) + c0 + 4 * pp;
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)lo_p);
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)hi_p);
-    Frag<bf16_t> f;
-    f.v = __builtin_bit_cast(bf16x8, (v8s)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    return f;
+    return tr_frag(sb + roff(r * p.S + kk * p.dil) + c0 + 4 * pp, sb + roff((r + 4) * p.S + kk * p.dil) + c0 + 4 * pp);
   };
 
   auto compute = [&]() {
@@ -609,27 +597,15 @@ __global__ void __launch_bounds__(256, 2) wgrad_mt_kernel(WgradArgs p, int chunk
     }
   }
 
-  if (do_bias) {
-    __shared__ float bred[4][64];
-    bred[tid >> 6][tid & 63] = bsum;
-    __syncthreads();
-    if (tid < TM && m0 + tid < p.M)
-      dw[p.n_w + (int64_t)grp * p.M + m0 + tid] = bred[0][tid] + bred[1][tid] + bred[2][tid] + bred[3][tid];
-  }
-  // D[m][n] (row = m: 4 g + e, col = n: li) -> part[split][grp][k][m][n]
+  if (do_bias)
+    wg_bias_finish(bsum, tid, TM, m0, p.M, [&](int m, float v) { dw[p.n_w + (int64_t)grp * p.M + m] = v; });
+  // D[m][n] -> part[split][grp][k][m][n]
 #pragma unroll
   for (int kk = 0; kk < KG; ++kk) {
     if (kk < nk) {
       float* dk = dw + ((int64_t)grp * p.K + k0 + kk) * p.M * p.N;
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < MI; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int m = m0 + wm + 16 * i + 4 * g + e, n = n0 + wn + 16 * j + li;
-            if (m < p.M && n < p.N) dk[(int64_t)m * p.N + n] = acc[kk][i][j][e];
-          }
+      wg_epilogue<MI>(acc[kk], m0 + wm + 4 * g, n0 + wn + li, p.M, p.N,
+                      [dk, N = p.N](int m, int n, float v) { dk[(int64_t)m * N + n] = v; });
     }
   }
 }
@@ -717,9 +693,33 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ x, in
 
 using namespace vo;
 
-// row-split plan shared by the workspace query and the launch: enough workgroups to fill 256
-// CUs ~4 deep, at least 4 chunks of 64 rows each, serial row chains of at most 64 chunks (a small
-// tile x tap grid -- the MSD's 32 x 16 groups -- otherwise leaves one workgroup walking every row)
+// Which kernel a vo_conv1d_wgrad_bias call takes and with what grid: every routing decision, host code without
+// a HIP call.  vo_conv1d_wgrad_plan runs wgrad_route and stops there; the launch runs it and launches from the same
+// struct it records (wgrad_record), so the two cannot disagree.
+enum { WG_ROUTE_PER_TAP = 1, WG_ROUTE_MULTI_TAP = 2, WG_ROUTE_K1 = 3 };
+struct WgradPlan {
+  int route;        // WG_ROUTE_*
+  int dtype, bias;
+  int tile;         // output tile edge (M and N): WG_T, K1_T or the multi-tap kernel's TM
+  int kg, sw, ntg;  // multi-tap: taps per run, window template (1, 2, 4), tap runs per group; else 0
+  int gpt;          // per-tap: groups per tile; else 1
+  int64_t splits;   // row splits = grid x
+  int rps;          // rows per split (multi-tap: the whole chunks of cps)
+  bool direct;      // the kernel writes dW / db in their final layout, no reduce
+  int gy;           // grid y: output tiles
+  int64_t gz;       // grid z: taps (per-tap) or tap runs (multi-tap) x groups
+  int chunks_per_b, cps;  // multi-tap: 64-row chunks per utterance / per split
+};
+
+static int wg_tiles(int M, int N, int t) { return ((M + t - 1) / t) * ((N + t - 1) / t); }
+
+// `splits` row splits of whole 64-row chunks each, and the splits that are then not empty
+static_assert(K1_R == WG_R, "one chunk height for the row-split plans");
+static void wgrad_split_rows(int64_t rows, int64_t splits, WgradPlan* pl) {
+  pl->rps = (int)(((rows + splits - 1) / splits + WG_R - 1) / WG_R * WG_R);
+  pl->splits = (rows + pl->rps - 1) / pl->rps;
+}
+
 // groups per tile of the per-tap kernel: narrow groups (the MSD's 16 x 8 .. 64 x 32 per group) are
 // packed side by side up to the 64 x 64 tile (one launch computed a 16 x 8 group in a 64 x 64 tile:
 // 1/32 of its MFMA work useful)
@@ -731,43 +731,47 @@ static int wgrad_gpt(int M, int N, int groups) {
   return gpt;
 }
 
-static void wgrad_plan(int B, int T_A, int M, int N, int K, int groups, int64_t* splits_out, int* rps_out) {
-  const int gpt = wgrad_gpt(M, N, groups);
-  const int64_t zk = (int64_t)K * (groups / gpt);
+// per-tap plan (wgrad_kernel): enough workgroups to fill 256 CUs ~4 deep, at least 4 chunks of 64 rows each, serial
+// row chains of at most 64 chunks (a small tile x tap grid -- the MSD's 32 x 16 groups -- otherwise leaves one
+// workgroup walking every row)
+static void wgrad_plan(int B, int T_A, int M, int N, int K, int groups, WgradPlan* pl) {
+  pl->tile = WG_T;
+  pl->gpt = wgrad_gpt(M, N, groups);
+  pl->gy = wg_tiles(M * pl->gpt, N * pl->gpt, WG_T);
+  pl->gz = (int64_t)K * (groups / pl->gpt);
   const int64_t rows = (int64_t)B * T_A;
-  const int tiles = ((M * gpt + WG_T - 1) / WG_T) * ((N * gpt + WG_T - 1) / WG_T);
-  const int wc = vo_tune_get("wgrad_cfg");
-  const int64_t target = wc == 1 ? 4096 : wc == 2 ? 8192 : wc == 3 ? 16384 : 1024;
-  int64_t splits = std::max<int64_t>(1, (target + (int64_t)tiles * zk - 1) / ((int64_t)tiles * zk));
+  int64_t splits = std::max<int64_t>(1, (1024 + pl->gy * pl->gz - 1) / (pl->gy * pl->gz));
   // short sequences (<= 4096 rows: the encoder's 384, split-bf16 / fp32): one chunk per split is allowed --
-  // their 6-chunk serial chains were a load round trip each (31.6 us per launch); wgrad_cfg 17 keeps >= 4
-  const int min_chunks = (rows <= 4096 && wc != 17) ? 1 : 4;
+  // their 6-chunk serial chains were a load round trip each (31.6 us per launch)
+  const int min_chunks = rows <= 4096 ? 1 : 4;
   splits = std::min<int64_t>(splits, std::max<int64_t>(1, rows / (min_chunks * WG_R)));
-  const int64_t max_rows = wc == 4 ? 2048 : wc == 5 ? 8192 : wc == 6 ? (int64_t)1 << 40 : 4096;
-  splits = std::max<int64_t>(splits, (rows + max_rows - 1) / max_rows);
-  const int rps = (int)(((rows + splits - 1) / splits + WG_R - 1) / WG_R * WG_R);
-  *splits_out = (rows + rps - 1) / rps;
-  *rps_out = rps;
+  splits = std::max<int64_t>(splits, (rows + 4095) / 4096);
+  wgrad_split_rows(rows, splits, pl);
 }
+
+// The one statement of which wgrad_mt_kernel<TM, KG, SW> exist: KG = 1 .. wgrad_mt_max_kg(TM, SW).  TM 64 x 9+
+// taps spill (strided: 6+, the larger window's staging registers).  The plan's clamp, the routing check and the
+// dispatch all read it.
+constexpr int wgrad_mt_max_kg(int tm, int sw) { return tm == 32 ? 11 : sw == 1 ? 8 : 5; }
 
 // multi-tap plan (wgrad_mt_kernel): the partials of a split cover the whole (K, M, N) output, so
 // splits are capped by their traffic (at most max(operand bytes, 16 MB) of partials); the taps are
 // then cut into runs (ntg per workgroup column) only as far as needed to give ~256 workgroups, the
 // rest of the parallelism comes from splits.  dil bounds a run's window (64 + (KG - 1) dil <= 128
-// rows); the splits never grow with dil, so the plan at dil = 1 sizes the workspace.
-struct MtPlan { int tm, kg, ntg, chunks_per_b, cps, splits; };
-static void wgrad_mt_plan(int B, int T_A, int M, int N, int K, int groups, int dil, MtPlan* pl, int S = 1) {
-  pl->tm = (M <= 32 && N <= 32) ? 32 : 64;
-  const int64_t tiles = (int64_t)((M + pl->tm - 1) / pl->tm) * ((N + pl->tm - 1) / pl->tm) * groups;
+// rows; stride S: 64 S + 64 rows, 1 + 64 / dil taps either way); the splits never grow with dil, so the plan at
+// dil = 1 sizes the workspace.
+static void wgrad_mt_plan(int B, int T_A, int M, int N, int K, int groups, int dil, int S, WgradPlan* pl) {
+  pl->tile = (M <= 32 && N <= 32) ? 32 : 64;
+  pl->sw = S == 1 ? 1 : S == 2 ? 2 : 4;
+  pl->gy = wg_tiles(M, N, pl->tile);
+  const int64_t tiles = (int64_t)pl->gy * groups;
   pl->chunks_per_b = (T_A + WM_R - 1) / WM_R;
   const int64_t total = (int64_t)B * pl->chunks_per_b;
   const int64_t rows = (int64_t)B * T_A;
   const int64_t operand = rows * ((int64_t)M + N) * groups * 2;
   const int64_t per_split = ((int64_t)groups * K * M * N + (int64_t)groups * M) * 4;
   const int64_t smax = std::max<int64_t>(1, std::min<int64_t>(total, std::max<int64_t>(operand, 16 << 20) / per_split));
-  // TM 64 x 9+ taps spill (strided: 5, the larger window's staging registers); the window (stride S: 64 S + 64
-  // rows) bounds a run to 1 + 64 / dil taps either way
-  const int kgmax = std::min(pl->tm == 64 ? (S > 1 ? 5 : 8) : 11, 1 + 64 / std::max(dil, 1));
+  const int kgmax = std::min(wgrad_mt_max_kg(pl->tile, pl->sw), 1 + 64 / std::max(dil, 1));
   const int forced = vo_tune_get("wgrad_kg");  // A/B: taps per run
   int ntg = (int)std::max<int64_t>(1, (256 + tiles * smax - 1) / (tiles * smax));
   int kg = forced > 0 ? forced : (K + ntg - 1) / ntg;
@@ -776,101 +780,40 @@ static void wgrad_mt_plan(int B, int T_A, int M, int N, int K, int groups, int d
   if (forced <= 0) kg = (K + ntg - 1) / ntg;  // balanced runs (K = 9 at 8 taps max: 5 + 4, not 8 + 1)
   pl->kg = kg;
   pl->ntg = ntg;
-  const int wc = vo_tune_get("wgrad_cfg");  // A/B: 19 / 20 = ~2048 / ~1024 workgroups
-  const int64_t wtarget = wc == 19 ? 2048 : wc == 20 ? 1024 : 512;
-  const int64_t want = std::max<int64_t>(1, (wtarget + tiles * ntg - 1) / (tiles * ntg));
+  pl->gz = (int64_t)ntg * groups;
+  const int64_t want = std::max<int64_t>(1, (512 + tiles * ntg - 1) / (tiles * ntg));  // ~512 workgroups
   const int64_t splits = std::min(smax, want);
   pl->cps = (int)((total + splits - 1) / splits);
-  pl->splits = (int)((total + pl->cps - 1) / pl->cps);
+  pl->splits = (total + pl->cps - 1) / pl->cps;
+  pl->rps = WM_R * pl->cps;
 }
 
 // K = 1 plan (wgrad_k1_kernel): ~512 workgroups (two per CU; wgrad_cfg 15 = 256, 16 = 1024), at least 4
 // chunks of 64 rows per split
-static void k1_plan(int B, int T_A, int M, int N, int64_t* splits_out, int* rps_out) {
-  const int64_t tiles = (int64_t)((M + K1_T - 1) / K1_T) * ((N + K1_T - 1) / K1_T);
+static void k1_plan(int B, int T_A, int M, int N, WgradPlan* pl) {
+  pl->tile = K1_T;
+  pl->gy = wg_tiles(M, N, K1_T);
+  pl->gz = 1;
   const int64_t rows = (int64_t)B * T_A;
   const int wc = vo_tune_get("wgrad_cfg");
   const int64_t target = wc == 15 ? 256 : wc == 16 ? 1024 : 512;
-  int64_t splits = (target + tiles - 1) / tiles;
-  splits = std::max<int64_t>(1, std::min<int64_t>(splits, rows / (4 * K1_R)));
-  const int rps = (int)(((rows + splits - 1) / splits + K1_R - 1) / K1_R * K1_R);
-  *splits_out = (rows + rps - 1) / rps;
-  *rps_out = rps;
+  const int64_t splits = (target + pl->gy - 1) / pl->gy;
+  wgrad_split_rows(rows, std::max<int64_t>(1, std::min<int64_t>(splits, rows / (4 * K1_R))), pl);
 }
 
+// the most row splits any route takes, at dil = 1
 extern "C" int64_t vo_conv1d_wgrad_workspace_size(int B, int T_A, int M, int N, int K, int groups) {
   if (B <= 0 || T_A <= 0 || M <= 0 || N <= 0 || K <= 0 || groups <= 0) return 0;
-  int64_t splits;
-  int rps;
-  wgrad_plan(B, T_A, M, N, K, groups, &splits, &rps);
-  MtPlan mt;
-  wgrad_mt_plan(B, T_A, M, N, K, groups, 1, &mt);
-  splits = std::max<int64_t>(splits, mt.splits);
-  if (K == 1 && groups == 1) {
-    int64_t k1s;
-    int k1r;
-    k1_plan(B, T_A, M, N, &k1s, &k1r);
-    splits = std::max<int64_t>(splits, k1s);
-  }
+  WgradPlan pt{}, mt{}, k1{};
+  wgrad_plan(B, T_A, M, N, K, groups, &pt);
+  wgrad_mt_plan(B, T_A, M, N, K, groups, 1, 1, &mt);
+  if (K == 1 && groups == 1) k1_plan(B, T_A, M, N, &k1);
+  const int64_t splits = std::max({pt.splits, mt.splits, k1.splits});
   return splits * ((int64_t)groups * K * M * N + (int64_t)groups * M) * (int64_t)sizeof(float);
 }
 
-template <int TM, int KG, int SW>
-static void wgrad_mt_launch(const WgradArgs& p, const MtPlan& pl, int groups, hipStream_t st) {
-  const int tiles = ((p.M + TM - 1) / TM) * ((p.N + TM - 1) / TM);
-  hipLaunchKernelGGL((wgrad_mt_kernel<TM, KG, SW>), dim3((unsigned)pl.splits, (unsigned)tiles,
-                     (unsigned)(pl.ntg * groups)), dim3(256), 0, st, p, pl.chunks_per_b, pl.cps, pl.ntg);
-}
-// the taps per run a (TM, SW) pair is instantiated for: TM 64 runs at most 8 taps, 5 when strided (wgrad_mt_plan)
-static int wgrad_mt_max_kg(int tm, int sw) { return tm == 32 ? 11 : sw == 1 ? 8 : 5; }
-
-// false: no instantiation for pl.kg, nothing launched (the caller must not reduce the unwritten workspace)
-template <int TM, int SW>
-static bool wgrad_mt_dispatch(const WgradArgs& p, const MtPlan& pl, int groups, hipStream_t st) {
-  switch (pl.kg) {
-    case 1: wgrad_mt_launch<TM, 1, SW>(p, pl, groups, st); return true;
-    case 2: wgrad_mt_launch<TM, 2, SW>(p, pl, groups, st); return true;
-    case 3: wgrad_mt_launch<TM, 3, SW>(p, pl, groups, st); return true;
-    case 4: wgrad_mt_launch<TM, 4, SW>(p, pl, groups, st); return true;
-    case 5: wgrad_mt_launch<TM, 5, SW>(p, pl, groups, st); return true;
-  }
-  if constexpr (TM == 32 || SW == 1) {
-    switch (pl.kg) {
-      case 6: wgrad_mt_launch<TM, 6, SW>(p, pl, groups, st); return true;
-      case 7: wgrad_mt_launch<TM, 7, SW>(p, pl, groups, st); return true;
-      case 8: wgrad_mt_launch<TM, 8, SW>(p, pl, groups, st); return true;
-    }
-  }
-  if constexpr (TM == 32) {
-    switch (pl.kg) {
-      case 9: wgrad_mt_launch<32, 9, SW>(p, pl, groups, st); return true;
-      case 10: wgrad_mt_launch<32, 10, SW>(p, pl, groups, st); return true;
-      case 11: wgrad_mt_launch<32, 11, SW>(p, pl, groups, st); return true;
-    }
-  }
-  return false;
-}
-
-// Which kernel a vo_conv1d_wgrad_bias call takes and with what grid: every routing decision, host code without
-// a HIP call.  vo_conv1d_wgrad_plan runs it and stops there; the launch runs it and launches from the same
-// struct it records (wgrad_record), so the two cannot disagree.
-enum { WG_ROUTE_PER_TAP = 1, WG_ROUTE_MULTI_TAP = 2, WG_ROUTE_K1 = 3 };
-struct WgradRoute {
-  int route;       // WG_ROUTE_*
-  int dtype, bias;
-  int abl;         // timing ablation (wgrad_cfg 11), per-tap only
-  int gpt;         // per-tap: groups per tile
-  int tiles;       // per-tap / K = 1: grid y
-  int64_t zk;      // per-tap: grid z
-  int64_t splits;  // per-tap / K = 1 (multi-tap: mt.splits)
-  int rps;         // per-tap / K = 1: rows per split
-  bool direct;     // the kernel writes dW / db in their final layout, no reduce
-  MtPlan mt;
-  int sw;          // multi-tap: window template (1, 2, 4)
-};
-
 static int wgrad_route(int B, int T_A, int T_B, int M, int N, int K, int S, int dil, int pad, int groups, int lda,
-                       int ldb, int pre_a, int pre_b, int dtype, int with_bias, WgradRoute* r) {
+                       int ldb, int pre_a, int pre_b, int dtype, int with_bias, WgradPlan* r) {
   VO_CHECK_ARG(!with_bias || !pre_a, "conv1d_wgrad: the fused bias gradient sums A as stored (pre_a must be off)");
   VO_CHECK_ARG(B > 0 && T_A > 0 && T_B > 0 && M > 0 && N > 0 && K >= 1 && S >= 1 && dil >= 1 && groups >= 1,
                "conv1d_wgrad: bad sizes");
@@ -880,18 +823,16 @@ static int wgrad_route(int B, int T_A, int T_B, int M, int N, int K, int S, int 
   VO_CHECK_ARG(M % ev == 0 && N % ev == 0 && lda % ev == 0 && ldb % ev == 0 && lda >= (int64_t)groups * M &&
                    ldb >= (int64_t)groups * N,
                "conv1d_wgrad: M=%d N=%d (per group, and leading dims) must be multiples of %d", M, N, ev);
-  *r = WgradRoute{};
+  *r = WgradPlan{};
   r->dtype = dtype;
   r->bias = with_bias != 0;
   r->gpt = 1;
-  r->abl = vo_tune_get("wgrad_cfg") == 11 ? 2 : 0;  // 11: no loads (timing)
   // K = 1 (Linear layers, bf16): the 128 x 128 tile kernel (wgrad_cfg 14 = the per-tap kernel, A/B)
   if (dtype == VO_BF16 && K == 1 && S == 1 && pad == 0 && groups == 1 && !pre_a && !pre_b && T_A == T_B &&
-      vo_tune_get("wgrad_cfg") != 14 && r->abl == 0) {
+      vo_tune_get("wgrad_cfg") != 14) {
     r->route = WG_ROUTE_K1;
-    k1_plan(B, T_A, M, N, &r->splits, &r->rps);
-    r->tiles = ((M + K1_T - 1) / K1_T) * ((N + K1_T - 1) / K1_T);
-    VO_CHECK_ARG(r->splits < (1 << 30) && r->tiles < 65536, "conv1d_wgrad: grid too large");
+    k1_plan(B, T_A, M, N, r);
+    VO_CHECK_ARG(r->splits < (1 << 30) && r->gy < 65536, "conv1d_wgrad: grid too large");
     r->direct = r->splits == 1;
     return VO_OK;
   }
@@ -902,28 +843,23 @@ static int wgrad_route(int B, int T_A, int T_B, int M, int N, int K, int S, int 
   const int64_t padded = (int64_t)((T_A + WM_R - 1) / WM_R) * WM_R;
   // (K = 1 on the multi-tap kernel measured 4-13 % slower at the C4 decoder's 1x1 shapes)
   // (many-tap convs -- the MSD's k = 41 layers at T_A = 65..257 -- also with up to half the chunk rows padding:
-  // the per-tap kernel restages both operands per tap, 41 times; wgrad_mt 3 = the 1/8 rule only)
-  const bool mt_ok = K >= 2 && (8 * (padded - T_A) <= T_A ||
-                                (K >= 16 && padded <= 2 * (int64_t)T_A && vo_tune_get("wgrad_mt") != 3));
+  // the per-tap kernel restages both operands per tap, 41 times)
+  const bool mt_ok = K >= 2 && (8 * (padded - T_A) <= T_A || (K >= 16 && padded <= 2 * (int64_t)T_A));
   // strided convs (S <= 4: the MSD's grouped layers) on the multi-tap kernel's wider windows (wgrad_mt 2 = off)
   const bool mt_stride = S == 1 || (S <= 4 && vo_tune_get("wgrad_mt") != 2);
-  if (dtype == VO_BF16 && mt_stride && mt_ok && vo_tune_get("wgrad_mt") != 1 && r->abl == 0) {
+  if (dtype == VO_BF16 && mt_stride && mt_ok && vo_tune_get("wgrad_mt") != 1) {
     r->route = WG_ROUTE_MULTI_TAP;
-    wgrad_mt_plan(B, T_A, M, N, K, groups, dil, &r->mt, S);
-    r->sw = S == 1 ? 1 : S == 2 ? 2 : 4;
-    VO_CHECK_ARG(r->mt.splits < (1 << 30) && r->mt.ntg * groups < 65536, "conv1d_wgrad: grid too large");
+    wgrad_mt_plan(B, T_A, M, N, K, groups, dil, S, r);
+    VO_CHECK_ARG(r->splits < (1 << 30) && r->gz < 65536, "conv1d_wgrad: grid too large");
     // wgrad_mt_plan clamps kg to the instantiated range; a kg outside it would launch nothing and leave the
     // reduce to sum an unwritten workspace
-    VO_CHECK_ARG(r->mt.kg >= 1 && r->mt.kg <= wgrad_mt_max_kg(r->mt.tm, r->sw),
-                 "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", r->mt.kg, r->mt.tm, r->sw);
+    VO_CHECK_ARG(r->kg >= 1 && r->kg <= wgrad_mt_max_kg(r->tile, r->sw),
+                 "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", r->kg, r->tile, r->sw);
     return VO_OK;
   }
   r->route = WG_ROUTE_PER_TAP;
-  r->gpt = wgrad_gpt(M, N, groups);
-  r->zk = (int64_t)K * (groups / r->gpt);
-  r->tiles = ((M * r->gpt + WG_T - 1) / WG_T) * ((N * r->gpt + WG_T - 1) / WG_T);
-  wgrad_plan(B, T_A, M, N, K, groups, &r->splits, &r->rps);
-  VO_CHECK_ARG(r->splits < (1 << 30) && r->tiles < 65536 && r->zk < 65536, "conv1d_wgrad: grid too large");
+  wgrad_plan(B, T_A, M, N, K, groups, r);
+  VO_CHECK_ARG(r->splits < (1 << 30) && r->gy < 65536 && r->gz < 65536, "conv1d_wgrad: grid too large");
   // one row split (short sequences: the encoder's 384 rows): the workgroups write dW / db in their final
   // layout -- the reduce pass would only permute (K, M, N) -> (M, N, K); wgrad_cfg 13 keeps it (A/B)
   r->direct = r->splits == 1 && vo_tune_get("wgrad_cfg") != 13;
@@ -931,16 +867,13 @@ static int wgrad_route(int B, int T_A, int T_B, int M, int N, int K, int S, int 
 }
 
 // vo_conv1d_wgrad_last_launch: this thread's last vo_conv1d_wgrad_bias call (zeroed at its entry, filled from
-// the route it launched)
+// the plan it launched)
 static thread_local int32_t g_wgrad_last[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {};
 
-static void wgrad_record(const WgradRoute& r, int32_t* rec) {
-  const bool mt = r.route == WG_ROUTE_MULTI_TAP;
-  const int64_t splits = mt ? r.mt.splits : r.splits;
+static void wgrad_record(const WgradPlan& r, int32_t* rec) {
   const int32_t v[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {
-      r.route, mt ? r.mt.tm : r.route == WG_ROUTE_K1 ? K1_T : WG_T, mt ? r.mt.kg : 0, mt ? r.sw : 0,
-      mt ? r.mt.ntg : 0, r.gpt, (int32_t)splits, mt ? WM_R * r.mt.cps : r.rps, r.direct ? 1 : 0,
-      r.direct ? 0 : splits >= 32 ? 16 : 1, r.dtype, r.bias};
+      r.route, r.tile, r.kg, r.sw, r.ntg, r.gpt, (int32_t)r.splits, r.rps, r.direct ? 1 : 0,
+      r.direct ? 0 : r.splits >= 32 ? 16 : 1, r.dtype, r.bias};
   memcpy(rec, v, sizeof(v));
 }
 
@@ -955,7 +888,7 @@ extern "C" int vo_conv1d_wgrad_last_launch(int32_t* rec, int n) { return wgrad_c
 extern "C" int vo_conv1d_wgrad_plan(int B, int T_A, int T_B, int M, int N, int K, int S, int dil, int pad, int groups,
                                     int pre_a, int pre_b, int dtype, int with_bias, int32_t* rec, int n) {
   int32_t v[VO_CONV1D_WGRAD_LAUNCH_FIELDS] = {};
-  WgradRoute r;
+  WgradPlan r;
   // the leading dimensions do not enter the routing: the narrowest valid ones
   const int rc = wgrad_route(B, T_A, T_B, M, N, K, S, dil, pad, groups, groups * M, groups * N, pre_a, pre_b, dtype,
                              with_bias, &r);
@@ -964,12 +897,36 @@ extern "C" int vo_conv1d_wgrad_plan(int B, int T_A, int T_B, int M, int N, int K
   return rc;
 }
 
+// ---- plan -> multi-tap instantiation: a fold over KG = 1 .. wgrad_mt_max_kg(TM, SW) for each (TM, SW) pair, so
+// exactly the kernels that statement names are compiled.  false: no instantiation for (pl.tile, pl.sw, pl.kg),
+// nothing launched (the caller must not reduce the unwritten workspace)
+template <int TM, int KG, int SW>
+static bool wgrad_mt_launch(const WgradArgs& p, const WgradPlan& pl, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((wgrad_mt_kernel<TM, KG, SW>), grid, dim3(256), 0, st, p, pl.chunks_per_b, pl.cps, pl.ntg);
+  return true;
+}
+template <int TM, int SW, int... I>  // I = 0 .. max KG - 1
+static bool wgrad_mt_launch_kg(const WgradArgs& p, const WgradPlan& pl, dim3 grid, hipStream_t st,
+                               std::integer_sequence<int, I...>) {
+  return ((pl.kg == I + 1 && wgrad_mt_launch<TM, I + 1, SW>(p, pl, grid, st)) || ...);
+}
+template <int TM, int SW>
+static bool wgrad_mt_launch_among(const WgradArgs& p, const WgradPlan& pl, dim3 grid, hipStream_t st) {
+  return pl.tile == TM && pl.sw == SW &&
+         wgrad_mt_launch_kg<TM, SW>(p, pl, grid, st, std::make_integer_sequence<int, wgrad_mt_max_kg(TM, SW)>{});
+}
+static bool wgrad_mt_dispatch(const WgradArgs& p, const WgradPlan& pl, dim3 grid, hipStream_t st) {
+  return wgrad_mt_launch_among<32, 1>(p, pl, grid, st) || wgrad_mt_launch_among<64, 1>(p, pl, grid, st) ||
+         wgrad_mt_launch_among<32, 2>(p, pl, grid, st) || wgrad_mt_launch_among<64, 2>(p, pl, grid, st) ||
+         wgrad_mt_launch_among<32, 4>(p, pl, grid, st) || wgrad_mt_launch_among<64, 4>(p, pl, grid, st);
+}
+
 extern "C" int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M,
                                     int N, int K, int S, int dil, int pad, int groups, int pre_a, int pre_b,
                                     float slope, int dtype, float* dw, float* db, float* workspace, void* stream) {
   memset(g_wgrad_last, 0, sizeof(g_wgrad_last));
   VO_CHECK_ARG(a && b && dw && workspace, "conv1d_wgrad: null pointer");
-  WgradRoute r;
+  WgradPlan r;
   const int rc = wgrad_route(B, T_A, T_B, M, N, K, S, dil, pad, groups, lda, ldb, pre_a, pre_b, dtype, db != nullptr,
                              &r);
   if (rc != VO_OK) return rc;
@@ -981,52 +938,28 @@ extern "C" int vo_conv1d_wgrad_bias(const void* a, int lda, int T_A, const void*
   p.bias = db != nullptr;
   p.n_w = (int64_t)groups * K * M * N;
   p.n_tot = p.n_w + (db ? (int64_t)groups * M : 0);
-  p.abl = r.abl;
   p.gpt = r.gpt;
   p.rows_per_split = r.rps;
   p.dwf = r.direct ? dw : nullptr;
   p.dbf = r.direct ? db : nullptr;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the route's kernel, then the reduce over the row splits unless the kernel wrote the result itself
+  const dim3 grid((unsigned)r.splits, (unsigned)r.gy, (unsigned)r.gz);
   if (r.route == WG_ROUTE_K1) {
-    hipLaunchKernelGGL(wgrad_k1_kernel, dim3((unsigned)r.splits, (unsigned)r.tiles), dim3(256), 0, st, p);
-    if (!r.direct) wgrad_reduce_launch(workspace, (int)r.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+    hipLaunchKernelGGL(wgrad_k1_kernel, grid, dim3(256), 0, st, p);
   } else if (r.route == WG_ROUTE_MULTI_TAP) {
-    const MtPlan& pl = r.mt;
-    bool launched;
-    if (r.sw == 1)
-      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 1>(p, pl, groups, st) : wgrad_mt_dispatch<64, 1>(p, pl, groups, st);
-    else if (r.sw == 2)
-      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 2>(p, pl, groups, st) : wgrad_mt_dispatch<64, 2>(p, pl, groups, st);
-    else
-      launched = pl.tm == 32 ? wgrad_mt_dispatch<32, 4>(p, pl, groups, st) : wgrad_mt_dispatch<64, 4>(p, pl, groups, st);
-    VO_CHECK_ARG(launched, "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", pl.kg, pl.tm, r.sw);
-    wgrad_reduce_launch(workspace, pl.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+    VO_CHECK_ARG(wgrad_mt_dispatch(p, r, grid, st),
+                 "conv1d_wgrad: no multi-tap kernel for %d taps per run (TM %d, SW %d)", r.kg, r.tile, r.sw);
+  } else if (dtype == VO_BF16) {
+    hipLaunchKernelGGL(wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, p);
+  } else if (dtype == VO_F32X3) {
+    hipLaunchKernelGGL(wgrad_kernel<bx3_t>, grid, dim3(256), 0, st, p);
   } else {
-    dim3 grid((unsigned)r.splits, (unsigned)r.tiles, (unsigned)r.zk);
-    if (dtype == VO_BF16)
-      hipLaunchKernelGGL(wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, p);
-    else if (dtype == VO_F32X3)
-      hipLaunchKernelGGL(wgrad_kernel<bx3_t>, grid, dim3(256), 0, st, p);
-    else
-      hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
-    if (!r.direct) wgrad_reduce_launch(workspace, (int)r.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
+    hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, p);
   }
+  if (!r.direct) wgrad_reduce_launch(workspace, (int)r.splits, p.n_w, p.n_tot, M, N, K, dw, db, st);
   wgrad_record(r, g_wgrad_last);
   VO_RETURN_LAUNCH();
-}
-
-extern "C" int vo_conv1d_wgrad_grouped(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M,
-                                       int N, int K, int S, int dil, int pad, int groups, int pre_a, int pre_b,
-                                       float slope, int dtype, float* dw, float* workspace, void* stream) {
-  return vo_conv1d_wgrad_bias(a, lda, T_A, b, ldb, T_B, B, M, N, K, S, dil, pad, groups, pre_a, pre_b, slope, dtype,
-                              dw, nullptr, workspace, stream);
-}
-
-extern "C" int vo_conv1d_wgrad(const void* a, int lda, int T_A, const void* b, int ldb, int T_B, int B, int M, int N,
-                               int K, int S, int dil, int pad, int pre_a, int pre_b, float slope, int dtype, float* dw,
-                               float* workspace, void* stream) {
-  return vo_conv1d_wgrad_grouped(a, lda, T_A, b, ldb, T_B, B, M, N, K, S, dil, pad, 1, pre_a, pre_b, slope, dtype, dw,
-                                 workspace, stream);
 }
 
 static int colsum_blocks(int64_t rows, int C, int* rpb) {

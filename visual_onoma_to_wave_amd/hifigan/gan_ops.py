@@ -11,7 +11,7 @@ Backward, per op:
     the strided conv kernel (dX = conv1d(dY, W, stride s, pad p));
   * loss gradients: ``vo_gan_reduce_grad``;
   * weight / bias gradients of dense and grouped convs (generator, MPD, MSD, conv_post):
-    ``vo_conv1d_wgrad[_grouped]`` (MFMA over transposed LDS reads) and ``vo_colsum``;
+    ``vo_conv1d_wgrad_bias`` (MFMA over transposed LDS reads) and ``vo_colsum``;
   * input gradient of strided / grouped discriminator convs: the conv kernel once per stride
     phase (taps of the phase reversed, channel roles swapped, rows interleaved) -- ``_dgrad``;
   * the mel-loss STFT backward: ``vo_stft_mel_bwd`` (per frame: the spectrum recomputed, the
@@ -361,7 +361,7 @@ class ConvFn(torch.autograd.Function):
         grouped_ok = g == 1 or (spec.transposed is None and x.shape[-1] == ci and (ci // g) % 8 == 0
                                 and (w.shape[0] // g) % 8 == 0)
         if (need_w or need_b) and grouped_ok:
-            # weight / bias gradient on MFMA (vo_conv1d_wgrad[_grouped], vo_colsum)
+            # weight / bias gradient on MFMA (vo_conv1d_wgrad_bias, vo_colsum)
             gzc = _pad_channels(gz.to(x.dtype))
             if need_w:
                 if spec.transposed is not None:

@@ -1977,7 +1977,7 @@ def char_features(energy, fstats, durations, n_bins, flat=False):
 
 def conv1d_wgrad(a, b, K, S=1, dil=1, pad=0, pre_a=None, pre_b=None, transposed=False, groups=1, with_bias=False,
                  split=False):
-    """Weight gradient on MFMA (vo_conv1d_wgrad).  Conv1d: a = dY (B, T_out, Co), b = x (B, T_in, Ci)
+    """Weight gradient on MFMA (vo_conv1d_wgrad_bias).  Conv1d: a = dY (B, T_out, Co), b = x (B, T_in, Ci)
     -> dW (Co, Ci / groups, K).  ConvTranspose1d (transposed=True): a = x (B, T_in, Ci), b = dY
     (B, T_up, Co) -> dW (Ci, Co, K).  pre_a / pre_b: leaky-ReLU slope applied to that operand
     (None = identity).  with_bias (conv form): also the bias gradient, column sums of a, from the
@@ -2009,7 +2009,7 @@ def conv1d_wgrad(a, b, K, S=1, dil=1, pad=0, pre_a=None, pre_b=None, transposed=
         dt = VO_F32X3
     _lib.check(L.vo_conv1d_wgrad_bias(_ptr(a), M, T_A, _ptr(b), N, T_B, B, mg, ng, K, S, dil, pad, groups,
                                       int(pre_a is not None), int(pre_b is not None), float(slope), dt,
-                                      _ptr(w), _ptr(db), _ptr(ws), _stream(a)), "vo_conv1d_wgrad")
+                                      _ptr(w), _ptr(db), _ptr(ws), _stream(a)), "vo_conv1d_wgrad_bias")
     return (w, db) if with_bias else w
 
 
